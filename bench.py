@@ -30,6 +30,9 @@ h-capped bandwidth regime.  At N > 1 the line is self-validating: before timing 
 rank-dependent constant image is reduced and checked (`reduce_selftest`), after timing the reduced frame is compared with
 the same snapshot rendered whole on rank 0's GPU (`reduce_check`); a failure exits non-zero.
 
+`--dump-outputs DIR` writes the last timed step's frame (rgba) and render target (image) as float32 .npy files for comparing
+two builds output for output; the inputs are generated from fixed seeds, so the same arguments give the same inputs.
+
 At N = 1 the process never imports torch (north_star: no PyTorch on this path); torch.distributed is used at
 N > 1 only, as the launcher's rendezvous for the 128-byte RCCL id, the barrier and the max-over-ranks time.
 """
@@ -56,6 +59,7 @@ KERNEL_SYMBOL = {"stream": "splat_stream_kernel", "mid": "splat_narrow_gather_ke
 # one ncclReduce of the R^2 x C float32 image onto the root over xGMI (ring: 7 steps of 1/8 of the image per link, ~153 GB/s per
 # link and ~20 us per step): an ESTIMATE -- no multi-GPU box was available to this build -- used only by `projected_speedup_1to8`
 REDUCE_ESTIMATE_MS = 0.3
+DUMP_LIMIT_BYTES = 64_000_000   # --dump-outputs: all .npy files of one run together
 
 
 def parse():
@@ -87,7 +91,14 @@ def parse():
     ap.add_argument("--headline-only", action="store_true",
                     help="only the headline frames: no extra configurations, no CPU baseline (what the profiler runs, so "
                          "that every kernel instance in a profile belongs to the headline workload)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps rank 0 writes what the last one computed as float32 DIR/<name>.npy: rgba (the "
+                         "colormapped frame the step returns) and image (the float render target it was mapped from); above "
+                         f"{DUMP_LIMIT_BYTES // 10**6} MB in all, a fixed seeded sample of pixels (DIR/pixel_index.npy)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def camera(scale):
@@ -176,6 +187,25 @@ def fragment_roofline(frags_by_kernel, kernel_ms, frame_ms):
     return {"bound": "valu_f32", "achieved": tf, "peak": VALU_F32_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": tf / VALU_F32_PEAK_TFLOPS,
             "flop_per_frame": flop_total, "per_kernel": per,
             "note": "useful flop = fragments x canonical FMAs (1 nearest, 2 bilinear) x 2; set-up, addressing and atomics are overhead"}
+
+
+def dump_outputs(out_dir, images, limit=DUMP_LIMIT_BYTES, seed=0):
+    """Write each (R, R, C) image as out_dir/<name>.npy in float32.  When they would exceed `limit` bytes together, every
+    file holds the same seeded sample of pixels instead, (k, C) in pixel order, and out_dir/pixel_index.npy (float64) holds
+    their flat indices: the sample depends only on R, the channel counts and `seed`, so two builds dump the same pixels."""
+    os.makedirs(out_dir, exist_ok=True)
+    header = 128                                     # bytes of an .npy header for these shapes
+    rows, cols = next(iter(images.values())).shape[:2]
+    n_pix = rows * cols
+    per_pixel = sum(4 * a.shape[2] for a in images.values())
+    out = {name: np.asarray(a, dtype=np.float32) for name, a in images.items()}
+    if n_pix * per_pixel + header * len(images) > limit:
+        n_keep = (limit - header * (len(images) + 1)) // (per_pixel + 8)
+        idx = np.sort(np.random.default_rng(seed).choice(n_pix, size=n_keep, replace=False))
+        out = {name: a.reshape(n_pix, -1)[idx] for name, a in out.items()}
+        out["pixel_index"] = idx.astype(np.float64)
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
 
 
 def main():
@@ -270,7 +300,7 @@ def main():
     t0 = time.perf_counter()
     for _ in range(args.steps):
         ts = time.perf_counter()
-        frame(True)
+        last = frame(True)
         step_s.append(time.perf_counter() - ts)
     barrier()
     elapsed = time.perf_counter() - t0
@@ -278,6 +308,9 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs and rank == 0:
+        # before any further frame: at N > 1 the render target is still the reduced image the colormap read
+        dump_outputs(args.dump_outputs, {"rgba": last, "image": ctx.read_image()})
 
     # ---- N > 1: the reduced frame, for the check against the whole snapshot below (one more frame, untimed) ----------
     reduced_image = None

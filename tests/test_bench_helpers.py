@@ -86,3 +86,28 @@ def test_reduce_selftest_pattern_sums_exactly_and_images_compare():
     assert not bench.compare_images(bad, whole, 8)["ok"]
     dust = whole.copy(); dust[0, 0, 0] = 1e-30
     assert not bench.compare_images(dust, whole, 8)["ok"]
+
+
+def test_dump_outputs_whole_then_seeded_sample_within_the_limit(tmp_path):
+    rs = np.random.RandomState(0)
+    # the headline (density, 1024^2) fits: both images whole, as float32
+    rgba = rs.randint(0, 256, (1024, 1024, 4)).astype(np.uint8)
+    image = rs.uniform(0.0, 1.0, (1024, 1024, 2)).astype(np.float32)
+    bench.dump_outputs(str(tmp_path / "small"), {"rgba": rgba, "image": image})
+    got = {n: np.load(tmp_path / "small" / (n + ".npy")) for n in ("rgba", "image")}
+    assert got["rgba"].dtype == np.float32 and np.array_equal(got["rgba"], rgba)
+    assert np.array_equal(got["image"], image) and not (tmp_path / "small" / "pixel_index.npy").exists()
+    # rgb at 2048^2 (BASELINE configs[4]) does not: the same seeded pixels in every file, all files within the limit
+    rgba = rs.randint(0, 256, (2048, 2048, 4)).astype(np.uint8)
+    image = rs.uniform(0.0, 1.0, (2048, 2048, 4)).astype(np.float32)
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), {"rgba": rgba, "image": image})
+        files = sorted((tmp_path / run).iterdir())
+        assert [f.name for f in files] == ["image.npy", "pixel_index.npy", "rgba.npy"]
+        assert sum(f.stat().st_size for f in files) <= bench.DUMP_LIMIT_BYTES
+    idx = np.load(tmp_path / "a" / "pixel_index.npy")
+    assert idx.dtype == np.float64 and np.array_equal(idx, np.load(tmp_path / "b" / "pixel_index.npy"))
+    assert len(idx) > 10**6 and np.all(np.diff(idx) > 0)
+    flat = idx.astype(np.int64)
+    assert np.array_equal(np.load(tmp_path / "a" / "rgba.npy"), rgba.reshape(-1, 4)[flat].astype(np.float32))
+    assert np.array_equal(np.load(tmp_path / "a" / "image.npy"), image.reshape(-1, 4)[flat])

@@ -67,11 +67,9 @@ def _worker(rank, world, port, out_dir):
 
 
 def test_two_rank_sharded_render_matches_single(tmp_path):
-    import torch.multiprocessing as mp
-    port = _free_port()
-    mp.spawn(_worker, args=(2, port, str(tmp_path)), nprocs=2, join=True)
     sys.path.insert(0, os.path.join(ROOT, "tests"))
-    from conftest import make_cloud
+    from conftest import make_cloud, spawn_ranks
+    spawn_ranks(_worker, 2, _free_port(), str(tmp_path))
     from oracle import oracle_c, oracle_np
     from topsy_amd import kernel_lut
     pos, h, m, q, _ = make_cloud(30011, seed=11)

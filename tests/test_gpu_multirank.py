@@ -56,8 +56,8 @@ def test_two_gpu_sharded_render_matches_single_gpu(tmp_path):
     from topsy_amd import _native, kernel_lut
     if _native.device_count() < 2:
         pytest.skip("needs two GPUs")
-    import torch.multiprocessing as mp
-    mp.spawn(_worker, args=(2, _free_port(), str(tmp_path)), nprocs=2, join=True)
+    from conftest import spawn_ranks
+    spawn_ranks(_worker, 2, _free_port(), str(tmp_path))
     n, R = 2_000_000, 512
     ctx = _native.Context(R, 2, device_id=0)
     ctx.set_kernel_mips(kernel_lut.kernel_mips())
