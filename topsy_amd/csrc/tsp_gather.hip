@@ -55,14 +55,160 @@ __device__ __forceinline__ void fmac_plain(float &acc, float x, float y) {     /
     asm volatile("v_fmac_f32_e32 %0, %1, %2" : "+v"(acc) : "v"(x), "v"(y));
 }
 
+// ---- the row walk as one asm body (option h2_walk = 1; single channel, W = 1, the 64 x 32 / 64 x 16 strips at 8 waves/SIMD) -------
+// The C++ walk below copies top = bot on every texel-row change and forms the prefetch address with a v_add: 4 vector instructions
+// per change.  Here the two rolling rows (r0, r1) swap roles instead, and the prefetch reads texel row r0 + 2 + i at an immediate
+// offset 260 (i mod 4) + 260 from a base stepped once every four changes: 2.25 vector instructions per change.  The walk is a state
+// machine whose state s = (changes so far) mod 4 is the program counter: state s has its own copy of the row code, with
+// top = r(s & 1), bot = r(~s & 1) and its own prefetch offset.  A group of four rows without a texel-row change runs its eight FMAs
+// without a per-row bit test (one s_and for the group); a group with changes takes the per-row tested copy.  Every operation on
+// the accumulators, the rolling rows and the prefetch is the C++ walk's, in the same order, so the float32 strip sums are
+// bit-identical (the jmpmask double step included).  The asm owns: its LDS waits (lgkmcnt; LDS returns in order), the row factors
+// (two ds_read_b32 per group, fetched one group ahead into two register pairs, as in the C++ walk's JIT path), and the DPP rule
+// (a VGPR a VALU wrote is not a DPP source within two wait states: the DPP sources here are the row factors, written by LDS only).
+#define H2A_S_(x) #x
+#define H2A_S(x) H2A_S_(x)
+#define H2A_TOP0 "%[r0]"
+#define H2A_TOP1 "%[r1]"
+#define H2A_TOP2 "%[r0]"
+#define H2A_TOP3 "%[r1]"
+#define H2A_BOT0 "%[r1]"
+#define H2A_BOT1 "%[r0]"
+#define H2A_BOT2 "%[r1]"
+#define H2A_BOT3 "%[r0]"
+#define H2A_NEXT0 "1"
+#define H2A_NEXT1 "2"
+#define H2A_NEXT2 "3"
+#define H2A_NEXT3 "0"
+#define H2A_STEP0 ""
+#define H2A_STEP1 ""
+#define H2A_STEP2 ""
+#define H2A_STEP3 "v_add_u32 %[va], 0x410, %[va]\n\t"      /* 4 texel rows: the base moves on after the fourth change */
+#define H2A_DPP(q) " quad_perm:[" #q "," #q "," #q "," #q "] row_mask:0xf bank_mask:0xf\n\t"
+// pixel row t in state S: acc += gy*top ; acc += fy*bot, the factors of row t from quad lane q of the group's factor pair p
+#define H2A_ROW(S, t, q, p)                                                                                    \
+    "v_fmac_f32_dpp %[a" #t "], %[gy" #p "], " H2A_TOP##S H2A_DPP(q)                                           \
+    "v_fmac_f32_dpp %[a" #t "], %[fy" #p "], " H2A_BOT##S H2A_DPP(q)
+// the same row behind its texel-row test: a change leaves to .Lh2c<S>_<t> and resumes at .Lh2r<S+1>_<t>
+#define H2A_TROW(S, t, q, p)                                                                                   \
+    "s_bitcmp1_b32 %[chg], " #t "\n\t"                                                                         \
+    "s_cbranch_scc1 .Lh2c" #S "_" #t "_%=\n"                                                                   \
+    ".Lh2r" #S "_" #t "_%=:\n\t" H2A_ROW(S, t, q, p)
+// group K (rows t0..t3, factor pair p) in state S: fetch the next group's factors (pair pn), skip an uncovered group, run the
+// eight FMAs untested when the group has no change.  The fast path falls through to the next group's head.
+#define H2A_GROUP(S, K, p, pn, t0, t1, t2, t3)                                                                 \
+    ".Lh2g" #S "_" #K "_%=:\n\t"                                                                               \
+    "ds_read_b32 %[fy" #pn "], %[rt] offset:32*(" #K "+1)\n\t"                                                 \
+    "ds_read_b32 %[gy" #pn "], %[rt] offset:32*(" #K "+1)+4\n\t"                                               \
+    "s_and_b32 %[tmp], %[cov], 15<<(4*" #K ")\n\t"                                                             \
+    "s_cbranch_scc0 .Lh2k" #S "_" #K "_%=\n\t"                                                                 \
+    "s_waitcnt lgkmcnt(2)\n\t"                  /* this group's factors (only the next group's two reads are younger) */ \
+    "s_and_b32 %[tmp], %[chg], 15<<(4*" #K ")\n\t"                                                             \
+    "s_cbranch_scc1 .Lh2s" #S "_" #K "_%=\n\t"                                                                 \
+    H2A_ROW(S, t0, 0, p) H2A_ROW(S, t1, 1, p) H2A_ROW(S, t2, 2, p) H2A_ROW(S, t3, 3, p)
+#define H2A_GROUP_LAST(S, K, p, t0, t1, t2, t3)                                                                \
+    ".Lh2g" #S "_" #K "_%=:\n\t"                                                                               \
+    "s_and_b32 %[tmp], %[cov], 15<<(4*" #K ")\n\t"                                                             \
+    "s_cbranch_scc0 .Lh2end_%=\n\t"                                                                            \
+    "s_waitcnt lgkmcnt(0)\n\t"                                                                                 \
+    "s_and_b32 %[tmp], %[chg], 15<<(4*" #K ")\n\t"                                                             \
+    "s_cbranch_scc1 .Lh2s" #S "_" #K "_%=\n\t"                                                                 \
+    H2A_ROW(S, t0, 0, p) H2A_ROW(S, t1, 1, p) H2A_ROW(S, t2, 2, p) H2A_ROW(S, t3, 3, p)                        \
+    "s_branch .Lh2end_%=\n"
+// out of line, group K of state S: the tested rows, then the next group (N: its label, `end` after the last);  the skip of an
+// uncovered group (the covered rows are contiguous: none below -> the next group, none above -> done)
+#define H2A_SLOW(S, K, N, p, t0, t1, t2, t3)                                                                   \
+    ".Lh2s" #S "_" #K "_%=:\n\t"                                                                               \
+    H2A_TROW(S, t0, 0, p) H2A_TROW(S, t1, 1, p) H2A_TROW(S, t2, 2, p) H2A_TROW(S, t3, 3, p)                    \
+    "s_branch .Lh2" #N "_%=\n"
+#define H2A_SKIP(S, K, N)                                                                                      \
+    ".Lh2k" #S "_" #K "_%=:\n\t"                                                                               \
+    "s_lshr_b32 %[tmp], %[cov], 4*(" #K "+1)\n\t"                                                              \
+    "s_cbranch_scc0 .Lh2end_%=\n\t"                                                                            \
+    "s_branch .Lh2" #N "_%=\n"
+// texel-row change at row t in state S: the row on top becomes the new bottom row = lerp(prefetched pair) (v_mul + v_fmac, the
+// C++ walk's), the pair of the row after it loads; a double step (jmpmask) clears its bit and changes once more from state S + 1
+#define H2A_CHG(S, t)                                                                                          \
+    ".Lh2c" #S "_" #t "_%=:\n\t"                                                                               \
+    "s_waitcnt lgkmcnt(0)\n\t"                                                                                 \
+    "v_mul_f32 " H2A_TOP##S ", %[nx], %[gx]\n\t"                                                               \
+    "v_fmac_f32 " H2A_TOP##S ", %[ny], %[fx]\n\t"                                                              \
+    "ds_read_b32 %[nx], %[va] offset:260*(" #S "+1)\n\t"                                                       \
+    "ds_read_b32 %[ny], %[va] offset:260*(" #S "+1)+4\n\t"                                                     \
+    H2A_STEP##S                                                                                                \
+    "s_bitcmp1_b32 %[jmp], " #t "\n\t"                                                                         \
+    "s_cbranch_scc0 .Lh2r" H2A_NEXT##S "_" #t "_%=\n\t"                                                        \
+    "s_bitset0_b32 %[jmp], " #t "\n\t"                                                                         \
+    "s_branch .Lh2c" H2A_NEXT##S "_" #t "_%=\n"
+#define H2A_CHG4(S, a, b, c, d) H2A_CHG(S, a) H2A_CHG(S, b) H2A_CHG(S, c) H2A_CHG(S, d)
+// one state: groups (fall-through), then its out-of-line code
+#define H2A_STATE16(S)                                                                                         \
+    H2A_GROUP(S, 0, 0, 1, 0, 1, 2, 3) H2A_GROUP(S, 1, 1, 0, 4, 5, 6, 7) H2A_GROUP(S, 2, 0, 1, 8, 9, 10, 11)     \
+    H2A_GROUP_LAST(S, 3, 1, 12, 13, 14, 15)                                                                    \
+    H2A_SLOW(S, 0, g##S##_1, 0, 0, 1, 2, 3) H2A_SLOW(S, 1, g##S##_2, 1, 4, 5, 6, 7)                            \
+    H2A_SLOW(S, 2, g##S##_3, 0, 8, 9, 10, 11) H2A_SLOW(S, 3, end, 1, 12, 13, 14, 15)                           \
+    H2A_SKIP(S, 0, g##S##_1) H2A_SKIP(S, 1, g##S##_2) H2A_SKIP(S, 2, g##S##_3)                                 \
+    H2A_CHG4(S, 0, 1, 2, 3) H2A_CHG4(S, 4, 5, 6, 7) H2A_CHG4(S, 8, 9, 10, 11) H2A_CHG4(S, 12, 13, 14, 15)
+#define H2A_STATE32(S)                                                                                         \
+    H2A_GROUP(S, 0, 0, 1, 0, 1, 2, 3) H2A_GROUP(S, 1, 1, 0, 4, 5, 6, 7) H2A_GROUP(S, 2, 0, 1, 8, 9, 10, 11)     \
+    H2A_GROUP(S, 3, 1, 0, 12, 13, 14, 15) H2A_GROUP(S, 4, 0, 1, 16, 17, 18, 19)                                \
+    H2A_GROUP(S, 5, 1, 0, 20, 21, 22, 23) H2A_GROUP(S, 6, 0, 1, 24, 25, 26, 27)                                \
+    H2A_GROUP_LAST(S, 7, 1, 28, 29, 30, 31)                                                                    \
+    H2A_SLOW(S, 0, g##S##_1, 0, 0, 1, 2, 3) H2A_SLOW(S, 1, g##S##_2, 1, 4, 5, 6, 7)                            \
+    H2A_SLOW(S, 2, g##S##_3, 0, 8, 9, 10, 11) H2A_SLOW(S, 3, g##S##_4, 1, 12, 13, 14, 15)                      \
+    H2A_SLOW(S, 4, g##S##_5, 0, 16, 17, 18, 19) H2A_SLOW(S, 5, g##S##_6, 1, 20, 21, 22, 23)                    \
+    H2A_SLOW(S, 6, g##S##_7, 0, 24, 25, 26, 27) H2A_SLOW(S, 7, end, 1, 28, 29, 30, 31)                         \
+    H2A_SKIP(S, 0, g##S##_1) H2A_SKIP(S, 1, g##S##_2) H2A_SKIP(S, 2, g##S##_3) H2A_SKIP(S, 3, g##S##_4)         \
+    H2A_SKIP(S, 4, g##S##_5) H2A_SKIP(S, 5, g##S##_6) H2A_SKIP(S, 6, g##S##_7)                                 \
+    H2A_CHG4(S, 0, 1, 2, 3) H2A_CHG4(S, 4, 5, 6, 7) H2A_CHG4(S, 8, 9, 10, 11) H2A_CHG4(S, 12, 13, 14, 15)      \
+    H2A_CHG4(S, 16, 17, 18, 19) H2A_CHG4(S, 20, 21, 22, 23) H2A_CHG4(S, 24, 25, 26, 27) H2A_CHG4(S, 28, 29, 30, 31)
+// entry: the first group's factors and the pair of texel row r0 + 2 load; exit: nothing of the asm's left in flight
+#define H2A_HEAD                                                                                               \
+    "ds_read_b32 %[nx], %[va]\n\t"                                                                             \
+    "ds_read_b32 %[ny], %[va] offset:4\n\t"                                                                    \
+    "ds_read_b32 %[fy0], %[rt]\n\t"                                                                            \
+    "ds_read_b32 %[gy0], %[rt] offset:4\n"
+#define H2A_TAIL ".Lh2end_%=:\n\t" "s_waitcnt lgkmcnt(0)"
+#define H2A_A4(a, i, j, k, l) [a##i] "+v"(acc[i][0]), [a##j] "+v"(acc[j][0]), [a##k] "+v"(acc[k][0]), [a##l] "+v"(acc[l][0])
+#define H2A_OPERANDS                                                                                           \
+    [r0] "+v"(top), [r1] "+v"(bot), [nx] "=&v"(nx), [ny] "=&v"(ny), [fy0] "=&v"(fy0), [gy0] "=&v"(gy0),         \
+    [fy1] "=&v"(fy1), [gy1] "=&v"(gy1), [va] "+v"(va), [jmp] "+s"(jmp), [tmp] "=&s"(tmp)
+#define H2A_INPUTS [gx] "v"(gx), [fx] "v"(fx), [rt] "v"(rt), [cov] "s"(cov), [chg] "s"(chg)
+
+// acc: the strip's accumulators; top / bot: x-interpolated texel rows r0, r0 + 1 of the first covered row; va: LDS byte address of
+// this lane's pair (r0 + 2, c); rt: LDS byte address of this lane's slot in the hit's row-factor table; masks as in the C++ walk
+template <int HR>
+__device__ __forceinline__ void h2_walk_asm(float (&acc)[HR][1], float top, float bot, float gx, float fx, int va, int rt,
+                                            unsigned cov, unsigned chg, unsigned jmp) {
+    float nx, ny, fy0, gy0, fy1, gy1;
+    unsigned tmp;
+    if constexpr (HR == 16) {
+        asm volatile(H2A_HEAD H2A_STATE16(0) H2A_STATE16(1) H2A_STATE16(2) H2A_STATE16(3) H2A_TAIL
+                     : H2A_A4(a, 0, 1, 2, 3), H2A_A4(a, 4, 5, 6, 7), H2A_A4(a, 8, 9, 10, 11), H2A_A4(a, 12, 13, 14, 15),
+                       H2A_OPERANDS
+                     : H2A_INPUTS
+                     : "memory", "scc");
+    } else {
+        static_assert(HR == 32, "asm row walk: 64 x 16 and 64 x 32 strips");
+        asm volatile(H2A_HEAD H2A_STATE32(0) H2A_STATE32(1) H2A_STATE32(2) H2A_STATE32(3) H2A_TAIL
+                     : H2A_A4(a, 0, 1, 2, 3), H2A_A4(a, 4, 5, 6, 7), H2A_A4(a, 8, 9, 10, 11), H2A_A4(a, 12, 13, 14, 15),
+                       H2A_A4(a, 16, 17, 18, 19), H2A_A4(a, 20, 21, 22, 23), H2A_A4(a, 24, 25, 26, 27), H2A_A4(a, 28, 29, 30, 31),
+                       H2A_OPERANDS
+                     : H2A_INPUTS
+                     : "memory", "scc");
+    }
+}
+
 constexpr int PT_ROWS = 66;          // LDS kernel image rows: 64 + two clamp-to-edge copies of row 63 (for r + 1, r + 2)
 constexpr int PT_STRIDE = 65;        // floats per row: 64 + one clamp-to-edge copy of column 63 (for c + 1); odd -> no bank conflicts
 
 constexpr int H2T = 256;             // threads per workgroup of kernel H2: 4 waves = 2 x 2 strips sharing one pair table
 
 // CNT: fragment counting compiled in (tsp_set_option "count_fragments"); the product instantiation carries none of it
-template <int MODE, int NACC, int W, int HR, int OCC, bool CNT>
+// AW: the row walk as one asm body (h2_walk_asm; option h2_walk), single channel, one column register
+template <int MODE, int NACC, int W, int HR, int OCC, bool CNT, bool AW>
 __global__ __launch_bounds__(H2T, OCC) void splat_huge2_kernel(TileArgs a) {
+    static_assert(!AW || (NACC == 1 && W == 1 && (HR == 16 || HR == 32)), "asm row walk: single channel, 64 x 16 / 64 x 32 strips");
     constexpr int C = (MODE == TSP_MODE_RGB) ? 4 : 2;
     constexpr int NW = (MODE == TSP_MODE_RGB) ? 2 : 1;
     constexpr int TW = 2 * 64 * W, TH = 2 * HR;            // tile: 2 x 2 wave strips of (64 W) x HR pixels
@@ -272,6 +418,18 @@ __global__ __launch_bounds__(H2T, OCC) void splat_huge2_kernel(TileArgs a) {
                 gxs[w] = (1.0f - fr) * cw;
                 if (CNT) ncov_x += covered ? 1 : 0;
             }
+            if constexpr (AW) {
+                typedef const __attribute__((address_space(3))) float LdsF;
+                const int r_off = __builtin_amdgcn_readlane(r512, __ffs((int)covmask) - 1 + HR * hh);
+                auto lerp_at = [&](int byteoff) -> float {      // = lerp(0, pair_at(0, byteoff)) of the C++ walk
+                    const float *t = reinterpret_cast<const float *>(PTb + byteoff + caddr[0]);
+                    return __builtin_fmaf(t[1], fxs[0], t[0] * gxs[0]);
+                };
+                const float t0 = lerp_at(r_off), t1 = lerp_at(r_off + PT_STRIDE * 4);
+                const int va = (int)(unsigned)(unsigned long long)(LdsF *)PT + r_off + 2 * PT_STRIDE * 4 + caddr[0];
+                const int rtq = (int)(unsigned)(unsigned long long)(LdsF *)(const float *)rt_quad_h;
+                h2_walk_asm<HR>(acc, t0, t1, gxs[0], fxs[0], va, rtq, (unsigned)covmask, (unsigned)chgmask, (unsigned)jmpmask);
+            } else {
             float top[W], bot[W];
             float2 nxt[W];                              // prefetched pair of texel row r + 2
             auto pair_at = [&](int w, int byteoff) -> float2 {
@@ -338,7 +496,8 @@ __global__ __launch_bounds__(H2T, OCC) void splat_huge2_kernel(TileArgs a) {
             // footprints of 64 px and up, whose texel rows change every 1-8 pixel rows below 512 px.)
             // (Round 5: a second, test-free copy of a group's eight FMAs for the groups without a texel-row change -- the per-row bit
             // tests are three quarters of this kernel's scalar instructions -- made the register allocator spill around every
-            // footprint's set-up at the control-flow merges: 32.7 -> 49 ms at 1e9 particles.  One code path per row it stays.)
+            // footprint's set-up at the control-flow merges: 32.7 -> 49 ms at 1e9 particles.  One code path per row it stays here;
+            // h2_walk_asm has both, its registers allocated by hand.)
 #define TSP_H2_GROUP(K)                                                                                        \
             if constexpr ((K) < NG) {                                                                          \
                 if constexpr (JIT && (K) + 1 < NG) rowf[((K) + 1) & 1] = rt_quad_h[4 * ((K) + 1)];               \
@@ -353,6 +512,7 @@ __global__ __launch_bounds__(H2T, OCC) void splat_huge2_kernel(TileArgs a) {
             TSP_H2_GROUP(12) TSP_H2_GROUP(13) TSP_H2_GROUP(14) TSP_H2_GROUP(15)
 #undef TSP_H2_GROUP
 #undef TSP_H2_ROW
+            }      // (C++ walk)
             if (CNT) n_frag += (unsigned long long)(ncov_x * __popcll((unsigned long long)covmask));
 #ifdef TSP_H2_DEBUG      // analysis build: (footprint, strip) pairs, covered rows and texel-row changes instead of the S / G fragment counts
             if (CNT && lane == 0) {
@@ -1258,8 +1418,13 @@ static int launch_huge2(tsp_context *ctx, TileArgs ta, long long n_huge) {
     split = (int)std::min<long long>(split, std::max<long long>(batches, 1));
     ta.split = split;
     ta.tiles_x = htiles_x;
-    if (ta.count_frag) hipLaunchKernelGGL((splat_huge2_kernel<MODE, NACC, W, HR, OCC, true>), dim3(htiles * split), dim3(H2T), smem, ctx->stream, ta);
-    else hipLaunchKernelGGL((splat_huge2_kernel<MODE, NACC, W, HR, OCC, false>), dim3(htiles * split), dim3(H2T), smem, ctx->stream, ta);
+    // the asm row walk (option h2_walk) exists for the single-channel strips at 8 waves/SIMD, the density frame's two shapes
+    constexpr bool AW_BUILT = NACC == 1 && W == 1 && OCC == 8;
+    if (AW_BUILT && ctx->h2_walk) {
+        if (ta.count_frag) hipLaunchKernelGGL((splat_huge2_kernel<MODE, NACC, W, HR, OCC, true, AW_BUILT>), dim3(htiles * split), dim3(H2T), smem, ctx->stream, ta);
+        else hipLaunchKernelGGL((splat_huge2_kernel<MODE, NACC, W, HR, OCC, false, AW_BUILT>), dim3(htiles * split), dim3(H2T), smem, ctx->stream, ta);
+    } else if (ta.count_frag) hipLaunchKernelGGL((splat_huge2_kernel<MODE, NACC, W, HR, OCC, true, false>), dim3(htiles * split), dim3(H2T), smem, ctx->stream, ta);
+    else hipLaunchKernelGGL((splat_huge2_kernel<MODE, NACC, W, HR, OCC, false, false>), dim3(htiles * split), dim3(H2T), smem, ctx->stream, ta);
     TSP_HIP(hipGetLastError());
     return TSP_OK;
 }
