@@ -565,21 +565,25 @@ def test_block_draws_in_record_slices(native, mips, mode_name):
     ctx.close()
 
 
+@pytest.mark.parametrize("overlap", [0, 1])
 @pytest.mark.parametrize("stage", [1, 2])
-def test_failed_block_leaves_the_accumulator_as_it_found_it(native, mips, stage):
+def test_failed_block_leaves_the_accumulator_as_it_found_it(native, mips, stage, overlap):
     """tsp_render draws a block whole or not at all: a failure injected after kernel S (stage 1: its small footprints are already
     in the accumulator) or after kernel G (stage 2) returns the error and restores the float64 accumulator, the float32 image, the
-    channel layout and the statistics of the previous call -- for a clearing block and for an accumulating one."""
-    n, R = 300_000, 512
+    channel layout and the statistics of the previous call -- for a clearing block and for an accumulating one.  With option
+    overlap_mid_huge the mid kernels run on the second stream and can still be adding into the accumulator when the block fails:
+    stage 2 then draws ~2e6 mid footprints of ~56 px (several ms of kernel N), and the restore has to wait for them."""
+    n, R = (300_000 if stage == 1 else 2_000_000), 512
     rs = np.random.RandomState(33)
     pos = (rs.normal(size=(n, 3)) * 60.0).astype(np.float32)
-    h = rs.choice(np.asarray([1.0, 2.5, 11.0, 30.0], dtype=np.float32), size=n)
+    h = rs.choice(np.asarray([1.0, 2.5, 11.0, 30.0], dtype=np.float32), size=n, p=None if stage == 1 else [0.05, 0.05, 0.85, 0.05])
     m = rs.uniform(0.5, 1.5, n).astype(np.float32)
     M, sf = camera(200.0)
     M2, sf2 = camera(120.0)
     half = n // 2
     ctx = native.Context(R, 2)
     ctx.set_kernel_mips(mips)
+    ctx.set_option("overlap_mid_huge", overlap)
     ctx.upload_particles(pos[:, 0], pos[:, 1], pos[:, 2], h, m)
     starts, lens = np.asarray([0], dtype=np.int64), np.asarray([half], dtype=np.int64)
     ctx.render(M, sf, starts, lens, clear=True)                  # frame A: the first half

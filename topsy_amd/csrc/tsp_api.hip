@@ -31,6 +31,67 @@ int ensure_array(float **p, int64_t n) {
     return TSP_OK;
 }
 
+int alloc_group(tsp_context *ctx, std::initializer_list<DeviceBuffer> bufs, std::initializer_list<Capacity> caps) {
+    for (const Capacity &c : caps) c.set(0);
+    hipError_t freed = hipSuccess;
+    for (const DeviceBuffer &b : bufs) {
+        if (*b.p) {
+            const hipError_t e = hipFree(*b.p);
+            if (freed == hipSuccess) freed = e;
+        }
+        *b.p = nullptr;
+    }
+    if (freed != hipSuccess) {
+        set_error("hipFree failed before allocating %s: %s", bufs.begin()->site, hipGetErrorString(freed));
+        return TSP_EHIP;
+    }
+    for (const DeviceBuffer &b : bufs) {
+        int rc = TSP_OK;
+        if (ctx->debug_fail_alloc > 0 && --ctx->debug_fail_alloc == 0) {
+            set_error("injected allocation failure at %s (debug_fail_alloc)", b.site);
+            rc = TSP_ENOMEM;
+        } else {
+            const hipError_t e = hipMalloc(b.p, b.bytes);
+            if (e != hipSuccess) {
+                (void)hipGetLastError();     // (a later launch check must not report this allocation)
+                *b.p = nullptr;
+                set_error("hipMalloc of %zu bytes failed at %s: %s", b.bytes, b.site, hipGetErrorString(e));
+                rc = e == hipErrorOutOfMemory ? TSP_ENOMEM : TSP_EHIP;
+            }
+        }
+        if (rc != TSP_OK) {      // the group is all or nothing
+            for (const DeviceBuffer &q : bufs) {
+                if (*q.p) (void)hipFree(*q.p);
+                *q.p = nullptr;
+            }
+            return rc;
+        }
+    }
+    for (const Capacity &c : caps) c.set(c.value);
+    return TSP_OK;
+}
+
+int check_workspace(const tsp_context *ctx) {
+    const Workspace &ws = ctx->ws;
+    struct Pair { int64_t cap; const void *p; const char *name; } pairs[] = {
+        {ws.mid_capacity, ws.mid_geom, "mid_geom"}, {ws.mid_capacity, ws.mid_w, "mid_w"},
+        {ws.huge_capacity, ws.huge_geom, "huge_geom"}, {ws.huge_capacity, ws.huge_w, "huge_w"},
+        {ws.hband_stride, ws.hband_geom, "hband_geom"}, {ws.hband_stride, ws.hband_w, "hband_w"}, {ws.hband_stride, ws.hband_count, "hband_count"},
+        {ws.hband_bands, ws.hband_geom, "hband_geom"},
+        {ws.mband_capacity, ws.mband_geom, "mband_geom"}, {ws.mband_capacity, ws.mband_w, "mband_w"},
+        {ws.mitem_capacity, ws.mitem_tile, "mitem_tile"},
+        {ws.mtile_capacity, ws.mband_count, "mband_count"}, {ws.mtile_capacity, ws.mband_base, "mband_base"},
+        {ws.mtile_capacity, ws.mitem_base, "mitem_base"},
+        {ws.chunk_capacity, ws.alive_list, "alive_list"},
+        {ws.bounds_capacity, ws.block_bounds, "block_bounds"},
+        {ws.range_capacity, ws.range_prefix, "range_prefix"},
+        {ws.count_R, ws.count_diff, "count_diff"}, {ws.count_R, ws.count_band, "count_band"},
+    };
+    for (const Pair &q : pairs)
+        TSP_REQUIRE(q.cap <= 0 || q.p, TSP_ESTATE, "workspace invariant broken: %s is null with capacity %lld", q.name, (long long)q.cap);
+    return TSP_OK;
+}
+
 static int upload_array(tsp_context *ctx, float **dst, const float *src, int64_t n) {
     if (!*dst) TSP_HIP(hipMalloc((void **)dst, (size_t)n * sizeof(float)));
     TSP_HIP(hipMemcpyAsync(*dst, src, (size_t)n * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
@@ -378,7 +439,10 @@ int tsp_render(tsp_context *ctx, const float *M, float scale_factor, const int64
     TSP_REQUIRE(ctx && M, TSP_EINVAL, "NULL argument");
     TSP_HIP(hipSetDevice(ctx->device));
     const size_t bytes = (size_t)ctx->R * ctx->R * ctx->Ccap * sizeof(double);
-    if (!ctx->image64_entry) TSP_HIP(hipMalloc((void **)&ctx->image64_entry, bytes));
+    if (!ctx->image64_entry) {
+        const int rc = alloc_group(ctx, {{"image64_entry", (void **)&ctx->image64_entry, bytes}}, {});
+        if (rc) return rc;
+    }
     TSP_HIP(hipMemcpyAsync(ctx->image64_entry, ctx->image64, bytes, hipMemcpyDeviceToDevice, ctx->stream));
     const int C_entry = ctx->C;
     const tsp_stats stats_entry = ctx->stats;
@@ -387,10 +451,12 @@ int tsp_render(tsp_context *ctx, const float *M, float scale_factor, const int64
     if (rc != TSP_OK) {
         const std::string why = tsp_last_error();        // (the restore below must not replace the reason of the failure)
         ctx->C = C_entry; ctx->stats = stats_entry; ctx->chunk_culled_particles = culled_entry;
+        // (option overlap_mid_huge: kernels N / G may still be adding into image64 on stream2 -- they finish before the copy)
+        const hipError_t e0 = ctx->stream2 ? hipStreamSynchronize(ctx->stream2) : hipSuccess;
         const hipError_t e1 = hipMemcpyAsync(ctx->image64, ctx->image64_entry, bytes, hipMemcpyDeviceToDevice, ctx->stream);
         const hipError_t e2 = hipStreamSynchronize(ctx->stream);
-        if (ctx->stream2) (void)hipStreamSynchronize(ctx->stream2);
-        if (e1 != hipSuccess || e2 != hipSuccess) set_error("%s; and the accumulator could not be restored (%s)", why.c_str(), hipGetErrorString(e1 != hipSuccess ? e1 : e2));
+        const hipError_t e = e0 != hipSuccess ? e0 : (e1 != hipSuccess ? e1 : e2);
+        if (e != hipSuccess) set_error("%s; and the accumulator could not be restored (%s)", why.c_str(), hipGetErrorString(e));
         else set_error("%s", why.c_str());
     }
     return rc;
@@ -469,9 +535,10 @@ static int render_block(tsp_context *ctx, const float *M, float scale_factor, co
             }
             pack[3 * nr] = acc;
             if (ctx->ws.range_capacity < (int64_t)pack.size()) {
-                if (ctx->ws.range_prefix) TSP_HIP(hipFree(ctx->ws.range_prefix));
-                ctx->ws.range_capacity = (int64_t)pack.size() * 2 + 64;
-                TSP_HIP(hipMalloc((void **)&ctx->ws.range_prefix, ctx->ws.range_capacity * sizeof(int64_t)));
+                const int64_t cap = (int64_t)pack.size() * 2 + 64;
+                if ((rc = alloc_group(ctx, {{"range_prefix_generic", (void **)&ctx->ws.range_prefix, (size_t)cap * sizeof(int64_t)}},
+                                      {{&ctx->ws.range_capacity, cap}})))
+                    return rc;
             }
             TSP_HIP(hipMemcpyAsync(ctx->ws.range_prefix, pack.data(), pack.size() * sizeof(int64_t),
                                    hipMemcpyHostToDevice, ctx->stream));
@@ -539,9 +606,8 @@ int tsp_set_reduced_image(tsp_context *ctx, const float *sum) {
 static int ensure_lut(tsp_context *ctx, const float *lut_rgba, int n_lut) {
     TSP_REQUIRE(lut_rgba && n_lut >= 2 && n_lut <= 65536, TSP_EINVAL, "bad colormap LUT (n=%d)", n_lut);
     if (ctx->lut_capacity < n_lut) {
-        if (ctx->lut) TSP_HIP(hipFree(ctx->lut));
-        TSP_HIP(hipMalloc((void **)&ctx->lut, (size_t)n_lut * 4 * sizeof(float)));
-        ctx->lut_capacity = n_lut;
+        const int rc = alloc_group(ctx, {{"lut", (void **)&ctx->lut, (size_t)n_lut * 4 * sizeof(float)}}, {{&ctx->lut_capacity, n_lut}});
+        if (rc) return rc;
     }
     TSP_HIP(hipMemcpyAsync(ctx->lut, lut_rgba, (size_t)n_lut * 4 * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
     return TSP_OK;
@@ -566,8 +632,10 @@ int tsp_colormap_rgb(tsp_context *ctx, float vmin, float vmax, float gamma, uint
     TSP_REQUIRE(ctx->C == 4, TSP_EINVAL, "rgb colormap needs a 4-channel image");
     TSP_HIP(hipSetDevice(ctx->device));
     const int64_t npix = (int64_t)ctx->R * ctx->R;
-    if (out_rgba_f32 && !ctx->outf) TSP_HIP(hipMalloc((void **)&ctx->outf, (size_t)npix * 4 * sizeof(float)));
-    int rc = launch_colormap_rgb(ctx, ctx->image, npix, ctx->C, vmin, vmax, gamma, out_rgba8 ? ctx->out8 : nullptr,
+    int rc;
+    if (out_rgba_f32 && !ctx->outf && (rc = alloc_group(ctx, {{"outf", (void **)&ctx->outf, (size_t)npix * 4 * sizeof(float)}}, {})))
+        return rc;
+    rc = launch_colormap_rgb(ctx, ctx->image, npix, ctx->C, vmin, vmax, gamma, out_rgba8 ? ctx->out8 : nullptr,
                                  out_rgba_f32 ? ctx->outf : nullptr);
     if (rc) return rc;
     if (out_rgba8) TSP_HIP(hipMemcpyAsync(out_rgba8, ctx->out8, (size_t)npix * 4, hipMemcpyDeviceToHost, ctx->stream));
@@ -580,13 +648,9 @@ int tsp_colormap_rgb(tsp_context *ctx, float vmin, float vmax, float gamma, uint
 int tsp_colormap_set_lut2d(tsp_context *ctx, const float *lut_rgba, int n) {
     TSP_REQUIRE(ctx && lut_rgba && n >= 2 && n <= 4096, TSP_EINVAL, "bad 2-D colormap LUT (n=%d)", n);
     TSP_HIP(hipSetDevice(ctx->device));
-    if (ctx->lut2d_n != n || !ctx->lut2d) {
-        // the size is recorded only once the new allocation exists: a failed hipMalloc leaves "no LUT"
-        ctx->lut2d_n = 0;
-        if (ctx->lut2d) (void)hipFree(ctx->lut2d);
-        ctx->lut2d = nullptr;
-        TSP_HIP(hipMalloc((void **)&ctx->lut2d, (size_t)n * n * 4 * sizeof(float)));
-        ctx->lut2d_n = n;
+    if (ctx->lut2d_n != n || !ctx->lut2d) {      // (a failed allocation leaves "no LUT")
+        const int rc = alloc_group(ctx, {{"lut2d", (void **)&ctx->lut2d, (size_t)n * n * 4 * sizeof(float)}}, {{&ctx->lut2d_n, n}});
+        if (rc) return rc;
     }
     TSP_HIP(hipMemcpy(ctx->lut2d, lut_rgba, (size_t)n * n * 4 * sizeof(float), hipMemcpyHostToDevice));
     return TSP_OK;
@@ -607,11 +671,7 @@ int tsp_colormap_bivariate(tsp_context *ctx, float vmin, float vmax, float densi
 }
 
 static int ensure_scratch(tsp_context *ctx, size_t bytes) {
-    if (ctx->scratch_bytes < bytes) {
-        if (ctx->scratch) TSP_HIP(hipFree(ctx->scratch));
-        TSP_HIP(hipMalloc(&ctx->scratch, bytes));
-        ctx->scratch_bytes = bytes;
-    }
+    if (ctx->scratch_bytes < bytes) return alloc_group(ctx, {{"colormap_scratch", &ctx->scratch, bytes}}, {{&ctx->scratch_bytes, (int64_t)bytes}});
     return TSP_OK;
 }
 
@@ -742,6 +802,11 @@ int tsp_set_option(tsp_context *ctx, const char *name, int64_t value) {
     if (!strcmp(name, "debug_fail_stage")) {   // test aid: the next tsp_render fails after kernel S (1) or after kernel G (2)
         TSP_REQUIRE(value >= 0 && value <= 2, TSP_EINVAL, "%s out of range", name);
         ctx->debug_fail_stage = (int)value;
+        return TSP_OK;
+    }
+    if (!strcmp(name, "debug_fail_alloc")) {   // test aid: the k-th device allocation from now on fails once (alloc_group)
+        TSP_REQUIRE(value >= 0, TSP_EINVAL, "%s out of range", name);
+        ctx->debug_fail_alloc = value;
         return TSP_OK;
     }
     if (!strcmp(name, "debug_gather_full_lut")) { ctx->debug_gather_full_lut = value ? 1 : 0; return TSP_OK; }

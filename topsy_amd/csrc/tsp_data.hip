@@ -152,11 +152,10 @@ int ensure_block_bounds(tsp_context *ctx) {
     const int64_t n = ctx->p.n, blocks = (n + BOUNDS_BLOCK - 1) / BOUNDS_BLOCK;
     if (blocks == 0) return TSP_OK;
     if (ws.bounds_capacity < blocks) {
-        if (ws.block_bounds) TSP_HIP(hipFree(ws.block_bounds));
-        ws.block_bounds = nullptr;
-        ws.bounds_capacity = blocks;
-        TSP_HIP(hipMalloc((void **)&ws.block_bounds, (size_t)blocks * 2 * sizeof(float4)));
+        const int rc = alloc_group(ctx, {{"block_bounds", (void **)&ws.block_bounds, (size_t)blocks * 2 * sizeof(float4)}}, {{&ws.bounds_capacity, blocks}});
+        if (rc) return rc;
     }
+    if (int rc = check_workspace(ctx)) return rc;
     hipLaunchKernelGGL(block_bounds_kernel, dim3((unsigned)blocks), dim3(64), 0, ctx->stream, ctx->p.x, ctx->p.y, ctx->p.z, ctx->p.h, n,
                        ws.block_bounds);
     TSP_HIP(hipGetLastError());
@@ -270,12 +269,14 @@ int ensure_weights(tsp_context *ctx, bool rgb) {
     if (p.n == 0 || (rgb ? p.wrgb_valid : p.wm_valid)) return TSP_OK;
     int rc;
     const unsigned grid = (unsigned)std::min<int64_t>((p.n + 255) / 256, (int64_t)ctx->cu_count * 32);
+    const size_t bytes = (size_t)p.n * sizeof(float);
     if (rgb) {
-        if ((rc = ensure_array(&p.wr, p.n)) || (rc = ensure_array(&p.wg, p.n)) || (rc = ensure_array(&p.wb, p.n))) return rc;
+        if ((rc = alloc_group(ctx, {{"weights_r", (void **)&p.wr, bytes}, {"weights_g", (void **)&p.wg, bytes}, {"weights_b", (void **)&p.wb, bytes}}, {})))
+            return rc;
         hipLaunchKernelGGL(weights_kernel, dim3(grid), dim3(256), 0, ctx->stream, p.h, p.r, p.g, p.b, p.n, p.wr, p.wg, p.wb);
         p.wrgb_valid = true;
     } else {
-        if ((rc = ensure_array(&p.wm, p.n))) return rc;
+        if ((rc = alloc_group(ctx, {{"weights_m", (void **)&p.wm, bytes}}, {}))) return rc;
         hipLaunchKernelGGL(weights_kernel, dim3(grid), dim3(256), 0, ctx->stream, p.h, p.m, (const float *)nullptr, (const float *)nullptr, p.n,
                            p.wm, (float *)nullptr, (float *)nullptr);
         p.wm_valid = true;
@@ -499,16 +500,13 @@ int content_sort(tsp_context *ctx, int kind, float scale, int64_t *n_finite, int
     const int64_t n = npix * (kind == 2 ? 3 : (kind == 3 ? ctx->C : 1));
     hipStream_t st = ctx->stream;
     if (ctx->sort_capacity < n) {
-        if (ctx->sort_keys) TSP_HIP(hipFree(ctx->sort_keys));
-        if (ctx->sort_keys_alt) TSP_HIP(hipFree(ctx->sort_keys_alt));
-        if (ctx->sort_tmp) TSP_HIP(hipFree(ctx->sort_tmp));
-        ctx->sort_tmp = nullptr;
-        TSP_HIP(hipMalloc((void **)&ctx->sort_keys, (size_t)n * 4));
-        TSP_HIP(hipMalloc((void **)&ctx->sort_keys_alt, (size_t)n * 4));
-        ctx->sort_capacity = n;
-        ctx->sort_tmp_bytes = 0;
-        TSP_HIP(hipcub::DeviceRadixSort::SortKeys(nullptr, ctx->sort_tmp_bytes, ctx->sort_keys, ctx->sort_keys_alt, n, 0, 32, st));
-        TSP_HIP(hipMalloc(&ctx->sort_tmp, ctx->sort_tmp_bytes ? ctx->sort_tmp_bytes : 16));
+        size_t tmp_bytes = 0;     // (the size query reads no key)
+        TSP_HIP(hipcub::DeviceRadixSort::SortKeys(nullptr, tmp_bytes, ctx->sort_keys, ctx->sort_keys_alt, n, 0, 32, st));
+        tmp_bytes = tmp_bytes ? tmp_bytes : 16;
+        const int rc = alloc_group(ctx, {{"sort_keys", (void **)&ctx->sort_keys, (size_t)n * 4}, {"sort_keys_alt", (void **)&ctx->sort_keys_alt, (size_t)n * 4},
+                                         {"sort_tmp", &ctx->sort_tmp, tmp_bytes}},
+                                   {{&ctx->sort_capacity, n}, {&ctx->sort_tmp_bytes, (int64_t)tmp_bytes}});
+        if (rc) return rc;
     }
     unsigned long long *counts = reinterpret_cast<unsigned long long *>(ctx->counters);   // scratch: reuse the counter block
     TSP_HIP(hipMemsetAsync(counts, 0, 2 * sizeof(unsigned long long), st));

@@ -1047,19 +1047,15 @@ static int bin_huge_records(tsp_context *ctx, TileArgs &ta, const float4 *huge_g
     // (one band: nothing to gain; a short list is scanned in microseconds; a huge image with a long list would not fit)
     if (n_bands < 2 || n_huge < 4096 || (long long)n_bands * n_huge * (long long)rec_bytes > ctx->huge_band_budget) return TSP_OK;
     if (ws.hband_stride < n_huge || ws.hband_bands < n_bands) {
-        if (ws.hband_geom) TSP_HIP(hipFree(ws.hband_geom));
-        if (ws.hband_w) TSP_HIP(hipFree(ws.hband_w));
-        if (ws.hband_count) TSP_HIP(hipFree(ws.hband_count));
-        ws.hband_geom = ws.hband_w = nullptr; ws.hband_count = nullptr;
-        ws.hband_stride = n_huge + n_huge / 8 + 1024;
-        ws.hband_bands = n_bands;
-        const size_t slots = (size_t)n_bands * (size_t)ws.hband_stride;
-        if ((long long)slots * (long long)(sizeof(float4) + 2 * sizeof(float)) > ctx->huge_band_budget + (ctx->huge_band_budget >> 2)) ws.hband_stride = n_huge;
-        const size_t slots2 = (size_t)n_bands * (size_t)ws.hband_stride;
-        TSP_HIP(hipMalloc(&ws.hband_geom, slots2 * sizeof(float4)));
-        TSP_HIP(hipMalloc(&ws.hband_w, slots2 * 2 * sizeof(float)));
-        TSP_HIP(hipMalloc((void **)&ws.hband_count, 256 * sizeof(int)));
+        int64_t stride = n_huge + n_huge / 8 + 1024;
+        if ((long long)n_bands * stride * (long long)(sizeof(float4) + 2 * sizeof(float)) > ctx->huge_band_budget + (ctx->huge_band_budget >> 2)) stride = n_huge;
+        const size_t slots = (size_t)n_bands * (size_t)stride;
+        const int rc = alloc_group(ctx, {{"hband_geom", &ws.hband_geom, slots * sizeof(float4)}, {"hband_w", &ws.hband_w, slots * 2 * sizeof(float)},
+                                         {"hband_count", (void **)&ws.hband_count, 256 * sizeof(int)}},
+                                   {{&ws.hband_stride, stride}, {&ws.hband_bands, n_bands}});
+        if (rc) return rc;
     }
+    if (int rc = check_workspace(ctx)) return rc;
     hipStream_t st = ctx->stream;
     TSP_HIP(hipMemsetAsync(ws.hband_count, 0, 256 * sizeof(int), st));
     const unsigned grid = (unsigned)((n_huge + 1023) / 1024);
@@ -1263,16 +1259,15 @@ static int bin_mid_records(tsp_context *ctx, TileArgs &ta, const float4 *mid_geo
     ba.disc_k2 = ta.disc_k2; ba.exact = exact ? 1 : 0; ba.narrow = exact ? 1 : 0;
     ba.win_rows = std::max(1, G_WIN_TILES / tiles_x);
     const int n_win = (tiles_y + ba.win_rows - 1) / ba.win_rows, win_tiles = std::min(tiles_y, ba.win_rows) * tiles_x;
+    int rc;
     if (ws.mtile_capacity < n_tiles) {
-        void *olds[] = {ws.mband_count, ws.mband_base, ws.mitem_base};
-        for (void *q : olds)
-            if (q) TSP_HIP(hipFree(q));
-        ws.mband_count = ws.mitem_base = nullptr; ws.mband_base = nullptr;
-        ws.mtile_capacity = n_tiles;
-        TSP_HIP(hipMalloc((void **)&ws.mband_count, 2 * (size_t)ws.mtile_capacity * sizeof(int)));               // counts | fill cursors
-        TSP_HIP(hipMalloc((void **)&ws.mband_base, ((size_t)ws.mtile_capacity + 1) * sizeof(long long)));
-        TSP_HIP(hipMalloc((void **)&ws.mitem_base, ((size_t)ws.mtile_capacity + 1) * sizeof(int)));
+        if ((rc = alloc_group(ctx, {{"mband_count", (void **)&ws.mband_count, 2 * (size_t)n_tiles * sizeof(int)},          // counts | fill cursors
+                                    {"mband_base", (void **)&ws.mband_base, ((size_t)n_tiles + 1) * sizeof(long long)},
+                                    {"mitem_base", (void **)&ws.mitem_base, ((size_t)n_tiles + 1) * sizeof(int)}},
+                              {{&ws.mtile_capacity, n_tiles}})))
+            return rc;
     }
+    if ((rc = check_workspace(ctx))) return rc;
     // records per item: short items balance a short list over the device, long ones amortise the LUT load and the final flush
     int item_records = ctx->mid_item_records;
     if (item_records <= 0) {
@@ -1298,16 +1293,15 @@ static int bin_mid_records(tsp_context *ctx, TileArgs &ta, const float4 *mid_geo
     TSP_HIP(hipMemcpyAsync(&total_items, ws.mitem_base + n_tiles, sizeof(int), hipMemcpyDeviceToHost, st));
     TSP_HIP(hipStreamSynchronize(st));
     if (ws.mband_capacity < total_records || ws.mitem_capacity < total_items) {
-        void *olds[] = {ws.mband_geom, ws.mband_w, ws.mitem_tile};
-        for (void *q : olds)
-            if (q) TSP_HIP(hipFree(q));
-        ws.mband_geom = ws.mband_w = nullptr; ws.mitem_tile = nullptr;
-        ws.mband_capacity = std::max<int64_t>(ws.mband_capacity, total_records + total_records / 4 + 1024);
-        ws.mitem_capacity = std::max<int64_t>(ws.mitem_capacity, (int64_t)total_items + total_items / 4 + 1024);
-        TSP_HIP(hipMalloc(&ws.mband_geom, (size_t)ws.mband_capacity * sizeof(float4)));
-        TSP_HIP(hipMalloc(&ws.mband_w, (size_t)ws.mband_capacity * 4 * sizeof(float)));      // (kernel N keeps a float2 / float4 of weights per record here)
-        TSP_HIP(hipMalloc((void **)&ws.mitem_tile, (size_t)ws.mitem_capacity * sizeof(int)));
+        const int64_t rec_cap = std::max<int64_t>(ws.mband_capacity, total_records + total_records / 4 + 1024);
+        const int64_t item_cap = std::max<int64_t>(ws.mitem_capacity, (int64_t)total_items + total_items / 4 + 1024);
+        if ((rc = alloc_group(ctx, {{"mband_geom", &ws.mband_geom, (size_t)rec_cap * sizeof(float4)},
+                                    {"mband_w", &ws.mband_w, (size_t)rec_cap * 4 * sizeof(float)},      // (kernel N keeps a float2 / float4 of weights per record here)
+                                    {"mitem_tile", (void **)&ws.mitem_tile, (size_t)item_cap * sizeof(int)}},
+                              {{&ws.mband_capacity, rec_cap}, {&ws.mitem_capacity, item_cap}})))
+            return rc;
     }
+    if ((rc = check_workspace(ctx))) return rc;
     hipLaunchKernelGGL(tile_prefix_kernel, dim3(1), dim3(1024), 0, st, (const int *)ws.mband_count, n_tiles, ws.mband_base, ws.mitem_base, ws.mitem_tile, total_items, item_records);
     hipLaunchKernelGGL((tile_fill_kernel<NW>), dim3(grid, n_win), dim3(256), lds ? 2 * win_tiles * sizeof(int) : 0, st, mid_geom, mid_w, n_mid, ba,
                        (float4 *)ws.mband_geom, (float *)ws.mband_w, (const long long *)ws.mband_base, ws.mband_count + ws.mtile_capacity,

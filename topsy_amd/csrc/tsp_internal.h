@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <initializer_list>
 #include <vector>
 #include <stdio.h>
 #include <string>
@@ -89,6 +90,7 @@ struct Workspace {     // per-context scratch of the three-class pipeline (grown
     int64_t range_capacity = 0;
     int *count_diff = nullptr;          // rgb: (R+1)^2 corner-difference image of the huge footprints' pixel rectangles
     int *count_band = nullptr;          // rgb: per (64-row band, column) sums of its row-scanned form
+    int count_R = 0;                    // resolution count_diff / count_band are sized for (0: not allocated)
 };
 
 }  // namespace tsp
@@ -148,6 +150,7 @@ struct tsp_context {
     bool overlap_mid_huge = false;    // option: kernels G and H2 on two streams (measured: no gain at 1.25e8, +6 % at 1e7)
     int64_t slice_records = 0;        // option: deferred records kernels G / H2 take per launch (0 = 2^27 mid / 2^30 huge); a block of any size draws in slices
     int debug_fail_stage = 0;         // test aid: the next render fails with TSP_ENOMEM after kernel S (1) / after kernel G (2); cleared by the failure
+    int64_t debug_fail_alloc = 0;     // test aid: the k-th allocation of alloc_group() from now on fails once, as hipMalloc would (0 = off)
     int stream_occ[3][2] = {};        // kernel S: workgroups resident per CU by [mode][one-channel window | all channels] (occupancy query, once per context)
     bool debug_no_raster = false;    // measurement aid: kernel S classifies and emits records but rasterises nothing (the image is then incomplete)
     int cu_count = 256;
@@ -170,6 +173,38 @@ struct DeviceScratch {
     void *release() { void *q = p; p = nullptr; return q; }
     void reset(void *q) { if (p) (void)hipFree(p); p = q; }
 };
+
+// Every device buffer that can be (re)allocated after tsp_create and the uploads -- the render workspace, the colormap and
+// post-pass staging -- goes through alloc_group().  A group is the buffers that are only ever used together, with the capacity
+// fields that describe them: the group is freed and its capacities zeroed first, then each buffer is allocated, and only once all
+// of them exist are the capacities recorded.  A failed allocation (or the injected one of option debug_fail_alloc) leaves every
+// pointer of the group null and its capacities 0, so the next call allocates again instead of trusting a stale size; it returns
+// TSP_ENOMEM (TSP_EHIP for another runtime error) with the site's name in tsp_last_error.  Site names are unique (a CPU test
+// scans the sources), written first so that they can be found: {"site", (void **)&ptr, bytes}, or SITE("site") where a name
+// is passed on.
+struct DeviceBuffer {
+    const char *site;
+    void **p;
+    size_t bytes;
+};
+struct Capacity {      // a capacity field and the value it takes once its group is allocated
+    int64_t *c64 = nullptr; int *c32 = nullptr; size_t *csz = nullptr;
+    int64_t value = 0;
+    Capacity(int64_t *c, int64_t v) : c64(c), value(v) {}
+    Capacity(int *c, int64_t v) : c32(c), value(v) {}
+    Capacity(size_t *c, int64_t v) : csz(c), value(v) {}
+    void set(int64_t v) const {
+        if (c64) *c64 = v;
+        else if (c32) *c32 = (int)v;
+        else *csz = (size_t)v;
+    }
+};
+int alloc_group(tsp_context *ctx, std::initializer_list<DeviceBuffer> bufs, std::initializer_list<Capacity> caps);
+#define SITE(name) name
+
+// Host-side invariant of the workspace: a capacity above 0 means every buffer it describes exists.  Checked before the kernels
+// that use the buffers are launched, so that a missed allocation site is an error (TSP_ESTATE) and never a write through null.
+int check_workspace(const tsp_context *ctx);
 
 // kernels / launchers implemented in the other translation units
 int launch_generic(tsp_context *ctx, const Camera &cam, const int64_t *d_ranges, int n_ranges,

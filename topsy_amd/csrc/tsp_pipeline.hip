@@ -768,9 +768,10 @@ __global__ __launch_bounds__(256) void count_apply_kernel(const int *__restrict_
 static int add_rect_counts(tsp_context *ctx, const float4 *mid_geom, long long n_mid, const float4 *huge_geom, long long n_huge) {
     Workspace &ws = ctx->ws;
     const int R = ctx->R, S = R + 1, nb = (R + CBAND - 1) / CBAND;
-    if (!ws.count_diff) {
-        TSP_HIP(hipMalloc((void **)&ws.count_diff, (size_t)S * S * sizeof(int)));
-        TSP_HIP(hipMalloc((void **)&ws.count_band, (size_t)nb * R * sizeof(int)));
+    if (ws.count_R != R) {
+        const int rc = alloc_group(ctx, {{"count_diff", (void **)&ws.count_diff, (size_t)S * S * sizeof(int)},
+                                         {"count_band", (void **)&ws.count_band, (size_t)nb * R * sizeof(int)}}, {{&ws.count_R, R}});
+        if (rc) return rc;
     }
     hipStream_t st = ctx->stream;
     TSP_HIP(hipMemsetAsync(ws.count_diff, 0, (size_t)S * S * sizeof(int), st));
@@ -786,13 +787,10 @@ static int add_rect_counts(tsp_context *ctx, const float4 *mid_geom, long long n
 // ---------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------
-static int grow(void **p, int64_t *cap, int64_t need, size_t elem) {
-    if (*cap >= need) return TSP_OK;
-    if (*p) TSP_HIP(hipFree(*p));
-    *p = nullptr;
-    TSP_HIP(hipMalloc(p, (size_t)need * elem));
-    *cap = need;
-    return TSP_OK;
+// the deferred-record lists: geometry and weights are one group (sized in records; weights: two floats per record).  The first
+// allocation and the one before kernel S's replay are different sites (a test makes each of them fail).
+static int alloc_list(tsp_context *ctx, void **geom, void **w, int64_t *cap, int64_t need, const char *geom_site, const char *w_site) {
+    return alloc_group(ctx, {{geom_site, geom, (size_t)need * sizeof(float4)}, {w_site, w, (size_t)need * 2 * sizeof(float)}}, {{cap, need}});
 }
 
 template <int MODE>
@@ -814,34 +812,27 @@ static int run_pipeline(tsp_context *ctx, const Camera &cam, const int64_t *h_st
     pack[3 * n_ranges] = n_chunks64;
     TSP_REQUIRE(n_chunks64 < (1ll << 30), TSP_EINVAL, "too many chunks");
     const int n_chunks = (int)n_chunks64;
+    int rc;
+    if ((rc = check_workspace(ctx))) return rc;
     if (ws.range_capacity < (int64_t)pack.size()) {
-        if (ws.range_prefix) TSP_HIP(hipFree(ws.range_prefix));
-        ws.range_capacity = (int64_t)pack.size() * 2 + 64;
-        TSP_HIP(hipMalloc((void **)&ws.range_prefix, ws.range_capacity * sizeof(int64_t)));
+        const int64_t cap = (int64_t)pack.size() * 2 + 64;
+        if ((rc = alloc_group(ctx, {{"range_prefix", (void **)&ws.range_prefix, (size_t)cap * sizeof(int64_t)}}, {{&ws.range_capacity, cap}}))) return rc;
     }
     TSP_HIP(hipMemcpyAsync(ws.range_prefix, pack.data(), pack.size() * sizeof(int64_t), hipMemcpyHostToDevice, st));
     // the list of chunks that survive culling (+ the per-workgroup counts of the culling pass behind it)
     if (ws.chunk_capacity < n_chunks) {
-        if (ws.alive_list) TSP_HIP(hipFree(ws.alive_list));
-        ws.alive_list = nullptr;
-        ws.chunk_capacity = (int64_t)n_chunks + n_chunks / 4 + 64;
-        TSP_HIP(hipMalloc((void **)&ws.alive_list, (ws.chunk_capacity + ws.chunk_capacity / 256 + 2) * sizeof(int)));
+        const int64_t cap = (int64_t)n_chunks + n_chunks / 4 + 64;
+        if ((rc = alloc_group(ctx, {{"alive_list", (void **)&ws.alive_list, (size_t)(cap + cap / 256 + 2) * sizeof(int)}}, {{&ws.chunk_capacity, cap}})))
+            return rc;
     }
     // record lists: start modest, grow to the exact need when a frame overflows (rare)
-    int rc;
     if ((rc = ensure_weights(ctx, MODE == TSP_MODE_RGB))) return rc;      // m / h^2 (rgb / h^2): once per upload, not per frame
-    if (ws.mid_capacity == 0) {
-        const int64_t guess = std::max<int64_t>(total / 4, 1 << 16);
-        if ((rc = grow(&ws.mid_geom, &ws.mid_capacity, guess, sizeof(float4)))) return rc;
-        if (ws.mid_w) TSP_HIP(hipFree(ws.mid_w));
-        TSP_HIP(hipMalloc(&ws.mid_w, (size_t)ws.mid_capacity * 2 * sizeof(float)));
-    }
-    if (ws.huge_capacity == 0) {
-        const int64_t guess = std::max<int64_t>(total / 16, 1 << 16);
-        if ((rc = grow(&ws.huge_geom, &ws.huge_capacity, guess, sizeof(float4)))) return rc;
-        if (ws.huge_w) TSP_HIP(hipFree(ws.huge_w));
-        TSP_HIP(hipMalloc(&ws.huge_w, (size_t)ws.huge_capacity * 2 * sizeof(float)));
-    }
+    if (ws.mid_capacity == 0 && (rc = alloc_list(ctx, &ws.mid_geom, &ws.mid_w, &ws.mid_capacity, std::max<int64_t>(total / 4, 1 << 16),
+                                                 SITE("mid_geom"), SITE("mid_w"))))
+        return rc;
+    if (ws.huge_capacity == 0 && (rc = alloc_list(ctx, &ws.huge_geom, &ws.huge_w, &ws.huge_capacity, std::max<int64_t>(total / 16, 1 << 16),
+                                                  SITE("huge_geom"), SITE("huge_w"))))
+        return rc;
 
     Particles parts = ctx->p;
     if (!ctx->use_quantity) parts.q = nullptr;
@@ -864,7 +855,7 @@ static int run_pipeline(tsp_context *ctx, const Camera &cam, const int64_t *h_st
     TSP_HIP(hipEventRecord(ctx->ev[7], st));      // (the culling passes, and the block bounds when they are stale, count as kernel S's time)
     if (cull) {
         if ((rc = ensure_block_bounds(ctx))) return rc;
-        if (!ws.cull_info) TSP_HIP(hipMalloc((void **)&ws.cull_info, 2 * sizeof(unsigned long long)));
+        if (!ws.cull_info && (rc = alloc_group(ctx, {{"cull_info", (void **)&ws.cull_info, 2 * sizeof(unsigned long long)}}, {}))) return rc;
         TSP_HIP(hipMemsetAsync(ws.cull_info, 0, 2 * sizeof(unsigned long long), st));
         CullArgs ca;
         ca.ranges = ws.range_prefix; ca.n_ranges = n_ranges; ca.n_chunks = n_chunks; ca.cam = cam;
@@ -921,16 +912,12 @@ static int run_pipeline(tsp_context *ctx, const Camera &cam, const int64_t *h_st
         if (!mid_over && !huge_over) break;
         TSP_REQUIRE(attempt == 0, TSP_ENOMEM, "record lists overflowed twice");
         // enlarge and replay kernel S in records-only mode (its small footprints are already in the image)
-        if (mid_over) {
-            if ((rc = grow(&ws.mid_geom, &ws.mid_capacity, (int64_t)hc.n_mid + (int64_t)hc.n_mid / 8 + 1024, sizeof(float4)))) return rc;
-            if (ws.mid_w) TSP_HIP(hipFree(ws.mid_w));
-            TSP_HIP(hipMalloc(&ws.mid_w, (size_t)ws.mid_capacity * 2 * sizeof(float)));
-        }
-        if (huge_over) {
-            if ((rc = grow(&ws.huge_geom, &ws.huge_capacity, (int64_t)hc.n_huge + (int64_t)hc.n_huge / 8 + 1024, sizeof(float4)))) return rc;
-            if (ws.huge_w) TSP_HIP(hipFree(ws.huge_w));
-            TSP_HIP(hipMalloc(&ws.huge_w, (size_t)ws.huge_capacity * 2 * sizeof(float)));
-        }
+        if (mid_over && (rc = alloc_list(ctx, &ws.mid_geom, &ws.mid_w, &ws.mid_capacity, (int64_t)hc.n_mid + (int64_t)hc.n_mid / 8 + 1024,
+                                         SITE("mid_geom_replay"), SITE("mid_w_replay"))))
+            return rc;
+        if (huge_over && (rc = alloc_list(ctx, &ws.huge_geom, &ws.huge_w, &ws.huge_capacity, (int64_t)hc.n_huge + (int64_t)hc.n_huge / 8 + 1024,
+                                          SITE("huge_geom_replay"), SITE("huge_w_replay"))))
+            return rc;
         TSP_HIP(hipMemsetAsync(ctx->counters, 0, sizeof(Counters), st));
         carry = hc;
     }
@@ -956,6 +943,7 @@ static int run_pipeline(tsp_context *ctx, const Camera &cam, const int64_t *h_st
         TSP_HIP(hipEventRecord(ctx->ev[8], st));
         TSP_HIP(hipStreamWaitEvent(st_mid, ctx->ev[8], 0));
     }
+    if ((rc = check_workspace(ctx))) return rc;
     if (ctx->debug_fail_stage == 1) { ctx->debug_fail_stage = 0; TSP_REQUIRE(false, TSP_ENOMEM, "injected failure after kernel S (debug_fail_stage)"); }
     // A block of any size draws (sph.py:306-332 has no limit on a block): the tile kernels index their records and work items with
     // 32 bits, so a longer list goes through them in slices -- bin, draw, next slice; the bins of a slice are bounded with it.

@@ -62,11 +62,10 @@ __global__ __launch_bounds__(256) void tile_periodic_kernel(const float *__restr
 int tile_periodic(tsp_context *ctx, int n, const float *h_offsets, const float *h_weights) {
     const size_t img_bytes = (size_t)ctx->R * ctx->R * ctx->C * sizeof(float);
     const size_t tab_bytes = (size_t)n * 3 * sizeof(float);
-    if (ctx->scratch_bytes < img_bytes + tab_bytes + 256) {
-        if (ctx->scratch) TSP_HIP(hipFree(ctx->scratch));
-        ctx->scratch = nullptr;
-        TSP_HIP(hipMalloc(&ctx->scratch, img_bytes + tab_bytes + 256));
-        ctx->scratch_bytes = img_bytes + tab_bytes + 256;
+    const size_t need = img_bytes + tab_bytes + 256;
+    if (ctx->scratch_bytes < need) {
+        const int rc = alloc_group(ctx, {{"periodic_scratch", &ctx->scratch, need}}, {{&ctx->scratch_bytes, (int64_t)need}});
+        if (rc) return rc;
     }
     float *d_out = (float *)ctx->scratch;
     float *d_off = (float *)((char *)ctx->scratch + ((img_bytes + 255) & ~(size_t)255));
