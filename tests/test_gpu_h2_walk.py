@@ -61,20 +61,37 @@ def _render(native, mips, scene, variant, walk, count):
         ctx.close()
 
 
+def _oracle(mips, scene):
+    from oracle import oracle_c, oracle_np
+    R, widths, n_per, seed, band = scene
+    x, y, z, h, m = _scene(R, widths, n_per, seed, band)
+    M, sf = oracle_np.transform_matrix(np.eye(3), np.zeros(3), R / 2.0)
+    return oracle_c.splat(x, y, z, h, m, mode=0, M=M, sf=sf, R=R, mips=mips)
+
+
 @pytest.mark.parametrize("variant", [5, 7])
 @pytest.mark.parametrize("name", sorted(SCENES))
 def test_asm_walk_matches_cpp_walk(native, mips, name, variant):
+    """...and each walk matches the float64 oracle (1e-5, exact fragment count): a mistake both walks share does not pass."""
     scene = SCENES[name]
+    want, nfrag = _oracle(mips, scene)
     for count in (1, 0):
         img0, nf0, nh0 = _render(native, mips, scene, variant, 0, count)
         img1, nf1, nh1 = _render(native, mips, scene, variant, 1, count)
         assert nh0 == nh1 and nh0 > 0, "the scene must reach kernel H2"
         if count:
             assert nf0 == nf1 and nf0 > 0
+            assert nf0 == nfrag, f"{name}, huge_variant {variant}: fragment count differs from the oracle"
         d = img0[..., 0]
         assert d.max() > 0
         assert (np.abs(img1[..., 0] - d) <= 1e-6 * np.abs(d) + 1e-30).all(), \
             f"{name}, huge_variant {variant}: max rel {np.max(np.abs(img1[..., 0] - d) / np.maximum(np.abs(d), 1e-300))}"
+        for walk, img in ((0, img0), (1, img1)):
+            w = want[..., 0]
+            assert (np.abs(img[..., 0] - w) <= 1e-5 * np.abs(w)).all(), \
+                f"{name}, huge_variant {variant}, h2_walk {walk}: max rel err vs the oracle " \
+                f"{np.max(np.abs(img[..., 0] - w) / np.maximum(np.abs(w), 1e-300))}"
+            assert (img[..., 1] == 0).all()
 
 
 def test_h2_walk_option_range(native):

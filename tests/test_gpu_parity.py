@@ -276,21 +276,28 @@ def test_reference_kats_through_hip(native, mips, golden):
 
 @pytest.mark.parametrize("R", [1, 2, 8, 33, 65])
 def test_tiny_and_odd_resolutions(native, mips, R):
-    """Resolutions below / not a multiple of every tile size (64-px window, 64x32 and 128x64 tiles)."""
+    """Resolutions below / not a multiple of every tile size (64-px window, 64x32 and 128x64 tiles), weighted and density (the
+    single-channel builds: kernel S's one-column path, kernel N's 16 x 32 strips, H2's asm walk)."""
     from oracle import oracle_np
     M, sf = oracle_np.transform_matrix(_rot(0.2, 0.1), np.zeros(3), 90.0)
     pos, h, m, q, _ = make_cloud(3000, seed=21)
-    ctx = native.Context(R, 2)
-    ctx.set_kernel_mips(mips)
-    ctx.upload_particles(pos[:, 0], pos[:, 1], pos[:, 2], h, m)
-    ctx.upload_quantity(q)
-    ctx.set_option("count_fragments", 1)
-    ctx.render(M, sf)
-    got = ctx.read_image()
-    want, nfrag = oracle_render(pos, h, m, q, None, 0, M, sf, R, mips)
-    assert ctx.stats()["n_fragments"] == nfrag
-    check_2ch(got, want, abs_terms_image(pos, h, m, q, M, sf, R, mips))
-    ctx.close()
+    for mode in ("weighted", "density"):
+        ctx = native.Context(R, 2)
+        ctx.set_kernel_mips(mips)
+        ctx.upload_particles(pos[:, 0], pos[:, 1], pos[:, 2], h, m)
+        if mode == "weighted":
+            ctx.upload_quantity(q)
+        ctx.set_option("count_fragments", 1)
+        ctx.render(M, sf)
+        got = ctx.read_image()
+        want, nfrag = oracle_render(pos, h, m, q if mode == "weighted" else None, None, 0, M, sf, R, mips)
+        assert ctx.stats()["n_fragments"] == nfrag, mode
+        if mode == "weighted":
+            check_2ch(got, want, abs_terms_image(pos, h, m, q, M, sf, R, mips))
+        else:
+            assert np.allclose(got[..., 0], want[..., 0], rtol=1e-5, atol=0)
+            assert (got[..., 1] == 0).all()
+        ctx.close()
 
 
 def test_single_particles_and_ties(native, mips, golden):
@@ -328,7 +335,7 @@ def test_single_particles_and_ties(native, mips, golden):
     ctx.close()
 
 
-@pytest.mark.parametrize("mode", ["weighted", "rgb", "depth"])
+@pytest.mark.parametrize("mode", ["weighted", "rgb", "depth", "density"])
 def test_scattered_small_footprints_leave_the_window(native, mips, mode):
     """Unordered particles with footprints of 0-11 px spread over a 1024^2 image: a 512-particle chunk spans far
     more than kernel S's 64-px LDS window, so most of them take the MID-list route (kernel G, mip 3); the counter
@@ -357,6 +364,12 @@ def test_scattered_small_footprints_leave_the_window(native, mips, mode):
         ctx.render(M, sf, mode=native.MODE_DEPTH)
         want, _ = oracle_render(pos, h, m, None, None, 1, M, sf, R, mips)
         assert np.allclose(ctx.read_image(), want, rtol=1e-5, atol=0)
+    elif mode == "density":
+        ctx.render(M, sf, mode=native.MODE_WEIGHTED)
+        want, _ = oracle_render(pos, h, m, None, None, 0, M, sf, R, mips)
+        got = ctx.read_image()
+        assert np.allclose(got[..., 0], want[..., 0], rtol=1e-5, atol=0)
+        assert (got[..., 1] == 0).all()
     else:
         ctx.upload_quantity(q)
         ctx.render(M, sf, mode=native.MODE_WEIGHTED)
@@ -392,7 +405,7 @@ def test_alternative_sampling_rules(native, mips, rule):
     ctx.close()
 
 
-@pytest.mark.parametrize("seed", range(12))
+@pytest.mark.parametrize("seed", range(16))
 def test_randomised_views(native, mips, seed):
     """Random resolution, camera, smoothing-length range and mode per seed; the three-class pipeline must agree
     with the oracle on the image (1e-5) and on the exact fragment count, including particles with degenerate
@@ -412,7 +425,7 @@ def test_randomised_views(native, mips, seed):
     # degenerate particles
     h[:6] = [0.0, -1.0, np.nan, np.inf, 1e-30, 1e30]
     pos[6, 0] = np.nan; pos[7, 1] = np.inf; pos[8, 2] = -np.inf
-    mode = ["weighted", "rgb", "depth"][seed % 3]
+    mode = ["weighted", "rgb", "depth"][seed % 3] if seed < 12 else "density"
     ctx = native.Context(R, 4 if mode == "rgb" else 2)
     ctx.set_kernel_mips(mips)
     ctx.upload_particles(pos[:, 0], pos[:, 1], pos[:, 2], h, None if mode == "rgb" else m)
@@ -428,6 +441,12 @@ def test_randomised_views(native, mips, seed):
         ctx.render(M, sf, mode=native.MODE_DEPTH)
         want, nfrag = oracle_render(pos, h, m, None, None, 1, M, sf, R, mips)
         assert np.allclose(ctx.read_image(), want, rtol=1e-5, atol=0)
+    elif mode == "density":
+        ctx.render(M, sf, mode=native.MODE_WEIGHTED)
+        want, nfrag = oracle_render(pos, h, m, None, None, 0, M, sf, R, mips)
+        got = ctx.read_image()
+        assert np.allclose(got[..., 0], want[..., 0], rtol=1e-5, atol=0)
+        assert (got[..., 1] == 0).all()
     else:
         ctx.upload_quantity(q)
         ctx.render(M, sf, mode=native.MODE_WEIGHTED)
@@ -436,11 +455,14 @@ def test_randomised_views(native, mips, seed):
     assert ctx.stats()["n_fragments"] == nfrag
     # and once more with the exact disc culling active (no fragment statistics)
     ctx.set_option("count_fragments", 0)
-    md = {"weighted": native.MODE_WEIGHTED, "rgb": native.MODE_RGB, "depth": native.MODE_DEPTH}[mode]
+    md = {"weighted": native.MODE_WEIGHTED, "rgb": native.MODE_RGB, "depth": native.MODE_DEPTH, "density": native.MODE_WEIGHTED}[mode]
     ctx.render(M, sf, mode=md)
     got = ctx.read_image()
     if mode == "weighted":
         check_2ch(got, want, abs_terms_image(pos, h, m, q, M, sf, R, mips))
+    elif mode == "density":
+        assert np.allclose(got[..., 0], want[..., 0], rtol=1e-5, atol=0)
+        assert (got[..., 1] == 0).all()
     else:
         assert np.allclose(got[..., :3], want[..., :3], rtol=1e-5, atol=0)
         if mode == "rgb":
@@ -448,7 +470,7 @@ def test_randomised_views(native, mips, seed):
     ctx.close()
 
 
-@pytest.mark.parametrize("mode", ["weighted", "depth", "rgb"])
+@pytest.mark.parametrize("mode", ["weighted", "depth", "rgb", "density"])
 @pytest.mark.parametrize("R", [200, 1024])
 def test_gather_kernel_class_boundaries(native, mips, mode, R):
     """Footprints right at the class boundary of the tile-gather kernel -- 64 px (nearest mip 0 -> bilinear: kernel G -> H2; a
@@ -490,6 +512,12 @@ def test_gather_kernel_class_boundaries(native, mips, mode, R):
             ctx.render(M, sf, mode=native.MODE_DEPTH)
             want, nfrag = oracle_render(pos, h, m, None, None, 1, M, sf, R, mips)
             assert np.allclose(ctx.read_image(), want, rtol=1e-5, atol=0)
+        elif mode == "density":
+            ctx.render(M, sf, mode=native.MODE_WEIGHTED)
+            want, nfrag = oracle_render(pos, h, m, None, None, 0, M, sf, R, mips)
+            got = ctx.read_image()
+            assert np.allclose(got[..., 0], want[..., 0], rtol=1e-5, atol=0)
+            assert (got[..., 1] == 0).all()
         else:
             ctx.upload_quantity(q)
             ctx.render(M, sf, mode=native.MODE_WEIGHTED)
@@ -500,6 +528,20 @@ def test_gather_kernel_class_boundaries(native, mips, mode, R):
             assert st["n_fragments"] == nfrag
         wide = int((h.astype(np.float64) * 2.0 * R / scale >= 64.0).sum())
         assert wide // 3 < st["n_huge"] <= wide     # (some of them are off-screen or outside the z-slab)
+    # density: the single-channel strip shapes / occupancies of kernel H2, both row walks, with and without fragment counting
+    if mode == "density":
+        for variant in (2, 4, 5, 6, 7):
+            for walk in (0, 1):
+                for count in (1, 0):
+                    ctx.set_option("huge_variant", variant); ctx.set_option("h2_walk", walk); ctx.set_option("count_fragments", count)
+                    ctx.render(M, sf, mode=native.MODE_WEIGHTED)
+                    got = ctx.read_image()
+                    assert np.allclose(got[..., 0], want[..., 0], rtol=1e-5, atol=0), (variant, walk)
+                    assert (got[..., 1] == 0).all(), (variant, walk)
+                    if count:
+                        assert ctx.stats()["n_fragments"] == nfrag, (variant, walk)
+        ctx.close()
+        return
     # kernel H2's other strip shape / occupancy builds (what other record counts select, and the A/B builds), exact culling on
     for variant in {"rgb": (4,), "weighted": (4,), "depth": (4,)}[mode]:
         ctx.set_option("huge_variant", variant)
@@ -731,3 +773,61 @@ def test_mid_footprints_with_weights_that_are_not_finite(native, mips, mode):
         assert (~finite).sum() > 0
     # (which of the TOUCHED pixels are finite may differ between the kernels: both skip the strips that lie outside the disc inscribed
     # in a footprint square -- where the kernel value is exactly 0 and "0 x inf" would be NaN -- and their strips differ in shape)
+
+
+@pytest.mark.parametrize("two_column_lane", [False, True], ids=["one_column", "one_lane_two_columns"])
+def test_density_one_column_footprints_share_pixels(native, mips, two_column_lane):
+    """Kernel S's one-column path of the density build (every lane of a wave draws one pixel: the lanes that hit the same pixel
+    are summed by DPP before one LDS add): sub-pixel footprints, one column and one row each, in clusters that fit the LDS window,
+    so that the 64 lanes of a wave hit 1, 2, 4, 5, 8, 64 and a random few distinct pixels -- the tree-sum rounds and the
+    lane-by-lane remainder.  With one lane per wave made two columns wide, the general path draws the same data.  Against the
+    oracle, exact fragment count included."""
+    from oracle import oracle_np
+    R, n_chunks = 256, 40
+    scale = R / 2.0                                         # 1 px = 1 length unit
+    M, sf = oracle_np.transform_matrix(np.eye(3), np.zeros(3), scale)
+    rs = np.random.RandomState(31)
+    n = 512 * n_chunks
+    lane = np.arange(n) % 64
+    wave = np.arange(n) // 64
+    patterns = [lambda l: 0 * l, lambda l: l % 2, lambda l: l // 16, lambda l: l % 5, lambda l: l // 8, lambda l: l,
+                lambda l: rs.randint(0, 3, size=l.shape), lambda l: (l * 7) % 3]
+    slot = np.zeros(n, dtype=np.int64)
+    for w in range(n // 64):
+        sel = wave == w
+        slot[sel] = patterns[w % len(patterns)](lane[sel])
+    # pixel of every slot: a 6 x 6 px grid of slots per wave, waves of a chunk side by side in a 40-px cluster
+    chunk = np.arange(n) // 512
+    cen = rs.randint(24, R - 24, size=(n_chunks, 2))
+    cen[:2] = [[2, 100], [R - 3, 7]]                        # clusters cut by the image edge
+    wic = wave % 8
+    pix = cen[chunk] + np.stack([(slot % 6) + 6 * (wic % 4) - 12, (slot // 6) % 6 + 6 * (wic // 4) - 6], axis=1)
+    P = rs.uniform(0.3, 1.9, n)
+    jit = rs.uniform(-1.0, 1.0, size=(n, 2)) * np.minimum(P, 2.0 - P)[:, None] * 0.45      # its own pixel centre covered, no other
+    pc = pix + 0.5 + jit
+    if two_column_lane:                                     # one lane per wave: centre on a column boundary, two columns wide
+        two = lane == 17
+        P[two] = 1.5
+        pc[two, 0] = pix[two, 0] + 1.0
+        pc[two, 1] = pix[two, 1] + 0.5
+    pos = np.zeros((n, 3), dtype=np.float32)
+    pos[:, 0] = pc[:, 0] - R / 2.0
+    pos[:, 1] = R / 2.0 - pc[:, 1]
+    h = (P * scale / (2.0 * R)).astype(np.float32)
+    m = rs.uniform(0.5, 2.0, n).astype(np.float32)
+    ctx = native.Context(R, 2)
+    ctx.set_kernel_mips(mips)
+    ctx.upload_particles(pos[:, 0], pos[:, 1], pos[:, 2], h, m)
+    want, nfrag = oracle_render(pos, h, m, None, None, 0, M, sf, R, mips)
+    for count in (1, 0):
+        ctx.set_option("count_fragments", count)
+        ctx.render(M, sf)
+        got = ctx.read_image()
+        st = ctx.stats()
+        assert st["n_mid"] == 0 and st["n_huge"] == 0 and st["n_small"] + st["n_culled"] == n, st
+        assert np.allclose(got[..., 0], want[..., 0], rtol=1e-5, atol=0), count
+        assert (got[..., 1] == 0).all()
+        if count:
+            assert st["n_fragments"] == nfrag
+    assert nfrag > 0.9 * n
+    ctx.close()

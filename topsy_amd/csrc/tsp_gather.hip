@@ -983,6 +983,78 @@ __global__ __launch_bounds__(H2T, OCC) void splat_narrow_gather_kernel(TileArgs 
 // ---------------------------------------------------------------------------------------------
 // band bins of the huge records
 // ---------------------------------------------------------------------------------------------
+// Huge records whose weights are not finite (an infinite or NaN mass, quantity or colour, or m / h^2 beyond float32)
+// ---------------------------------------------------------------------------------------------
+// A particle changes only the pixels its square covers (no fragment runs outside the reference's quad).  Kernel H2 cannot keep that
+// for such a weight: its row walk multiplies the weight by the factors of every column and row of a strip, and the factors of the
+// columns and rows the square does not cover are 0 -- 0 x inf = NaN in pixels the particle never reaches.  This pass finds those
+// records before kernel H2 (and the band fill) read the list, draws each of them pixel by pixel over its square with the canonical
+// arithmetic of the generic kernel, and negates its width in the list: kernel H2 and the band fill take only records of positive
+// width, the rgb rectangle counts use |width|.  Records with finite weights pass through untouched, so kernel H2's code is the same.
+// One read of the list per render block; the drawing is the rare path (one workgroup per found record, 256 pixels per step).
+template <int MODE>
+__global__ __launch_bounds__(256) void huge_nonfinite_kernel(float4 *__restrict__ geom, const float *__restrict__ w, long long n,
+                                                             int second_channel, TileArgs a) {
+    constexpr int C = (MODE == TSP_MODE_RGB) ? 4 : 2;
+    constexpr int NW = (MODE == TSP_MODE_RGB) ? 2 : 1;
+    constexpr int PER = 4;                 // records per thread
+    __shared__ int s_n;
+    __shared__ int s_rec[256 * PER];
+    if (threadIdx.x == 0) s_n = 0;
+    __syncthreads();
+    const long long first = (long long)blockIdx.x * 256 * PER + threadIdx.x;
+#pragma unroll
+    for (int k = 0; k < PER; ++k) {
+        const long long i = first + k * 256;
+        if (i >= n) break;
+        const float w0 = geom[i].w;
+        bool ok = __builtin_fabsf(w0) < __builtin_inff();
+        if (MODE == TSP_MODE_RGB || second_channel) ok = ok && __builtin_fabsf(w[i * NW]) < __builtin_inff();
+        if (NW == 2) ok = ok && __builtin_fabsf(w[i * NW + 1]) < __builtin_inff();
+        if (!ok) s_rec[atomicAdd(&s_n, 1)] = (int)(i - (long long)blockIdx.x * 256 * PER);
+    }
+    __syncthreads();
+    const int n_odd = s_n;
+    if (n_odd == 0) return;
+    const int R = a.cam.R;
+    unsigned long long nfrag = 0;
+    for (int r = 0; r < n_odd; ++r) {
+        const long long i = (long long)blockIdx.x * 256 * PER + s_rec[r];
+        const float4 g = geom[i];
+        Proj p;
+        p.pcx = g.x; p.pcy = g.y; p.P = g.z; p.half = 0.5f * g.z; p.invP = 1.0f / g.z;
+        const float a0 = g.w, a1 = (MODE == TSP_MODE_RGB || second_channel) ? w[i * NW] : 0.0f, a2 = (NW == 2) ? w[i * NW + 1] : 0.0f;
+        int ilo, ihi, jlo, jhi;
+        cover_range(p.pcx, p.half, R, ilo, ihi);
+        cover_range(p.pcy, p.half, R, jlo, jhi);
+        const int nx = ihi - ilo + 1;
+        const long long npx = (ilo <= ihi && jlo <= jhi) ? (long long)nx * (jhi - jlo + 1) : 0;
+        for (long long idx = threadIdx.x; idx < npx; idx += 256) {
+            const int jj = (int)(idx / nx);
+            const int j = jlo + jj, ii = ilo + (int)(idx - (long long)jj * nx);
+            const float k = sample_kernel(a.mips, p, -1, ((float)ii + 0.5f) - p.pcx, ((float)j + 0.5f) - p.pcy);
+            double *px = a.img + ((size_t)j * R + ii) * C;
+            if (MODE == TSP_MODE_RGB) {      // (channel 3, the square count, comes from the rectangle sums like every huge record's)
+                gatomic_add(px + 0, (double)(k * a0));
+                gatomic_add(px + 1, (double)(k * a1));
+                gatomic_add(px + 2, (double)(k * a2));
+            } else {
+                const float val = k * a0;
+                gatomic_add(px + 0, (double)val);
+                if (second_channel) gatomic_add(px + 1, (double)(val * a1));
+            }
+        }
+        nfrag += (unsigned long long)npx;
+        __syncthreads();                    // (every thread has read the record before it is marked)
+        if (threadIdx.x == 0) geom[i].z = -g.z;
+    }
+    if (a.count_frag && threadIdx.x == 0 && nfrag) {
+        atomicAdd(&a.cnt->n_fragments, nfrag);
+        atomicAdd(&a.cnt->n_frag_class[2], nfrag);
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
 // Every tile of kernel H2 used to scan the WHOLE huge list (at 1e9 particles: 128 tiles x 85 MB through eight non-coherent
 // L2s = 12.7 GB of fabric reads per launch, and 1/12 of the kernel's instructions spent on records that cannot reach the tile).
 // One pass copies every record into the bin of each 64-row image band its square reaches (a square of P pixels reaches
@@ -1010,7 +1082,8 @@ __global__ __launch_bounds__(256) void huge_band_fill_kernel(const float4 *__res
             // (margin: one pixel plus two ulps of the coordinate, so that it still covers the rounding of g.y -+ half beyond 2^23 px)
             const float half = 0.5f * g[k].z, mg = 1.0f + 2.4e-7f * (__builtin_fabsf(g[k].y) + half), lo = g[k].y - half - mg, hi = g[k].y + half + mg;
             // (non-finite or off-image squares: no band; kernel S emits only records that cover a pixel)
-            if (hi >= 0.0f && lo < (float)R && lo == lo && hi == hi) {
+            // (a negative width: a record with a weight that is not finite, drawn by huge_nonfinite_kernel)
+            if (g[k].z > 0.0f && hi >= 0.0f && lo < (float)R && lo == lo && hi == hi) {
                 b0[k] = max(0, (int)__builtin_floorf(fmaxf(lo, 0.0f) * (1.0f / HBAND_H)));
                 b1[k] = min(n_bands - 1, (int)__builtin_floorf(fminf(hi, (float)R) * (1.0f / HBAND_H)));
             }
@@ -1434,6 +1507,9 @@ static int launch_gather_mode(tsp_context *ctx, TileArgs ta, bool second_channel
     if (n_huge > 0) {
         ta.geom = huge_geom; ta.w = huge_w; ta.n_records = n_huge;
         TSP_REQUIRE(n_huge < (1ll << 31), TSP_EINVAL, "%lld deferred footprints in one render block (the tile-gather kernel indexes them with 32 bits)", n_huge);
+        hipLaunchKernelGGL(huge_nonfinite_kernel<MODE>, dim3((unsigned)((n_huge + 1023) / 1024)), dim3(256), 0, st,
+                           const_cast<float4 *>(huge_geom), huge_w, n_huge, second_channel ? 1 : 0, ta);
+        TSP_HIP(hipGetLastError());
         if ((rc = bin_huge_records<(MODE == TSP_MODE_RGB) ? 2 : 1>(ctx, ta, huge_geom, huge_w, n_huge))) return rc;
         if (MODE == TSP_MODE_RGB) {
             // three accumulator sets: 96 VGPRs at 5 waves/SIMD (11.5 against 12.5 ms at 4 for the 64-128 px band of config 4)

@@ -710,7 +710,7 @@ __global__ __launch_bounds__(256) void rect_count_corners_kernel(const float4 *_
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
     const float4 g = geom[i];
-    const float half = 0.5f * g.z;
+    const float half = 0.5f * __builtin_fabsf(g.z);      // (a huge record with a weight that is not finite carries -P: huge_nonfinite_kernel)
     int ilo, ihi, jlo, jhi;
     cover_range(g.x, half, R, ilo, ihi);
     cover_range(g.y, half, R, jlo, jhi);

@@ -38,6 +38,8 @@ __global__ __launch_bounds__(256) void splat_generic_kernel(Particles p, const i
     constexpr int C = (MODE == TSP_MODE_RGB) ? 4 : 2;
     const int lane = threadIdx.x & 63;
     const int R = cam.R;
+    // a density render (no quantity) leaves channel 1 alone: "+ val x 0" would turn it NaN under a weight that is not finite
+    const bool has_ch1 = MODE != TSP_MODE_WEIGHTED || p.q != nullptr;
     unsigned long long nfrag = 0, nculled = 0;
 
     for (int64_t base = (int64_t)blockIdx.x * 256 + (threadIdx.x & ~63); base < total;
@@ -87,7 +89,7 @@ __global__ __launch_bounds__(256) void splat_generic_kernel(Particles p, const i
                     } else {
                         const float val = k * w0;
                         atomic_add_f32(px + 0, val);
-                        atomic_add_f32(px + 1, val * w1);
+                        if (has_ch1) atomic_add_f32(px + 1, val * w1);
                     }
                 }
             }
@@ -119,7 +121,7 @@ __global__ __launch_bounds__(256) void splat_generic_kernel(Particles p, const i
                 } else {
                     const float val = k * a0;
                     atomic_add_f32(px + 0, val);
-                    atomic_add_f32(px + 1, val * a1);
+                    if (has_ch1) atomic_add_f32(px + 1, val * a1);
                 }
             }
             if (lane == 0) nfrag += bn;
