@@ -76,7 +76,8 @@ const char *tsp_last_error(void);
  * 105: the LDS scatter kernel of the footprints below 64 px (kernel M) is gone -- kernel G, a register gather over per-strip bins of
  * the deferred records, draws them at every size: the options "mid_split" and "debug_extra_lds" return TSP_EINVAL; new options
  * "mid_item_records", "mid_item_scale_milli", "stream_batch_chunks", "debug_gather_full_lut"; "stream_blocks_per_cu" now counts the
- * persistent workgroups of kernel S per CU (0 = as many as stay resident).  No entry point or struct changed. */
+ * persistent workgroups of kernel S per CU (0 = as many as stay resident).  No entry point or struct changed.
+ * 106: new entry point tsp_smoothing_lengths (k-nearest-neighbour smoothing lengths); nothing else changed. */
 int tsp_version(void);
 int tsp_stats_size(void);
 
@@ -211,6 +212,19 @@ int tsp_colormap_rgb_host(tsp_context *ctx, const float *img, int H, int W, int 
  * additively blended into a cleared target.  The float64 accumulator keeps the untiled render, so a
  * later tsp_render(clear = 0) continues from the raw image and the tiling is re-applied afterwards. */
 int tsp_tile_periodic(tsp_context *ctx, int n, const float *offsets_xy, const float *weights);
+
+/* SPH smoothing lengths by k-nearest neighbours (the pynbody.sph.smooth call of reference loader.py:222-240).
+ * Host arrays in and out; uses ctx's device and stream only: resident particles, image, accumulator and tsp_stats unchanged.
+ * For a particle i with finite coordinates, h_out[i] = 0.5f * sqrtf(k-th smallest d2) over every j with finite coordinates
+ * (j = i included, at distance 0; ties and duplicates count), where in float32 with these operations in this order
+ *     dx = x[j] - x[i] (dy, dz alike);  period > 0 only: t = dx / period; t = rint(t); dx = dx - (period * t);
+ *     d2 = (dx * dx + dy * dy) + dz * dz,
+ * k = n_neighbours.  A particle with a non-finite coordinate gets NaN and is nobody's neighbour.  2 <= n_neighbours <= 64,
+ * period = 0 (open box) or finite and > 0, 1 <= n < 2^31, at least n_neighbours particles with finite coordinates; anything
+ * else returns TSP_EINVAL and writes nothing.  Device memory is allocated for the call only (about 48 bytes per particle);
+ * a failed allocation returns TSP_ENOMEM. */
+int tsp_smoothing_lengths(tsp_context *ctx, int64_t n, const float *x, const float *y, const float *z,
+                          int n_neighbours, float period, float *h_out);
 
 /* On-device autorange support (replaces the image read-back + host
  * np.percentile of Colormap.autorange_vmin_vmax / _autorange_using_values, reference

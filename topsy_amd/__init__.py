@@ -7,6 +7,8 @@
 
 The GPU work goes through libtopsy_splat.so (include/topsy_splat.h).  There is no CPU fallback.
 """
+import numpy as np
+
 from . import config
 from .drawreason import DrawReason
 
@@ -23,13 +25,37 @@ def test(nparticle=config.TEST_DATA_NUM_PARTICLES_DEFAULT, **kwargs):
                                  **kwargs)
 
 
-def from_arrays(pos, smooth, mass, quantities=None, rgb=None, with_cells=False, **kwargs):
-    """Visualizer over caller-supplied numpy arrays (e.g. taken from a pynbody snapshot)."""
+def from_arrays(pos, smooth, mass, quantities=None, rgb=None, with_cells=False, n_smooth=None, periodicity_scale=None,
+                **kwargs):
+    """Visualizer over caller-supplied numpy arrays (e.g. taken from a pynbody snapshot).
+
+    smooth=None computes the smoothing lengths on the GPU from the n_smooth (default config.SMOOTH_NEIGHBOURS) nearest
+    neighbours, in the periodic box of side periodicity_scale if one is given; vis.data_loader.get_smooth() returns them."""
     from . import visualizer, loader
     return visualizer.Visualizer(data_loader_class=loader.ArrayDataLoader,
                                  data_loader_kwargs={"pos": pos, "smooth": smooth, "mass": mass,
-                                                     "quantities": quantities, "rgb": rgb, "with_cells": with_cells},
+                                                     "quantities": quantities, "rgb": rgb, "with_cells": with_cells,
+                                                     "n_smooth": n_smooth, "periodicity_scale": periodicity_scale},
                                  **kwargs)
+
+
+def smoothing_lengths(pos, n_smooth=config.SMOOTH_NEIGHBOURS, periodicity_scale=None, device_id=0):
+    """SPH smoothing lengths of an (n, 3) position array on GPU `device_id`: half the distance to the n_smooth-th nearest
+    particle, the particle itself included (pynbody's snap['smooth'] convention); NaN where a coordinate is not finite.
+    periodicity_scale: side of a periodic box (None: open).  Returns float32 (n,), to be cached as the caller likes."""
+    from . import _native, loader
+    n_smooth, period = loader.check_smoothing_arguments(n_smooth, periodicity_scale)
+    pos = np.asarray(pos, dtype=np.float32)
+    if pos.ndim != 2 or pos.shape[1] != 3:
+        raise ValueError(f"pos must have shape (n, 3), not {pos.shape}")
+    n_finite = int(np.isfinite(pos).all(axis=1).sum())
+    if n_finite < n_smooth:
+        raise ValueError(f"{n_finite} particles have finite coordinates; n_smooth = {n_smooth} needs at least as many")
+    ctx = _native.Context(1, 2, device_id)
+    try:
+        return ctx.smoothing_lengths(pos[:, 0], pos[:, 1], pos[:, 2], n_smooth, period)
+    finally:
+        ctx.close()
 
 
 def synthetic_on_device(n_total, first=0, count=None, h_cap=0.0, **kwargs):

@@ -16,7 +16,7 @@ MODE_WEIGHTED, MODE_DEPTH, MODE_RGB = 0, 1, 2
 PIPE_DEFAULT, PIPE_GENERIC = 0, 1
 SAMPLE_BILINEAR_MIP0, SAMPLE_BILINEAR_MIP = 0x10, 0x20      # diagnostic sampling rules (generic kernel)
 UNIQUE_ID_BYTES = 128
-ABI_VERSION = 105            # include/topsy_splat.h: tsp_version()
+ABI_VERSION = 106            # include/topsy_splat.h: tsp_version()
 
 
 class BackendUnavailable(RuntimeError):
@@ -82,6 +82,7 @@ SIGNATURES = {
     "tsp_colormap_rgb_host": (ctypes.c_int, [_ctx, _fp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_float,
                                              ctypes.c_float, ctypes.c_float, _u8p, _fp]),
     "tsp_tile_periodic": (ctypes.c_int, [_ctx, ctypes.c_int, _fp, _fp]),
+    "tsp_smoothing_lengths": (ctypes.c_int, [_ctx, ctypes.c_int64, _fp, _fp, _fp, ctypes.c_int, ctypes.c_float, _fp]),
     "tsp_content_sort": (ctypes.c_int, [_ctx, ctypes.c_int, ctypes.c_float, _i64p, _i64p]),
     "tsp_content_values": (ctypes.c_int, [_ctx, _i64p, ctypes.c_int, _fp]),
     "tsp_get_stats": (ctypes.c_int, [_ctx, ctypes.POINTER(Stats)]),
@@ -319,6 +320,17 @@ class Context:
         if off.size != 2 * w.size:
             raise ValueError("offsets must have shape (n, 2) for n weights")
         _check(self._lib.tsp_tile_periodic(self._h, w.size, _ptr(off), _ptr(w)))
+
+    def smoothing_lengths(self, x, y, z, n_neighbours=32, period=None):
+        """SPH smoothing lengths of caller-ordered float32 positions (tsp_smoothing_lengths): half the distance to the
+        n_neighbours-th nearest particle, the particle itself included; NaN where a coordinate is not finite.  period: the
+        side of a periodic box (None or 0: open).  Uses this context's device only; what is resident stays as it is."""
+        n = len(x)
+        x, y, z = _f32(x, n, "x"), _f32(y, n, "y"), _f32(z, n, "z")
+        out = np.empty(n, dtype=np.float32)
+        _check(self._lib.tsp_smoothing_lengths(self._h, n, _ptr(x), _ptr(y), _ptr(z), int(n_neighbours),
+                                               float(np.float32(period or 0.0)), _ptr(out)))
+        return out
 
     def content_sort(self, kind, scale=1.0):
         """Sort the finite content values on the device; returns (n_finite, n_nonpositive)."""

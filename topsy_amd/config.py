@@ -17,6 +17,9 @@ REFERENCE_MAX_PARTICLES_PER_EXPORT_RENDERCALL = 2 ** 25   # config.py:22
 MAX_PARTICLES_PER_EXPORT_RENDERCALL = 2 ** 40
 DEFAULT_CELLS_NSIDE = 16             # config.py:27
 CELL_LAYOUT_FRACTIONAL_PADDING = 1e-5  # config.py:33
+# neighbours of the smoothing length a snapshot without one gets (tsp_smoothing_lengths): pynbody.sph.smooth's default,
+# called by the reference's PynbodyDataLoader._perform_smoothing (loader.py:222-240)
+SMOOTH_NEIGHBOURS = 32
 
 # --- backend-specific knobs (no reference counterpart) -------------------------------------
 # smallest number of uniform random strata used by the load-time spatial ordering (tsp_reorder_spatial):

@@ -7,6 +7,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <cmath>
 #include <vector>
 
 #include "tsp_internal.h"
@@ -165,7 +166,7 @@ using namespace tsp;
 extern "C" {
 
 const char *tsp_last_error(void) { return g_err; }
-int tsp_version(void) { return 105; }     // 101: tsp_stats gained ms_mega, n_mega (16 bytes); 102: the per-kernel fragment counts (32 bytes); 103: n_chunk_culled (8 bytes); 104: matrix-core / kernel-I options removed; 105: kernel M's options removed (kernel G draws the mid footprints)
+int tsp_version(void) { return 106; }     // 106: tsp_smoothing_lengths; 101: tsp_stats gained ms_mega, n_mega (16 bytes); 102: the per-kernel fragment counts (32 bytes); 103: n_chunk_culled (8 bytes); 104: matrix-core / kernel-I options removed; 105: kernel M's options removed (kernel G draws the mid footprints)
 int tsp_stats_size(void) { return (int)sizeof(tsp_stats); }
 
 int tsp_device_count(void) {
@@ -736,6 +737,18 @@ int tsp_colormap_rgb_host(tsp_context *ctx, const float *img, int H, int W, int 
     if (out_rgba_f32) TSP_HIP(hipMemcpyAsync(out_rgba_f32, d_of, of, hipMemcpyDeviceToHost, ctx->stream));
     TSP_HIP(hipStreamSynchronize(ctx->stream));
     return TSP_OK;
+}
+
+int tsp_smoothing_lengths(tsp_context *ctx, int64_t n, const float *x, const float *y, const float *z, int n_neighbours,
+                          float period, float *h_out) {
+    TSP_REQUIRE(ctx && x && y && z && h_out, TSP_EINVAL, "NULL argument");
+    TSP_REQUIRE(n >= 1 && n < (1ll << 31), TSP_EINVAL, "n = %lld outside [1, 2^31)", (long long)n);
+    TSP_REQUIRE(n_neighbours >= 2 && n_neighbours <= 64, TSP_EINVAL, "n_neighbours = %d outside [2, 64]", n_neighbours);
+    TSP_REQUIRE(period == 0.0f || (std::isfinite(period) && period > 0.0f), TSP_EINVAL,
+                "period must be 0 (open box) or finite and > 0, not %g", (double)period);
+    TSP_REQUIRE(n >= n_neighbours, TSP_EINVAL, "%lld particles, n_neighbours = %d", (long long)n, n_neighbours);
+    TSP_HIP(hipSetDevice(ctx->device));
+    return smoothing_lengths(ctx, n, x, y, z, n_neighbours, period == 0.0f ? 0.0f : period, h_out);
 }
 
 int tsp_tile_periodic(tsp_context *ctx, int n, const float *offsets_xy, const float *weights) {

@@ -227,4 +227,6 @@ int launch_image_convert(tsp_context *ctx, bool to_float);
 int tile_periodic(tsp_context *ctx, int n, const float *h_offsets, const float *h_weights);
 int content_sort(tsp_context *ctx, int kind, float scale, int64_t *n_finite, int64_t *n_nonpositive);   // image64 -> image (true) or image -> image64 (false)
 int ensure_array(float **p, int64_t n);
+int smoothing_lengths(tsp_context *ctx, int64_t n, const float *x, const float *y, const float *z, int k, float period,
+                      float *h_out);   // tsp_smooth.hip: per-call DeviceScratch only, no context state
 }  // namespace tsp

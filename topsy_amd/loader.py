@@ -158,18 +158,42 @@ class TestDataLoader(AbstractDataLoader):
         return 100.0 if self._periodic else None
 
 
+def check_smoothing_arguments(n_smooth, periodicity_scale):
+    """The arguments of a smoothing-length computation, checked on the host (tsp_smoothing_lengths would refuse them):
+    returns (n_smooth as int, period as float, 0 = open box).  Raises ValueError."""
+    if isinstance(n_smooth, bool) or not isinstance(n_smooth, (int, np.integer)) or not 2 <= n_smooth <= 64:
+        raise ValueError(f"n_smooth must be an integer from 2 to 64, not {n_smooth!r}")
+    if periodicity_scale is None:
+        return int(n_smooth), 0.0
+    try:
+        period = float(periodicity_scale)
+    except (TypeError, ValueError):
+        raise ValueError(f"periodicity_scale must be None or a finite number > 0, not {periodicity_scale!r}") from None
+    if not (np.isfinite(period) and 0 < period <= float(np.finfo(np.float32).max)):
+        raise ValueError(f"periodicity_scale must be None or a finite number > 0, not {periodicity_scale!r}")
+    return int(n_smooth), period
+
+
 class ArrayDataLoader(AbstractDataLoader):
     """Particles given as numpy arrays (e.g. pulled from a pynbody snapshot by the caller:
-    snap['pos'], snap['smooth'], snap['mass'], ...; reference PynbodyDataInMemory, loader.py:79-154)."""
+    snap['pos'], snap['smooth'], snap['mass'], ...; reference PynbodyDataInMemory, loader.py:79-154).
+
+    smooth=None: the snapshot has no smoothing lengths (dark matter, stars).  The loader then records that it needs them
+    (`needs_smoothing`); ParticleBuffers computes them on the GPU from the n_smooth nearest neighbours before the upload
+    (the reference calls pynbody.sph.smooth there, loader.py:222-240) and hands them back through set_smooth()."""
 
     # reference PynbodyDataInMemory.get_rgb_masses (loader.py:115-121): (band, weight) per rgb channel
     RGB_BANDS = (("I", 0.5), ("V", 1.0), ("U", 1.0))
 
     def __init__(self, device=None, pos=None, smooth=None, mass=None, quantities=None, rgb=None,
-                 units="kpc", periodicity_scale=None, with_cells=False, band_magnitudes=None):
+                 units="kpc", periodicity_scale=None, with_cells=False, band_magnitudes=None, n_smooth=None):
         super().__init__(device)
         self._pos = np.asarray(pos, dtype=np.float32)
-        self._smooth = np.asarray(smooth, dtype=np.float32)
+        self.needs_smoothing = smooth is None
+        self.n_smooth = config.SMOOTH_NEIGHBOURS if n_smooth is None else n_smooth
+        if self.needs_smoothing or n_smooth is not None:
+            self.n_smooth, _ = check_smoothing_arguments(self.n_smooth, periodicity_scale if self.needs_smoothing else None)
+        self._smooth = None if smooth is None else np.asarray(smooth, dtype=np.float32)
         self._mass = np.asarray(mass, dtype=np.float32)
         self._quantities = {k: np.asarray(v, dtype=np.float32) for k, v in (quantities or {}).items()}
         self._rgb = None if rgb is None else np.asarray(rgb, dtype=np.float32)
@@ -177,7 +201,12 @@ class ArrayDataLoader(AbstractDataLoader):
         self._mags = None if band_magnitudes is None else {k: np.asarray(v, dtype=np.float64) for k, v in band_magnitudes.items()}
         self._units = units
         self._period = periodicity_scale
-        if not (len(self._pos) == len(self._smooth) == len(self._mass)):
+        if self.needs_smoothing:
+            if self._pos.ndim != 2 or self._pos.shape[1] != 3:
+                raise ValueError(f"pos must have shape (n, 3), not {self._pos.shape}")
+            if len(self._pos) != len(self._mass):
+                raise ValueError("pos and mass must have the same length")
+        elif not (len(self._pos) == len(self._smooth) == len(self._mass)):
             raise ValueError("pos, smooth and mass must have the same length")
         if with_cells:
             # cell sort + shuffle inside cells, as PynbodyDataInMemory.__init__ (loader.py:88-97)
@@ -186,7 +215,9 @@ class ArrayDataLoader(AbstractDataLoader):
             self._cell_layout, order = cell_layout.CellLayout.from_positions(self._pos, lo - pad, hi + pad,
                                                                               config.DEFAULT_CELLS_NSIDE)
             order = order[self._cell_layout.randomize_within_cells()]
-            self._pos, self._smooth, self._mass = self._pos[order], self._smooth[order], self._mass[order]
+            self._pos, self._mass = self._pos[order], self._mass[order]
+            if self._smooth is not None:
+                self._smooth = self._smooth[order]
             self._quantities = {k: v[order] for k, v in self._quantities.items()}
             if self._rgb is not None:
                 self._rgb = self._rgb[order]
@@ -200,7 +231,16 @@ class ArrayDataLoader(AbstractDataLoader):
         return self._pos
 
     def get_smooth(self):
+        if self._smooth is None:
+            raise RuntimeError("no smoothing lengths yet: they are computed on the GPU when the particles are uploaded")
         return self._smooth
+
+    def set_smooth(self, smooth):
+        """Smoothing lengths in this loader's particle order (computed by ParticleBuffers when smooth=None was given)."""
+        smooth = np.asarray(smooth, dtype=np.float32)
+        if smooth.shape != (len(self),):
+            raise ValueError(f"smooth must have shape ({len(self)},), not {smooth.shape}")
+        self._smooth = smooth
 
     def get_mass(self):
         return self._mass

@@ -195,6 +195,11 @@ class MultiGpuContext:
 
         self._map(lambda g, c: c.upload_band_magnitudes(np.ascontiguousarray(self._take(mags, g, axis=1)), weights))
 
+    def smoothing_lengths(self, x, y, z, n_neighbours=32, period=None):
+        """Smoothing lengths of the whole (caller-ordered) snapshot, computed on the first context: the neighbour search needs
+        every particle in one place.  Touches no shard's particles or image, so it needs no end_frame first."""
+        return self.contexts[0].smoothing_lengths(x, y, z, n_neighbours, period)
+
     def generate_synthetic(self, n_total, first=0, count=None, seed=1337, h_cap=0.0, with_quantity=False, with_rgb=False):
         count = n_total - first if count is None else count
         # the generator's index bijection makes every index range a uniform sample: contiguous shards are balanced

@@ -53,6 +53,13 @@ class ParticleBuffers:
                 self.context.reorder_spatial(self._num_strata(ld.count), ld.seed)
                 self._note_ordering()
             return
+        if getattr(ld, "needs_smoothing", False) and getattr(ld, "_smooth", None) is None:
+            # no smoothing lengths in the snapshot: k nearest neighbours on the GPU (the reference runs pynbody.sph.smooth
+            # on the CPU here, loader.py:222-240), in the loader's order, before anything is uploaded
+            logger.info(f"Computing smoothing lengths from {ld.n_smooth} neighbours on the GPU")
+            pos = ld.get_positions()
+            ld.set_smooth(self.context.smoothing_lengths(pos[:, 0], pos[:, 1], pos[:, 2], ld.n_smooth,
+                                                         ld.get_periodicity_scale() or 0.0))
         logger.info("Uploading position+smoothing+mass arrays")
         ps = ld.get_pos_smooth()
         self.context.upload_particles(ps[:, 0], ps[:, 1], ps[:, 2], ps[:, 3], ld.get_mass())
