@@ -77,7 +77,9 @@ const char *tsp_last_error(void);
  * the deferred records, draws them at every size: the options "mid_split" and "debug_extra_lds" return TSP_EINVAL; new options
  * "mid_item_records", "mid_item_scale_milli", "stream_batch_chunks", "debug_gather_full_lut"; "stream_blocks_per_cu" now counts the
  * persistent workgroups of kernel S per CU (0 = as many as stay resident).  No entry point or struct changed.
- * 106: new entry point tsp_smoothing_lengths (k-nearest-neighbour smoothing lengths); nothing else changed. */
+ * 106: new entry point tsp_smoothing_lengths (k-nearest-neighbour smoothing lengths); nothing else changed.
+ * 107: surface rendering: tsp_set_sphere_mips, tsp_density_order_stats, tsp_render_surface, tsp_surface_present and the
+ * struct tsp_surface_params; nothing else changed. */
 int tsp_version(void);
 int tsp_stats_size(void);
 
@@ -225,6 +227,57 @@ int tsp_tile_periodic(tsp_context *ctx, int n, const float *offsets_xy, const fl
  * a failed allocation returns TSP_ENOMEM. */
 int tsp_smoothing_lengths(tsp_context *ctx, int64_t n, const float *x, const float *y, const float *z,
                           int n_neighbours, float period, float *h_out);
+
+/* Surface rendering: DepthSPHWithOcclusion + ColorAsSurfaceMap (reference src/topsy/sph.py:448-656, shaders/sph.wgsl:94-122,
+ * 149-158, shaders/smooth.wgsl, shaders/surface.wgsl, colormap/surface.py).  Float32 throughout, operations in the order written.
+ *
+ * tsp_set_sphere_mips: the sphere texture (LocalSphereKernel, normalisation 1): 64^2 + 32^2 + 16^2 + 8^2 texel-centre samples of
+ * sqrtf(4 - d^2) for d < 2, else -0.01; same layout and arguments as tsp_set_kernel_mips, stored next to the SPH mips.
+ *
+ * tsp_density_order_stats: the values at the given ascending ranks of rho = m / ((h * h) * h) over the n resident particles, sorted
+ * as numpy sorts float32 (NaN last).  Device memory for the call only (about 12 bytes per particle); resident data, image and
+ * accumulator are unchanged.  Needs mass (TSP_EINVAL otherwise) and 0 <= ranks[i] < n.
+ *
+ * tsp_render_surface: the occlusion pass.  A particle is drawn iff rho > density_cut and it passes the keep rule of tsp_render
+ * (0 <= cz <= 1, finite P > 0, pcx, pcy).  Its covered pixels and texel rule are those of tsp_render; k is the sphere-texture
+ * sample.  For a covered pixel: depth = cz + zs * k with zs = (h * scale_factor) * 0.5; the fragment is dropped if k < 0; it
+ * competes with dc = min(depth, 1) if dc > 0.  Per pixel the fragment with the largest dc wins, on equal dc the lowest resident
+ * index.  The float64 accumulator holds 64-bit keys (bits(dc) << 32) | (0xFFFFFFFF - index) while the context is in this state;
+ * the presentation image becomes 2-channel (q_winner, depth_winner) with the unclamped depth, or (0, 0) where nothing won, q = 0
+ * without an active quantity.  clear = 0 continues the keys of an earlier tsp_render_surface call (any split of the particles
+ * into blocks gives the same image bit for bit); after a surface call tsp_render(clear = 0) returns TSP_ESTATE, clear = 1
+ * renders as usual.  Needs a context with mass, fewer than 2^32 resident particles and tsp_set_sphere_mips (TSP_EINVAL /
+ * TSP_ESTATE).  tsp_get_stats afterwards: n_particles, ms_total; ms_stream = the draw, ms_mid = the resolve. */
+typedef struct tsp_surface_params {
+    double smoothing_scale;      /* bilateral filter: sig = max(smoothing_scale, 1e-5), ss = (float)(sig * R), rs = (float)(sig * 2) */
+    float depth_scale;           /* D = depth * depth_scale */
+    float light_direction[3];
+    float light_color[3];
+    float ambient_color[3];
+    float vmin, vmax;            /* material range (weighted_average only) */
+    int weighted_average;        /* 0: material 1; 1: colormap LUT of q (log: of canon_log10f(q)) */
+    int log_scale;
+    const float *lut_rgba;       /* n_lut RGBA float32 entries (weighted_average only) */
+    int n_lut;
+} tsp_surface_params;
+
+/* tsp_surface_present: the bilateral filter of the 2-channel image (q, depth), then optionally the lit shading.
+ *   n = min((int)(ss * 4) + 1, 100), half = n / 2; for dy in [-half, half] (outer), dx in [-half, half] (inner), sample
+ *   coordinates clamped to the image: ds = sqrtf((float)(dx*dx + dy*dy)); ws = exp(-(ds*ds) / ((2*ss)*ss));
+ *   dd = |d - d_centre|; wr = exp(-(dd*dd) / ((2*rs)*rs)); w = ws*wr; sum += d*w; wsum += w.  Output (q_centre, sum / wsum);
+ *   exp is the canonical expf of the colormap.  content_out: R*R*2 floats of it (or NULL).
+ *   Shading per pixel of the filtered image F, neighbours clamped at the edges, D = F.depth * depth_scale:
+ *   n = normalize(-(D_right - D_left) * 0.5, -(D_down - D_up) * 0.5, 1 / R) (row j+1 is down; length sqrtf((x*x + y*y) + z*z),
+ *   each component divided by it); rgb = (light_color * max(n.L, 0) * mat + ambient_color * mat) * (clamp(D, 0, 0.5) * 2),
+ *   n.L = (x*Lx + y*Ly) + z*Lz; alpha 1; mat as the scalar colormap's LUT lerp of clamp((v - vmin) / (vmax - vmin)), NaN -> 0.
+ *   rgba8_out: R*R*4 bytes, floor(255 * clamp(c) + 0.5) (or NULL).  ms_out: [filter, shading] GPU milliseconds (or NULL).
+ * Needs the active image to be 2-channel (TSP_EINVAL otherwise).  The image and accumulator are unchanged. */
+int tsp_set_sphere_mips(tsp_context *ctx, const float *lut, int n0, int n_levels);
+int tsp_density_order_stats(tsp_context *ctx, const int64_t *ranks, int n_ranks, float *values_out);
+int tsp_render_surface(tsp_context *ctx, const float *M, float scale_factor, float density_cut, const int64_t *starts,
+                       const int64_t *lens, int n_ranges, int clear, double *gpu_ms_out);
+int tsp_surface_present(tsp_context *ctx, const tsp_surface_params *params, float *content_out, uint8_t *rgba8_out,
+                        double *ms_out);
 
 /* On-device autorange support (replaces the image read-back + host
  * np.percentile of Colormap.autorange_vmin_vmax / _autorange_using_values, reference

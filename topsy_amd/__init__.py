@@ -58,6 +58,14 @@ def smoothing_lengths(pos, n_smooth=config.SMOOTH_NEIGHBOURS, periodicity_scale=
         ctx.close()
 
 
+def SurfaceView(visualizer, **colormap_params):
+    """Surface rendering of `visualizer`'s scene (the reference's render_mode "surface"): the front-most sphere of every
+    particle above a density cut, smoothed and lit.  render(), get_sph_image() ((R, R, 2) filtered (q, depth)),
+    get_sph_presentation_image() ((R, R, 4) uint8), colormap_autorange(), view["depth_scale"] etc., density_cut_percentile."""
+    from . import surface
+    return surface.SurfaceView(visualizer, **colormap_params)
+
+
 def synthetic_on_device(n_total, first=0, count=None, h_cap=0.0, **kwargs):
     """Visualizer over a device-generated shard of the synthetic snapshot (1e8-1e9 particles)."""
     from . import visualizer, loader

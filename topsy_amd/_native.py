@@ -16,7 +16,15 @@ MODE_WEIGHTED, MODE_DEPTH, MODE_RGB = 0, 1, 2
 PIPE_DEFAULT, PIPE_GENERIC = 0, 1
 SAMPLE_BILINEAR_MIP0, SAMPLE_BILINEAR_MIP = 0x10, 0x20      # diagnostic sampling rules (generic kernel)
 UNIQUE_ID_BYTES = 128
-ABI_VERSION = 106            # include/topsy_splat.h: tsp_version()
+ABI_VERSION = 107            # include/topsy_splat.h: tsp_version()
+
+
+class SurfaceParams(ctypes.Structure):
+    """struct tsp_surface_params (include/topsy_splat.h)."""
+    _fields_ = [("smoothing_scale", ctypes.c_double), ("depth_scale", ctypes.c_float),
+                ("light_direction", ctypes.c_float * 3), ("light_color", ctypes.c_float * 3), ("ambient_color", ctypes.c_float * 3),
+                ("vmin", ctypes.c_float), ("vmax", ctypes.c_float), ("weighted_average", ctypes.c_int), ("log_scale", ctypes.c_int),
+                ("lut_rgba", ctypes.POINTER(ctypes.c_float)), ("n_lut", ctypes.c_int)]
 
 
 class BackendUnavailable(RuntimeError):
@@ -83,6 +91,11 @@ SIGNATURES = {
                                              ctypes.c_float, ctypes.c_float, _u8p, _fp]),
     "tsp_tile_periodic": (ctypes.c_int, [_ctx, ctypes.c_int, _fp, _fp]),
     "tsp_smoothing_lengths": (ctypes.c_int, [_ctx, ctypes.c_int64, _fp, _fp, _fp, ctypes.c_int, ctypes.c_float, _fp]),
+    "tsp_set_sphere_mips": (ctypes.c_int, [_ctx, _fp, ctypes.c_int, ctypes.c_int]),
+    "tsp_density_order_stats": (ctypes.c_int, [_ctx, _i64p, ctypes.c_int, _fp]),
+    "tsp_render_surface": (ctypes.c_int, [_ctx, _fp, ctypes.c_float, ctypes.c_float, _i64p, _i64p, ctypes.c_int, ctypes.c_int,
+                                          ctypes.POINTER(ctypes.c_double)]),
+    "tsp_surface_present": (ctypes.c_int, [_ctx, ctypes.c_void_p, _fp, _u8p, ctypes.POINTER(ctypes.c_double)]),
     "tsp_content_sort": (ctypes.c_int, [_ctx, ctypes.c_int, ctypes.c_float, _i64p, _i64p]),
     "tsp_content_values": (ctypes.c_int, [_ctx, _i64p, ctypes.c_int, _fp]),
     "tsp_get_stats": (ctypes.c_int, [_ctx, ctypes.POINTER(Stats)]),
@@ -331,6 +344,65 @@ class Context:
         _check(self._lib.tsp_smoothing_lengths(self._h, n, _ptr(x), _ptr(y), _ptr(z), int(n_neighbours),
                                                float(np.float32(period or 0.0)), _ptr(out)))
         return out
+
+    # ---- surface (include/topsy_splat.h "Surface rendering") ---------------------------------
+    def set_sphere_mips(self, mips, n0=64, n_levels=4):
+        mips = _f32(mips, name="sphere mips")
+        _check(self._lib.tsp_set_sphere_mips(self._h, _ptr(mips), n0, n_levels))
+
+    def density_order_stats(self, ranks):
+        """Values of rho = m / h^3 over the resident particles at the given ascending ranks (numpy's sort order, NaN last)."""
+        r = np.ascontiguousarray(ranks, dtype=np.int64)
+        out = np.empty(len(r), dtype=np.float32)
+        _check(self._lib.tsp_density_order_stats(self._h, r.ctypes.data_as(_i64p), len(r), _ptr(out)))
+        return out
+
+    def render_surface(self, matrix, scale_factor, density_cut, starts=None, lens=None, clear=True):
+        """The occlusion pass: (q, depth) of the front-most sphere per pixel becomes the 2-channel image; returns GPU ms."""
+        M = _f32(np.asarray(matrix, dtype=np.float32).reshape(16), 16, "matrix")
+        ms = ctypes.c_double(0.0)
+        if starts is None:
+            sp = lp = None
+            nr = 0
+        else:
+            s = np.ascontiguousarray(starts, dtype=np.int64)
+            l = np.ascontiguousarray(lens, dtype=np.int64)
+            if s.shape != l.shape or s.ndim != 1:
+                raise ValueError("starts and lens must be 1-D arrays of equal length")
+            if len(s) == 0:
+                s = np.zeros(1, dtype=np.int64)
+                l = np.zeros(1, dtype=np.int64)
+            sp, lp, nr = s.ctypes.data_as(_i64p), l.ctypes.data_as(_i64p), len(s)
+        _check(self._lib.tsp_render_surface(self._h, _ptr(M), float(scale_factor), float(np.float32(density_cut)), sp, lp, nr,
+                                            int(bool(clear)), ctypes.byref(ms)))
+        self.active_channels = 2
+        return ms.value
+
+    def surface_present(self, smoothing_scale=0.01, depth_scale=1.0, light_direction=(0.0, 0.0, 1.0), light_color=(1.0, 1.0, 1.0),
+                        ambient_color=(0.2, 0.2, 0.2), vmin=0.0, vmax=1.0, weighted_average=False, log=False, lut_rgba=None,
+                        content=True, rgba=True, timings=None):
+        """Bilateral filter of the (q, depth) image, then the lit shading.  Returns (content (R, R, 2) float32 or None,
+        rgba (R, R, 4) uint8 or None); `timings`, a list, receives [filter ms, shading ms]."""
+        p = SurfaceParams()
+        p.smoothing_scale = float(smoothing_scale)
+        p.depth_scale = float(depth_scale)
+        p.light_direction[:] = [float(np.float32(v)) for v in light_direction]
+        p.light_color[:] = [float(np.float32(v)) for v in light_color]
+        p.ambient_color[:] = [float(np.float32(v)) for v in ambient_color]
+        p.vmin, p.vmax = float(np.float32(vmin)), float(np.float32(vmax))
+        p.weighted_average, p.log_scale = int(bool(weighted_average)), int(bool(log))
+        lut = None
+        if weighted_average:
+            lut = _f32(lut_rgba, name="lut")
+            p.lut_rgba, p.n_lut = _ptr(lut), lut.size // 4
+        R = self.resolution
+        c = np.empty((R, R, 2), dtype=np.float32) if content else None
+        o = np.empty((R, R, 4), dtype=np.uint8) if rgba else None
+        ms = (ctypes.c_double * 2)()
+        _check(self._lib.tsp_surface_present(self._h, ctypes.byref(p), _ptr(c), None if o is None else o.ctypes.data_as(_u8p), ms))
+        if timings is not None:
+            timings[:] = [ms[0], ms[1]]
+        return c, o
 
     def content_sort(self, kind, scale=1.0):
         """Sort the finite content values on the device; returns (n_finite, n_nonpositive)."""

@@ -83,7 +83,7 @@ class ColormapHolder:
 
     def colormap_kind(self):
         """'bivariate' | 'rgb' | 'scalar': the family of the active implementation (what the reference's
-        make_ui_controller dispatches on, src/topsy/colormap/__init__.py:131-147; 'surface' is out of scope here)."""
+        make_ui_controller dispatches on, src/topsy/colormap/__init__.py:131-147; 'surface' belongs to topsy_amd.SurfaceView)."""
         self._check_valid()
         if isinstance(self._impl, BivariateColormap):
             return "bivariate"

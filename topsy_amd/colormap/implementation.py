@@ -26,8 +26,22 @@ def percentile_from_order_statistics(fetch, first, n, q, transform=None):
     the data dtype, so a Python-float q interpolates in float32 and an array q in float64; virtual index
     (n-1)*q; _lerp with its t >= 0.5 branch.  The device autorange therefore equals the host one bit for
     bit (tests/test_host_logic.py, tests/test_gpu_visualizer.py)."""
+    return _quantile_from_order_statistics(fetch, first, n, q, np.true_divide(q, np.float32(100)), transform)
+
+
+def quantile_from_order_statistics(fetch, n, quantiles):
+    """np.quantile(sample, quantiles) (method 'linear') of the float32 `sample` known through its order statistics in numpy's sort
+    order (NaN last): the same arithmetic as percentile_from_order_statistics with the quantiles as given, and numpy's NaN rule --
+    a sample holding a NaN has NaN at every quantile."""
+    last = np.asarray(fetch(np.array([n - 1])), dtype=np.float32)[0]
+    if np.isnan(last):
+        dtype = np.result_type(np.float32, np.asarray(quantiles).dtype)
+        return np.full(np.shape(quantiles), np.nan, dtype=dtype) if np.ndim(quantiles) else dtype.type(np.nan)
+    return _quantile_from_order_statistics(fetch, 0, n, quantiles, quantiles, None)
+
+
+def _quantile_from_order_statistics(fetch, first, n, q, quantiles, transform):
     scalar = np.ndim(q) == 0
-    quantiles = np.true_divide(q, np.float32(100))          # Python float -> float32, float64 array stays
     virtual = np.asanyarray((n - 1) * quantiles)
     prev_f = np.floor(virtual)
     prev = np.atleast_1d(prev_f).astype(np.intp)

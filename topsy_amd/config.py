@@ -3,6 +3,7 @@ time-budgeted progressive rendering and the colormap LUT behave identically."""
 
 DEFAULT_RESOLUTION = 1024            # config.py:1
 DEFAULT_COLORMAP = "twilight_shifted"  # config.py:2
+MAX_SURFACE_SMOOTH_PIXELS = 100        # config.py:44: largest bilateral filter window of the surface map
 DEFAULT_SCALE = 200.0                # config.py:4  half-width of the view, kpc
 TARGET_FPS = 30                      # config.py:6
 INITIAL_PARTICLES_TO_RENDER = 1e5    # config.py:7

@@ -154,6 +154,7 @@ static void free_particles(tsp_context *ctx) {
     p.perm = nullptr;
     p.n = 0;
     ctx->ws.bounds_valid = false;
+    ctx->surface_keys = false;         // the keys name particles that are gone: a surface block must start with clear = 1
     ctx->strata_offsets.clear();
     ctx->cell_offsets.clear();
     ctx->cell_bits = 0;
@@ -166,7 +167,7 @@ using namespace tsp;
 extern "C" {
 
 const char *tsp_last_error(void) { return g_err; }
-int tsp_version(void) { return 106; }     // 106: tsp_smoothing_lengths; 101: tsp_stats gained ms_mega, n_mega (16 bytes); 102: the per-kernel fragment counts (32 bytes); 103: n_chunk_culled (8 bytes); 104: matrix-core / kernel-I options removed; 105: kernel M's options removed (kernel G draws the mid footprints)
+int tsp_version(void) { return 107; }     // 107: surface rendering; 106: tsp_smoothing_lengths; 101: tsp_stats gained ms_mega, n_mega (16 bytes); 102: the per-kernel fragment counts (32 bytes); 103: n_chunk_culled (8 bytes); 104: matrix-core / kernel-I options removed; 105: kernel M's options removed (kernel G draws the mid footprints)
 int tsp_stats_size(void) { return (int)sizeof(tsp_stats); }
 
 int tsp_device_count(void) {
@@ -190,7 +191,7 @@ static int create_resources(tsp_context *ctx, int device_id, int resolution, int
     TSP_HIP(hipMemsetAsync(ctx->image, 0, npx * n_channels * sizeof(float), ctx->stream));
     TSP_HIP(hipMalloc((void **)&ctx->image64, npx * n_channels * sizeof(double)));
     TSP_HIP(hipMemsetAsync(ctx->image64, 0, npx * n_channels * sizeof(double), ctx->stream));
-    TSP_HIP(hipMalloc((void **)&ctx->mips, MIP_TOTAL * sizeof(float)));
+    TSP_HIP(hipMalloc((void **)&ctx->mips, 2 * MIP_TOTAL * sizeof(float)));   // SPH kernel mips, then the sphere mips
     TSP_HIP(hipMalloc((void **)&ctx->counters, sizeof(Counters)));
     TSP_HIP(hipMemsetAsync(ctx->counters, 0, sizeof(Counters), ctx->stream));
     TSP_HIP(hipMalloc((void **)&ctx->out8, npx * 4));
@@ -407,6 +408,7 @@ int tsp_reorder_spatial(tsp_context *ctx, int n_strata, uint64_t seed, int64_t *
     TSP_REQUIRE(n_strata >= 1 && n_strata <= 4096, TSP_EINVAL, "n_strata %d out of range", n_strata);
     TSP_REQUIRE(ctx->p.n > 0, TSP_ESTATE, "no particles resident");
     TSP_HIP(hipSetDevice(ctx->device));
+    ctx->surface_keys = false;         // (the keys hold indices of the old order)
     return reorder_spatial(ctx, n_strata, seed, perm_out);
 }
 
@@ -438,6 +440,7 @@ static int render_block(tsp_context *ctx, const float *M, float scale_factor, co
 int tsp_render(tsp_context *ctx, const float *M, float scale_factor, const int64_t *starts, const int64_t *lens,
                int n_ranges, int clear, int mode, int flags, double *gpu_ms_out) {
     TSP_REQUIRE(ctx && M, TSP_EINVAL, "NULL argument");
+    TSP_REQUIRE(clear || !ctx->surface_keys, TSP_ESTATE, "the accumulator holds the keys of tsp_render_surface: start with clear = 1");
     TSP_HIP(hipSetDevice(ctx->device));
     const size_t bytes = (size_t)ctx->R * ctx->R * ctx->Ccap * sizeof(double);
     if (!ctx->image64_entry) {
@@ -459,6 +462,8 @@ int tsp_render(tsp_context *ctx, const float *M, float scale_factor, const int64
         const hipError_t e = e0 != hipSuccess ? e0 : (e1 != hipSuccess ? e1 : e2);
         if (e != hipSuccess) set_error("%s; and the accumulator could not be restored (%s)", why.c_str(), hipGetErrorString(e));
         else set_error("%s", why.c_str());
+    } else {
+        ctx->surface_keys = false;
     }
     return rc;
 }
@@ -589,6 +594,7 @@ int tsp_write_image(tsp_context *ctx, const float *in) {
     int rc = launch_image_convert(ctx, false);                 // keep the master copy consistent
     if (rc) return rc;
     ctx->image_is_reduced = false;
+    ctx->surface_keys = false;
     TSP_HIP(hipStreamSynchronize(ctx->stream));
     return TSP_OK;
 }
@@ -753,6 +759,7 @@ int tsp_smoothing_lengths(tsp_context *ctx, int64_t n, const float *x, const flo
 
 int tsp_tile_periodic(tsp_context *ctx, int n, const float *offsets_xy, const float *weights) {
     TSP_REQUIRE(ctx && n >= 0 && n <= 4096 && (n == 0 || (offsets_xy && weights)), TSP_EINVAL, "bad argument");
+    TSP_REQUIRE(!ctx->surface_keys, TSP_ESTATE, "the accumulator holds surface keys: periodic tiling needs a density render");
     TSP_HIP(hipSetDevice(ctx->device));
     return tile_periodic(ctx, n, offsets_xy, weights);
 }
@@ -778,6 +785,85 @@ int tsp_content_values(tsp_context *ctx, const int64_t *ranks, int n_ranks, floa
         memcpy(&out[i], &bits, 4);
     }
     return TSP_OK;
+}
+
+int tsp_set_sphere_mips(tsp_context *ctx, const float *lut, int n0, int n_levels) {
+    TSP_REQUIRE(ctx && lut, TSP_EINVAL, "NULL argument");
+    TSP_REQUIRE(n0 == 64 && n_levels == 4, TSP_EINVAL, "sphere texture must be 64^2 with 4 mip levels, got n0=%d levels=%d", n0,
+                n_levels);
+    TSP_HIP(hipSetDevice(ctx->device));
+    TSP_HIP(hipMemcpy(ctx->mips + MIP_TOTAL, lut, MIP_TOTAL * sizeof(float), hipMemcpyHostToDevice));
+    ctx->have_sphere_mips = true;
+    return TSP_OK;
+}
+
+int tsp_density_order_stats(tsp_context *ctx, const int64_t *ranks, int n_ranks, float *values_out) {
+    TSP_REQUIRE(ctx && n_ranks >= 0 && (n_ranks == 0 || (ranks && values_out)), TSP_EINVAL, "bad argument");
+    TSP_REQUIRE(ctx->p.n > 0 && ctx->p.m, TSP_EINVAL, "the density cut needs resident particles with mass");
+    for (int i = 0; i < n_ranks; ++i)
+        TSP_REQUIRE(ranks[i] >= 0 && ranks[i] < ctx->p.n, TSP_EINVAL, "rank %lld outside [0, %lld)", (long long)ranks[i],
+                    (long long)ctx->p.n);
+    TSP_HIP(hipSetDevice(ctx->device));
+    return density_order_stats(ctx, ranks, n_ranks, values_out);
+}
+
+int tsp_render_surface(tsp_context *ctx, const float *M, float scale_factor, float density_cut, const int64_t *starts,
+                       const int64_t *lens, int n_ranges, int clear, double *gpu_ms_out) {
+    TSP_REQUIRE(ctx && M, TSP_EINVAL, "NULL argument");
+    TSP_REQUIRE(ctx->p.n == 0 || ctx->p.m, TSP_EINVAL, "the surface pass needs the mass array (density cut)");
+    TSP_REQUIRE(ctx->p.n < ((int64_t)1 << 32), TSP_EINVAL, "the surface keys hold indices below 2^32");
+    TSP_REQUIRE(n_ranges >= 0 && (n_ranges == 0 || (starts && lens) || (!starts && !lens)), TSP_EINVAL, "bad ranges");
+    TSP_REQUIRE(ctx->have_sphere_mips, TSP_ESTATE, "tsp_set_sphere_mips must be called before tsp_render_surface");
+    TSP_REQUIRE(clear || ctx->surface_keys, TSP_ESTATE, "clear = 0 continues a surface image; the accumulator holds none");
+    TSP_HIP(hipSetDevice(ctx->device));
+    // clip the ranges to [0, n) as tsp_render does
+    std::vector<int64_t> s, l;
+    if (!starts) {
+        if (ctx->p.n > 0) { s.push_back(0); l.push_back(ctx->p.n); }
+    } else {
+        for (int i = 0; i < n_ranges; ++i) {
+            TSP_REQUIRE(lens[i] >= 0, TSP_EINVAL, "range %d has negative length %lld", i, (long long)lens[i]);
+            int64_t b = starts[i], len = lens[i];
+            if (b < 0) {
+                len = (len > -b) ? len + b : 0;
+                b = 0;
+            }
+            if (b >= ctx->p.n || len == 0) continue;
+            if (len > ctx->p.n - b) len = ctx->p.n - b;
+            s.push_back(b);
+            l.push_back(len);
+        }
+    }
+    int64_t total = 0;
+    for (int64_t v : l) total += v;
+    Camera cam;
+    for (int i = 0; i < 12; ++i) cam.m[i] = M[i];
+    cam.sf = scale_factor;
+    cam.R = ctx->R;
+    cam.Rf = (float)ctx->R;
+    cam.halfR = 0.5f * cam.Rf;
+    double ms_draw = 0.0, ms_resolve = 0.0;
+    const int rc = render_surface(ctx, cam, density_cut, s.data(), l.data(), (int)s.size(), total, clear, &ms_draw, &ms_resolve);
+    if (rc) return rc;
+    ctx->C = 2;
+    ctx->surface_keys = true;
+    ctx->image_is_reduced = false;
+    ctx->stats.ms_stream = ms_draw;
+    ctx->stats.ms_mid = ms_resolve;
+    ctx->stats.ms_total = ms_draw + ms_resolve;
+    if (gpu_ms_out) *gpu_ms_out = ms_draw + ms_resolve;
+    return TSP_OK;
+}
+
+int tsp_surface_present(tsp_context *ctx, const tsp_surface_params *params, float *content_out, uint8_t *rgba8_out,
+                        double *ms_out) {
+    TSP_REQUIRE(ctx && params, TSP_EINVAL, "NULL argument");
+    TSP_REQUIRE(ctx->C == 2, TSP_EINVAL, "surface presentation needs a 2-channel (q, depth) image, the active one has %d", ctx->C);
+    TSP_REQUIRE(std::isfinite(params->smoothing_scale), TSP_EINVAL, "smoothing_scale must be finite");
+    TSP_REQUIRE(!rgba8_out || !params->weighted_average || (params->lut_rgba && params->n_lut >= 2 && params->n_lut <= 65536),
+                TSP_EINVAL, "weighted_average needs a colormap LUT of 2 to 65536 entries");
+    TSP_HIP(hipSetDevice(ctx->device));
+    return surface_present(ctx, *params, content_out, rgba8_out, ms_out);
 }
 
 int tsp_get_stats(tsp_context *ctx, tsp_stats *out) {

@@ -105,8 +105,10 @@ struct tsp_context {
     float *image = nullptr;           // R*R*C float32 render target (what read-back, colormap and reduce see)
     double *image64 = nullptr;        // float64 master copy every kernel accumulates into (rounded once per render)
     double *image64_entry = nullptr;  // image64 as tsp_render found it: what a failed block puts back (the call draws all of a block or none of it)
-    float *mips = nullptr;            // 5440 floats
+    float *mips = nullptr;            // 2 x 5440 floats: the SPH kernel mips, then the sphere mips of the surface pass
     bool have_mips = false;
+    bool have_sphere_mips = false;    // tsp_set_sphere_mips was called
+    bool surface_keys = false;        // image64 holds the 64-bit occlusion keys of tsp_render_surface, not float64 sums
     bool lut_mirror_symmetric = false;    // every mip level equals its left-right and top-bottom mirror images bit for bit
     bool lut_zero_outside_disc = false;   // every level-0 texel whose centre is >= 2h from the centre is exactly 0
     tsp::Particles p;
@@ -229,4 +231,10 @@ int content_sort(tsp_context *ctx, int kind, float scale, int64_t *n_finite, int
 int ensure_array(float **p, int64_t n);
 int smoothing_lengths(tsp_context *ctx, int64_t n, const float *x, const float *y, const float *z, int k, float period,
                       float *h_out);   // tsp_smooth.hip: per-call DeviceScratch only, no context state
+// tsp_surface.hip: the occlusion pass + resolve (keys in image64, (q, depth) in image), the rho order statistics and the
+// filter + shading; per-call memory is DeviceScratch
+int render_surface(tsp_context *ctx, const Camera &cam, float cut, const int64_t *h_starts, const int64_t *h_lens,
+                   int n_ranges, int64_t total, int clear, double *ms_draw, double *ms_resolve);
+int density_order_stats(tsp_context *ctx, const int64_t *ranks, int n_ranks, float *values_out);
+int surface_present(tsp_context *ctx, const tsp_surface_params &prm, float *content_out, uint8_t *rgba8_out, double *ms_out);
 }  // namespace tsp

@@ -62,3 +62,22 @@ def kernel_mips(n0=64, n_levels=4):
         _cache[key] = np.concatenate(
             [kernel_image(n0 // 2 ** i).astype(np.float32).ravel() for i in range(n_levels)])
     return _cache[key]
+
+
+def sphere_image(n_samples):
+    """n x n texel-centre samples of the sphere profile sqrt(4 - d^2) over [-2, 2]^2, -0.01 from d >= 2 on, normalisation 1:
+    LocalSphereKernel of the surface pass (reference sph.py:448-456, 497-501), evaluated in float64 as there."""
+    centres = np.linspace(-2 + 2.0 / n_samples, 2 - 2.0 / n_samples, n_samples)
+    gx, gy = np.meshgrid(centres, centres)
+    d = np.sqrt(gx ** 2 + gy ** 2)
+    with np.errstate(invalid="ignore"):
+        return np.where(d < 2.0, np.sqrt(4.0 - d ** 2), -0.01)
+
+
+def sphere_mips(n0=64, n_levels=4):
+    """The sphere texture's mip levels, concatenated float32 (uploaded next to kernel_mips() by tsp_set_sphere_mips)."""
+    key = ("sphere", n0, n_levels)
+    if key not in _cache:
+        _cache[key] = np.concatenate(
+            [sphere_image(n0 // 2 ** i).astype(np.float32).ravel() for i in range(n_levels)])
+    return _cache[key]

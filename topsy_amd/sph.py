@@ -13,7 +13,7 @@ import logging
 
 import numpy as np
 
-from . import _native, config
+from . import _native, config, kernel_lut
 from .drawreason import DrawReason
 from .util import GpuFrameTimer
 
@@ -195,3 +195,78 @@ class DepthSPH(SPH):
 
     def _prepare_buffers(self):
         pass
+
+
+def density_quantiles(context, num_samples=101):
+    """np.quantile(m / h^3, linspace(0, 1, num_samples)) over the resident particles (reference sph.py:486), from ONE device sort:
+    the ranks the interpolation reads (and the largest, for numpy's NaN rule) are fetched together."""
+    from .colormap.implementation import quantile_from_order_statistics
+    n = context.num_particles
+    q = np.linspace(0, 1, num_samples)
+    if n == 0:
+        return np.full(len(q), np.nan)
+    prev = np.floor((n - 1) * q).astype(np.intp)           # the ranks of the 'linear' method, as the helper forms them
+    ranks = np.unique(np.concatenate([prev, np.minimum(prev + 1, n - 1), [n - 1]]))
+    vals = dict(zip(ranks.tolist(), context.density_order_stats(ranks)))
+
+    def fetch(r):
+        return np.array([vals[int(k)] for k in np.asarray(r)], dtype=np.float32)
+    with np.errstate(invalid="ignore", over="ignore"):
+        return np.asarray(quantile_from_order_statistics(fetch, n, q))
+
+
+class DepthSPHWithOcclusion(SPH):
+    """Front-most sphere of every particle above a density cut: (q, depth) per pixel, the input of the surface map (reference
+    sph.py:458-656, vertex_depth_with_cut + fragment_raw with a greater-than depth test).  Draws every resident particle in one
+    tsp_render_surface call; the density cut is the percentile of rho = m / h^3 over them, from device order statistics."""
+    _rho_percentiles_num_samples = 101      # the cut is sampled at every percentile from 0 to 100
+
+    def __init__(self, visualizer, render_resolution, wrapping=False, share_render_progression=None):
+        context = visualizer.particle_buffers.context
+        if getattr(context, "n_gpus", 1) != 1:
+            raise NotImplementedError("surface rendering runs on one GPU: a multi-GPU visualizer has no occlusion pass")
+        if wrapping:
+            raise NotImplementedError("surface rendering has no periodic tiling")
+        super().__init__(visualizer, render_resolution, wrapping, share_render_progression)
+        self._context.set_sphere_mips(kernel_lut.sphere_mips())
+        self._percentile_to_den_cut = self._density_quantiles()
+        self._cut_val = float(np.mean(self.get_density_cut_percentile_range()))    # start at the median density
+
+    def _density_quantiles(self):
+        return density_quantiles(self._context, self._rho_percentiles_num_samples)
+
+    def get_density_cut_percentile(self):
+        return self._cut_val
+
+    def set_density_cut_percentile(self, value):
+        self._cut_val = value
+        self.invalidate()
+
+    def get_density_cut_percentile_range(self):
+        return 0.0, 100.0
+
+    def density_cut(self):
+        """The rho threshold of the current percentile (reference sph.py:508-511), as the float32 the pass compares against."""
+        return np.float32(self._percentile_to_den_cut[int(self._cut_val / 100.0 * (self._rho_percentiles_num_samples - 1))])
+
+    def render(self, draw_reason=DrawReason.CHANGE):
+        if draw_reason == DrawReason.PRESENTATION_CHANGE and self._target_is_mine():
+            return False
+        self._prepare_buffers()
+        M, sf = self._get_transform_params()
+        with self._render_timer.block() as timed:
+            timed.gpu_ms = self._context.render_surface(M, sf, self.density_cut())
+        self._render_timer.end_frame()
+        mean = self._render_timer.running_mean_duration
+        self.last_render_fps = 1.0 / mean if mean > 0 else float("inf")
+        self.last_render_mass_scale = 1.0
+        self.last_render_blocks = 1
+        self.has_rendered = True
+        self._visualizer.particle_buffers.last_renderer = self
+        return True
+
+    def needs_refine(self):
+        return False
+
+    def get_image(self):
+        return self._get_image_unscaled()     # maxima, not sums: no mass scaling (reference sph.py:655-656)

@@ -18,7 +18,7 @@ logger = logging.getLogger(__name__)
 
 _VALID_MODES = {"univariate", "bivariate", "rgb", "rgb-hdr", "surface"}
 _UNSUPPORTED_MODES = {
-    "surface": "needs the depth-tested occlusion pass and bilateral filter (out of scope, SURVEY.md section 2)",
+    "surface": "it is not a mode of the visualizer yet: use topsy_amd.SurfaceView(vis) for the surface rendering",
 }
 
 
