@@ -79,7 +79,8 @@ const char *tsp_last_error(void);
  * persistent workgroups of kernel S per CU (0 = as many as stay resident).  No entry point or struct changed.
  * 106: new entry point tsp_smoothing_lengths (k-nearest-neighbour smoothing lengths); nothing else changed.
  * 107: surface rendering: tsp_set_sphere_mips, tsp_density_order_stats, tsp_render_surface, tsp_surface_present and the
- * struct tsp_surface_params; nothing else changed. */
+ * struct tsp_surface_params; nothing else changed.
+ * 108: frame composition: tsp_present and the structs tsp_present_base / tsp_present_layer; nothing else changed. */
 int tsp_version(void);
 int tsp_stats_size(void);
 
@@ -278,6 +279,90 @@ int tsp_render_surface(tsp_context *ctx, const float *M, float scale_factor, flo
                        const int64_t *lens, int n_ranges, int clear, double *gpu_ms_out);
 int tsp_surface_present(tsp_context *ctx, const tsp_surface_params *params, float *content_out, uint8_t *rgba8_out,
                         double *ms_out);
+
+/* Frame composition: the W x H frame a user looks at, saves or records -- VisualizerBase.get_presentation_image / _encode_draw
+ * (reference src/topsy/visualizer.py:367-384,480-491): the presentation image colormapped onto a canvas of any size, then an
+ * ordered list of layers blended on top (colorbar, scale bar and its label, crosshairs, simulation cube, status line).  One call,
+ * one kernel: every pixel computes its base colour and applies the layers in order.  Float32 throughout, the operations in
+ * the order written, no fused multiply-adds; the rules below are restated in numpy by the tests (tests/present_ref.py).
+ *
+ * Canvas.  W, H in [1, 16384]; pixel (i, j), column i, row j from the top, has its centre at xc = i + 0.5f, yc = j + 0.5f.
+ *
+ * Base layer (colormap.wgsl:42-73 and the sampler of colormap/implementation.py:240-325).  The R x R float32 presentation image
+ * of the context (what tsp_colormap_* read: periodic tiling and the mass-scale folding included) covers the square of side
+ * S = max(W, H) centred on the canvas -- the aspect squash of colormap.wgsl:50-58; texture row 0 is the top (:60-65).  With
+ *     k = (float)R / (float)S,  ox = 0.5f * (float)(W - S),  oy = 0.5f * (float)(H - S),
+ *     ax = (xc - ox) * k,  ay = (yc - oy) * k,
+ * the sample of every raw channel is
+ *   - k <= 1 (magnification: mag_filter linear): tx = ax - 0.5f, x0 = floorf(tx), fx = tx - x0, i0 = clamp((int)x0, 0, R-1),
+ *     i1 = clamp((int)x0 + 1, 0, R-1) (ty, y0, fy, j0, j1 alike);  lerp(a, b, f) = f == 0 ? a : a * (1 - f) + b * f;
+ *     value = lerp(lerp(T[j0][i0], T[j0][i1], fx), lerp(T[j1][i0], T[j1][i1], fx), fy)
+ *   - k > 1 (minification: min_filter nearest, no mips): T[clamp((int)floorf(ay), 0, R-1)][clamp((int)floorf(ax), 0, R-1)]
+ * (clamp-to-edge).  At W = H = R, k = 1 and tx = i exactly, so the frame is tsp_colormap_*'s image bit for bit.  The raw channels
+ * are sampled first and mapped afterwards (weighted maps divide the sampled g by the sampled r) by the maps of tsp_colormap_scalar,
+ * tsp_colormap_bivariate (LUT of tsp_colormap_set_lut2d) and tsp_colormap_rgb (4-channel image).  TSP_PRESENT_RGB_HDR is the rgb
+ * map on an rgba16float canvas: the unclamped float colour, alpha 1.
+ *
+ * Layers, in order; every instance of a textured quad and every segment of a line set is one primitive, drawn in turn.
+ *   Textured quad (overlay.wgsl, overlay.py): texture_rgba = th rows (row 0 at the top) of tw RGBA float32 texels; clip_origin
+ *   (x0, y0), clip_extent (w, h) > 0, tex_origin (u0, v0), tex_extent (du, dv); n_instances clip offsets (dx, dy) and weights.
+ *   Instance k covers, in pixels,
+ *       X0 = ((x0 + dx) + 1) * (0.5f * W),      X1 = (((x0 + dx) + w) + 1) * (0.5f * W),
+ *       Y0 = (1 - ((y0 + dy) + h)) * (0.5f * H),  Y1 = (1 - (y0 + dy)) * (0.5f * H),
+ *   a pixel iff X0 <= xc < X1 and Y0 <= yc < Y1; its colour is the texture sampled with a linear filter (mag and min), clamp-to-
+ *   edge, at u = u0 + ((xc - X0) / (X1 - X0)) * du, v = v0 + ((yc - Y0) / (Y1 - Y0)) * dv: the base layer's linear rule with
+ *   tx = u * tw - 0.5f, ty = v * th - 0.5f, times the weight (all four channels).
+ *   Line set (line.wgsl, line.py:12-35): segments from starts[s] to ends[s] (xyzw each), row-major transform M (clip = M * p;
+ *   px = ((M[0] * x + M[1] * y) + M[2] * z) + M[3] * w, py alike with M[4..7]), colour, width_px.  In float32:
+ *       a = (px_s * W, py_s * H), b = (px_e * W, py_e * H), (dx, dy) = b - a, len = sqrtf(dx * dx + dy * dy),
+ *       n = (-(dy / len), dx / len), o = ((n.x * width_px) * 0.5f, (n.y * width_px) * 0.5f),
+ *       corners a - o, a + o, b + o, b - o, each divided by (W, H) (back to clip) and taken to pixels:
+ *       X = (cx + 1) * (0.5f * W), Y = (1 - cy) * (0.5f * H).
+ *   Coverage: twice the signed area A = sum over the edges P -> Q of (P.x * Q.y - Q.x * P.y), in corner order from 0; when A < 0
+ *   the order is reversed, when A is 0 or not a number the segment covers nothing.  Per edge ex = Q.x - P.x, ey = Q.y - P.y,
+ *   E = ex * (yc - P.y) - ey * (xc - P.x); a pixel is covered iff every edge has E > 0, or E == 0 on an edge with ey < 0 or
+ *   (ey == 0 and ex > 0).  (This is the top-left rule: the left and top edges are closed, right and bottom open, as for the quads.)
+ * Blending (overlay.py _blending, colour and alpha): out = src * src.a + dst * (1 - src.a), per channel, alpha included.  On the
+ * rgba8unorm canvas dst is byte / 255.0f and every primitive's result is stored as floor(255 * clamp(c, 0, 1) + 0.5) (NaN -> 0)
+ * before the next one; on the rgba16float canvas it is rounded to float16 (to nearest even, no clamp) after the base layer and
+ * after every primitive.
+ *
+ * Limits (TSP_EINVAL otherwise, nothing written): 0 <= n_layers <= 1024, at most 65536 primitives in all; a quad has a texture of
+ * 1..16384 texels per side, 1..128 instances, finite geometry with w, h > 0, |u0| + |du| and |v0| + |dv| <= 1024 and finite
+ * offsets / weights; a line set 1..65536 segments, finite width >= 0.  The base layer needs a LUT of 2..65536 entries (scalar),
+ * tsp_colormap_set_lut2d (bivariate, TSP_ESTATE) or a 4-channel image (rgb).  out: H x W x 4 uint8, or H x W x 4 float16
+ * (binary16 bits, uint16) for TSP_PRESENT_RGB_HDR.  Device memory for textures, primitive table and output staging is allocated
+ * for the call only (TSP_ENOMEM on failure).  A failed call leaves the accumulator, the presentation image and `out` untouched.
+ * gpu_ms_out (or NULL): GPU time of the composition kernel (hipEvents). */
+enum { TSP_PRESENT_SCALAR = 0, TSP_PRESENT_BIVARIATE = 1, TSP_PRESENT_RGB = 2, TSP_PRESENT_RGB_HDR = 3 };
+enum { TSP_LAYER_QUAD = 0, TSP_LAYER_LINES = 1 };
+typedef struct tsp_present_base {
+    int map;                         /* TSP_PRESENT_* */
+    float vmin, vmax;                /* the already-scaled shader parameters, as tsp_colormap_* take them */
+    float density_vmin, density_vmax;    /* bivariate */
+    float gamma;                     /* rgb */
+    int log_scale, weighted;         /* scalar, bivariate */
+    const float *lut_rgba;           /* scalar: n_lut RGBA float32 entries */
+    int n_lut;
+} tsp_present_base;
+typedef struct tsp_present_layer {
+    int kind;                        /* TSP_LAYER_* */
+    /* TSP_LAYER_QUAD */
+    const float *texture_rgba;       /* tex_height x tex_width x 4 */
+    int tex_width, tex_height;
+    float clip_origin[2], clip_extent[2], tex_origin[2], tex_extent[2];
+    int n_instances;
+    const float *instance_offsets;   /* n_instances x 2 */
+    const float *instance_weights;   /* n_instances */
+    /* TSP_LAYER_LINES */
+    int n_segments;
+    const float *starts, *ends;      /* n_segments x 4 (xyzw) */
+    float transform[16];             /* row-major */
+    float color[4];
+    float width_px;
+} tsp_present_layer;
+int tsp_present(tsp_context *ctx, int width, int height, const tsp_present_base *base, const tsp_present_layer *layers,
+                int n_layers, void *out, double *gpu_ms_out);
 
 /* On-device autorange support (replaces the image read-back + host
  * np.percentile of Colormap.autorange_vmin_vmax / _autorange_using_values, reference

@@ -16,7 +16,9 @@ MODE_WEIGHTED, MODE_DEPTH, MODE_RGB = 0, 1, 2
 PIPE_DEFAULT, PIPE_GENERIC = 0, 1
 SAMPLE_BILINEAR_MIP0, SAMPLE_BILINEAR_MIP = 0x10, 0x20      # diagnostic sampling rules (generic kernel)
 UNIQUE_ID_BYTES = 128
-ABI_VERSION = 107            # include/topsy_splat.h: tsp_version()
+ABI_VERSION = 108            # include/topsy_splat.h: tsp_version()
+PRESENT_SCALAR, PRESENT_BIVARIATE, PRESENT_RGB, PRESENT_RGB_HDR = 0, 1, 2, 3
+LAYER_QUAD, LAYER_LINES = 0, 1
 
 
 class SurfaceParams(ctypes.Structure):
@@ -25,6 +27,23 @@ class SurfaceParams(ctypes.Structure):
                 ("light_direction", ctypes.c_float * 3), ("light_color", ctypes.c_float * 3), ("ambient_color", ctypes.c_float * 3),
                 ("vmin", ctypes.c_float), ("vmax", ctypes.c_float), ("weighted_average", ctypes.c_int), ("log_scale", ctypes.c_int),
                 ("lut_rgba", ctypes.POINTER(ctypes.c_float)), ("n_lut", ctypes.c_int)]
+
+
+class PresentBase(ctypes.Structure):
+    """struct tsp_present_base (include/topsy_splat.h "Frame composition")."""
+    _fields_ = [("map", ctypes.c_int), ("vmin", ctypes.c_float), ("vmax", ctypes.c_float), ("density_vmin", ctypes.c_float),
+                ("density_vmax", ctypes.c_float), ("gamma", ctypes.c_float), ("log_scale", ctypes.c_int), ("weighted", ctypes.c_int),
+                ("lut_rgba", ctypes.POINTER(ctypes.c_float)), ("n_lut", ctypes.c_int)]
+
+
+class PresentLayer(ctypes.Structure):
+    """struct tsp_present_layer."""
+    _fields_ = [("kind", ctypes.c_int), ("texture_rgba", ctypes.POINTER(ctypes.c_float)), ("tex_width", ctypes.c_int),
+                ("tex_height", ctypes.c_int), ("clip_origin", ctypes.c_float * 2), ("clip_extent", ctypes.c_float * 2),
+                ("tex_origin", ctypes.c_float * 2), ("tex_extent", ctypes.c_float * 2), ("n_instances", ctypes.c_int),
+                ("instance_offsets", ctypes.POINTER(ctypes.c_float)), ("instance_weights", ctypes.POINTER(ctypes.c_float)),
+                ("n_segments", ctypes.c_int), ("starts", ctypes.POINTER(ctypes.c_float)), ("ends", ctypes.POINTER(ctypes.c_float)),
+                ("transform", ctypes.c_float * 16), ("color", ctypes.c_float * 4), ("width_px", ctypes.c_float)]
 
 
 class BackendUnavailable(RuntimeError):
@@ -96,6 +115,8 @@ SIGNATURES = {
     "tsp_render_surface": (ctypes.c_int, [_ctx, _fp, ctypes.c_float, ctypes.c_float, _i64p, _i64p, ctypes.c_int, ctypes.c_int,
                                           ctypes.POINTER(ctypes.c_double)]),
     "tsp_surface_present": (ctypes.c_int, [_ctx, ctypes.c_void_p, _fp, _u8p, ctypes.POINTER(ctypes.c_double)]),
+    "tsp_present": (ctypes.c_int, [_ctx, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
+                                   ctypes.POINTER(ctypes.c_double)]),
     "tsp_content_sort": (ctypes.c_int, [_ctx, ctypes.c_int, ctypes.c_float, _i64p, _i64p]),
     "tsp_content_values": (ctypes.c_int, [_ctx, _i64p, ctypes.c_int, _fp]),
     "tsp_get_stats": (ctypes.c_int, [_ctx, ctypes.POINTER(Stats)]),
@@ -500,6 +521,66 @@ class Context:
             out = np.empty((H, W, 4), dtype=np.uint8)
             _check(self._lib.tsp_colormap_rgb_host(self._h, _ptr(img), H, W, C, float(vmin), float(vmax), float(gamma),
                                                    out.ctypes.data_as(_u8p), None))
+        return out
+
+    # ---- frame composition ----------------------------------------------------------------
+    def present(self, width, height, base, layers=(), timings=None):
+        """Compose a (height, width, 4) frame (tsp_present): the presentation image colormapped onto the canvas, then `layers`
+        in order.  base: dict with "map" ("scalar" | "bivariate" | "rgb" | "rgb-hdr"), "vmin", "vmax" and as the map needs
+        "lut" (scalar, (n, 4) float32), "log", "weighted", "density_vmin", "density_vmax" (bivariate, after colormap_set_lut2d),
+        "gamma" (rgb).  A layer is a dict with "kind" "quad" (texture (th, tw, 4) float32, clip (x0, y0, w, h), tex (u0, v0, du,
+        dv), offsets (n, 2), weights (n,)) or "lines" (starts / ends (n, 4), transform (4, 4) row-major, color (4,), width).
+        Returns uint8, or float16 for "rgb-hdr".  `timings`, a list, receives the composition kernel's GPU ms."""
+        maps = {"scalar": PRESENT_SCALAR, "bivariate": PRESENT_BIVARIATE, "rgb": PRESENT_RGB, "rgb-hdr": PRESENT_RGB_HDR}
+        b = PresentBase()
+        b.map = maps[base["map"]]
+        b.vmin, b.vmax = float(np.float32(base["vmin"])), float(np.float32(base["vmax"]))
+        b.density_vmin = float(np.float32(base.get("density_vmin", 0.0)))
+        b.density_vmax = float(np.float32(base.get("density_vmax", 1.0)))
+        b.gamma = float(np.float32(base.get("gamma", 1.0)))
+        b.log_scale, b.weighted = int(bool(base.get("log", False))), int(bool(base.get("weighted", False)))
+        keep = []             # the arrays the structs point into stay alive for the call
+        if b.map == PRESENT_SCALAR:
+            lut = _f32(base["lut"], name="lut")
+            keep.append(lut)
+            b.lut_rgba, b.n_lut = _ptr(lut), lut.size // 4
+        arr = (PresentLayer * max(1, len(layers)))()
+        for L, d in zip(arr, layers):
+            if d["kind"] == "quad":
+                tex = _f32(d["texture"], name="texture")
+                if tex.ndim != 3 or tex.shape[2] != 4:
+                    raise ValueError(f"a quad texture must have shape (h, w, 4), not {tex.shape}")
+                off = _f32(d.get("offsets", [[0.0, 0.0]]), name="offsets").reshape(-1)
+                w = _f32(d.get("weights", [1.0]), name="weights").reshape(-1)
+                if off.size != 2 * w.size:
+                    raise ValueError("offsets must have shape (n, 2) for n weights")
+                keep += [tex, off, w]
+                L.kind = LAYER_QUAD
+                L.texture_rgba, L.tex_height, L.tex_width = _ptr(tex), tex.shape[0], tex.shape[1]
+                x0, y0, cw, ch = (float(np.float32(v)) for v in d["clip"])
+                u0, v0, du, dv = (float(np.float32(v)) for v in d.get("tex", (0.0, 0.0, 1.0, 1.0)))
+                L.clip_origin[:], L.clip_extent[:], L.tex_origin[:], L.tex_extent[:] = [x0, y0], [cw, ch], [u0, v0], [du, dv]
+                L.n_instances, L.instance_offsets, L.instance_weights = w.size, _ptr(off), _ptr(w)
+            elif d["kind"] == "lines":
+                st = _f32(d["starts"], name="starts").reshape(-1)
+                en = _f32(d["ends"], name="ends").reshape(-1)
+                if st.size != en.size or st.size % 4:
+                    raise ValueError("starts and ends must both have shape (n, 4)")
+                keep += [st, en]
+                L.kind = LAYER_LINES
+                L.n_segments, L.starts, L.ends = st.size // 4, _ptr(st), _ptr(en)
+                L.transform[:] = [float(v) for v in _f32(d.get("transform", np.eye(4)), 16, "transform").reshape(16)]
+                L.color[:] = [float(v) for v in _f32(d["color"], 4, "color")]
+                L.width_px = float(np.float32(d["width"]))
+            else:
+                raise ValueError(f"unknown layer kind {d['kind']!r}")
+        W, H = int(width), int(height)
+        hdr = b.map == PRESENT_RGB_HDR
+        out = np.empty((max(H, 0), max(W, 0), 4), dtype=np.float16 if hdr else np.uint8)
+        ms = ctypes.c_double(0.0)
+        _check(self._lib.tsp_present(self._h, W, H, ctypes.byref(b), arr, len(layers), out.ctypes.data, ctypes.byref(ms)))
+        if timings is not None:
+            timings[:] = [ms.value]
         return out
 
     # ---- multi-GPU ------------------------------------------------------------------------

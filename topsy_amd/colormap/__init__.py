@@ -73,6 +73,11 @@ class ColormapHolder:
         self._check_valid()
         self._impl.set_scaling(width, height, mass_scaling)
 
+    def present_base(self, context):
+        """The base layer of tsp_present with the current shader parameters (call set_scaling first)."""
+        self._check_valid()
+        return self._impl.present_base(context)
+
     def sph_raw_output_to_image(self, sph_raw_output):
         self._check_valid()
         return self._impl.sph_raw_output_to_image(sph_raw_output)

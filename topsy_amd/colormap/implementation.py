@@ -245,6 +245,14 @@ class Colormap(ColormapBase):
         return ctx.colormap_scalar(self._lut, p["vmin"], p["vmax"], self._params["log"],
                                    self._params.get("weighted_average", False))
 
+    def present_base(self, ctx):
+        """The base layer of a composed frame (tsp_present): this map on the resident image."""
+        p = self._shader_params
+        if self._output_dtype() != np.uint8:
+            raise ValueError(f"Unsupported output format for a LUT colormap: {self._output_format}")
+        return {"map": "scalar", "lut": self._lut, "vmin": p["vmin"], "vmax": p["vmax"], "log": self._params["log"],
+                "weighted": self._params.get("weighted_average", False)}
+
     def _run_on_host_image(self, ctx, img):
         p = self._shader_params
         if self._output_dtype() != np.uint8:
@@ -363,6 +371,11 @@ class RGBColormap(Colormap):
     def _run_on_target(self, ctx):
         return self._run(lambda a, b, g, f: ctx.colormap_rgb(a, b, g, as_float=f))
 
+    def present_base(self, ctx):
+        p = self._shader_params
+        return {"map": "rgb" if self._output_dtype() == np.uint8 else "rgb-hdr", "vmin": p["vmin"], "vmax": p["vmax"],
+                "gamma": p["gamma"]}
+
     def _run_on_host_image(self, ctx, img):
         return self._run(lambda a, b, g, f: ctx.colormap_rgb_host(img, a, b, g, as_float=f))
 
@@ -448,6 +461,14 @@ class BivariateColormap(Colormap):
         self._ensure_lut_resident(ctx)
         return ctx.colormap_bivariate(p["vmin"], p["vmax"], p["density_vmin"], p["density_vmax"], self._params["log"],
                                       self._params.get("weighted_average", False))
+
+    def present_base(self, ctx):
+        p = self._shader_params
+        if self._output_dtype() != np.uint8:
+            raise ValueError(f"Unsupported output format for a LUT colormap: {self._output_format}")
+        self._ensure_lut_resident(ctx)
+        return {"map": "bivariate", "vmin": p["vmin"], "vmax": p["vmax"], "density_vmin": p["density_vmin"],
+                "density_vmax": p["density_vmax"], "log": self._params["log"], "weighted": self._params.get("weighted_average", False)}
 
     def _run_on_host_image(self, ctx, img):
         p = self._shader_params

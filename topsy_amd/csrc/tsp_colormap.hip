@@ -25,22 +25,7 @@ __global__ __launch_bounds__(256) void colormap_scalar_kernel(const float *__res
         } else {
             r = img[p * C]; g = img[p * C + 1];
         }
-        float v = weighted ? g / r : r;
-        if (log_scale) v = canon_log10f(v);
-        float t = (v - vmin) / range;
-        t = (t != t) ? 0.0f : t;
-        t = t < 0.0f ? 0.0f : (t > 1.0f ? 1.0f : t);
-        const float c = t * (float)n_lut - 0.5f;
-        const float c0 = __builtin_floorf(c);
-        const float f = c - c0;
-        const int i0 = clampi((int)c0, 0, n_lut - 1), i1 = clampi((int)c0 + 1, 0, n_lut - 1);
-        const float gq = 1.0f - f;
-        const float4 a = lut[i0], b = lut[i1];
-        const uint32_t R8 = unorm8(a.x * gq + b.x * f);
-        const uint32_t G8 = unorm8(a.y * gq + b.y * f);
-        const uint32_t B8 = unorm8(a.z * gq + b.z * f);
-        const uint32_t A8 = unorm8(a.w * gq + b.w * f);
-        out[p] = R8 | (G8 << 8) | (B8 << 16) | (A8 << 24);
+        out[p] = map_scalar_rgba8(r, g, lut, n_lut, vmin, range, log_scale, weighted);
     }
 }
 
@@ -51,13 +36,7 @@ __global__ __launch_bounds__(256) void colormap_rgb_kernel(const float *__restri
     for (int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x; p < npix; p += (int64_t)gridDim.x * 256) {
         float c[3];
 #pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            const float v = canon_log10f(img[p * C + k]);
-            float x = (v - vmin) / range;
-            x = (x != x) ? 0.0f : x;
-            x = x < 0.0f ? 0.0f : x;
-            c[k] = canon_powf(x, gamma);
-        }
+        for (int k = 0; k < 3; ++k) c[k] = map_rgb_channel(img[p * C + k], vmin, range, gamma);
         if (out8) out8[p] = unorm8(c[0]) | (unorm8(c[1]) << 8) | (unorm8(c[2]) << 16) | (255u << 24);
         if (outf) outf[p] = make_float4(c[0], c[1], c[2], 1.0f);
     }
@@ -72,24 +51,7 @@ __global__ __launch_bounds__(256) void colormap_bivariate_kernel(const float *__
     const float range = vmax - vmin, drange = dvmax - dvmin;
     for (int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x; p < npix; p += (int64_t)gridDim.x * 256) {
         const float r = img[p * C], g = img[p * C + 1];
-        float x = (canon_log10f(r) - dvmin) / drange;
-        float y = weighted ? g / r : r;
-        if (log_scale) y = canon_log10f(y);
-        y = (y - vmin) / range;
-        x = (x != x || x < 0.0f) ? 0.0f : (x > 1.0f ? 1.0f : x);
-        y = (y != y || y < 0.0f) ? 0.0f : (y > 1.0f ? 1.0f : y);
-        const float cx = x * (float)n - 0.5f, cy = y * (float)n - 0.5f;
-        const float x0 = __builtin_floorf(cx), y0 = __builtin_floorf(cy);
-        const float fx = cx - x0, fy = cy - y0, gx = 1.0f - fx, gy = 1.0f - fy;
-        const int i0 = clampi((int)x0, 0, n - 1), i1 = clampi((int)x0 + 1, 0, n - 1);
-        const int j0 = clampi((int)y0, 0, n - 1), j1 = clampi((int)y0 + 1, 0, n - 1);
-        const float4 a = lut[(size_t)j0 * n + i0], b = lut[(size_t)j0 * n + i1];
-        const float4 c = lut[(size_t)j1 * n + i0], d = lut[(size_t)j1 * n + i1];
-        const uint32_t R8 = unorm8((a.x * gx + b.x * fx) * gy + (c.x * gx + d.x * fx) * fy);
-        const uint32_t G8 = unorm8((a.y * gx + b.y * fx) * gy + (c.y * gx + d.y * fx) * fy);
-        const uint32_t B8 = unorm8((a.z * gx + b.z * fx) * gy + (c.z * gx + d.z * fx) * fy);
-        const uint32_t A8 = unorm8((a.w * gx + b.w * fx) * gy + (c.w * gx + d.w * fx) * fy);
-        out[p] = R8 | (G8 << 8) | (B8 << 16) | (A8 << 24);
+        out[p] = map_bivariate_rgba8(r, g, lut, n, vmin, range, dvmin, drange, log_scale, weighted);
     }
 }
 

@@ -215,4 +215,59 @@ __device__ __forceinline__ uint32_t unorm8(float c) {   // rgba8unorm store: rou
     return (uint32_t)__builtin_floorf(c * 255.0f + 0.5f);
 }
 
+// ------------------------------------------------------------------------------------------
+// the per-pixel maps of the colormap post-pass (colormap.wgsl :91-159), shared by kernels B / B' (tsp_colormap.hip) and the
+// frame composition (tsp_present.hip); `range` = vmax - vmin, formed once by the caller
+// ------------------------------------------------------------------------------------------
+__device__ __forceinline__ uint32_t map_scalar_rgba8(float r, float g, const float4 *__restrict__ lut, int n_lut, float vmin,
+                                                     float range, int log_scale, int weighted) {
+    float v = weighted ? g / r : r;
+    if (log_scale) v = canon_log10f(v);
+    float t = (v - vmin) / range;
+    t = (t != t) ? 0.0f : t;
+    t = t < 0.0f ? 0.0f : (t > 1.0f ? 1.0f : t);
+    const float c = t * (float)n_lut - 0.5f;
+    const float c0 = __builtin_floorf(c);
+    const float f = c - c0;
+    const int i0 = clampi((int)c0, 0, n_lut - 1), i1 = clampi((int)c0 + 1, 0, n_lut - 1);
+    const float gq = 1.0f - f;
+    const float4 a = lut[i0], b = lut[i1];
+    const uint32_t R8 = unorm8(a.x * gq + b.x * f);
+    const uint32_t G8 = unorm8(a.y * gq + b.y * f);
+    const uint32_t B8 = unorm8(a.z * gq + b.z * f);
+    const uint32_t A8 = unorm8(a.w * gq + b.w * f);
+    return R8 | (G8 << 8) | (B8 << 16) | (A8 << 24);
+}
+
+__device__ __forceinline__ uint32_t map_bivariate_rgba8(float r, float g, const float4 *__restrict__ lut, int n, float vmin,
+                                                        float range, float dvmin, float drange, int log_scale, int weighted) {
+    float x = (canon_log10f(r) - dvmin) / drange;
+    float y = weighted ? g / r : r;
+    if (log_scale) y = canon_log10f(y);
+    y = (y - vmin) / range;
+    x = (x != x || x < 0.0f) ? 0.0f : (x > 1.0f ? 1.0f : x);
+    y = (y != y || y < 0.0f) ? 0.0f : (y > 1.0f ? 1.0f : y);
+    const float cx = x * (float)n - 0.5f, cy = y * (float)n - 0.5f;
+    const float x0 = __builtin_floorf(cx), y0 = __builtin_floorf(cy);
+    const float fx = cx - x0, fy = cy - y0, gx = 1.0f - fx, gy = 1.0f - fy;
+    const int i0 = clampi((int)x0, 0, n - 1), i1 = clampi((int)x0 + 1, 0, n - 1);
+    const int j0 = clampi((int)y0, 0, n - 1), j1 = clampi((int)y0 + 1, 0, n - 1);
+    const float4 a = lut[(size_t)j0 * n + i0], b = lut[(size_t)j0 * n + i1];
+    const float4 c = lut[(size_t)j1 * n + i0], d = lut[(size_t)j1 * n + i1];
+    const uint32_t R8 = unorm8((a.x * gx + b.x * fx) * gy + (c.x * gx + d.x * fx) * fy);
+    const uint32_t G8 = unorm8((a.y * gx + b.y * fx) * gy + (c.y * gx + d.y * fx) * fy);
+    const uint32_t B8 = unorm8((a.z * gx + b.z * fx) * gy + (c.z * gx + d.z * fx) * fy);
+    const uint32_t A8 = unorm8((a.w * gx + b.w * fx) * gy + (c.w * gx + d.w * fx) * fy);
+    return R8 | (G8 << 8) | (B8 << 16) | (A8 << 24);
+}
+
+// one channel of fragment_main_tri: gamma_map(log10(value)) (colormap.wgsl:131-159), unclamped above (the HDR canvas value)
+__device__ __forceinline__ float map_rgb_channel(float value, float vmin, float range, float gamma) {
+    const float v = canon_log10f(value);
+    float x = (v - vmin) / range;
+    x = (x != x) ? 0.0f : x;
+    x = x < 0.0f ? 0.0f : x;
+    return canon_powf(x, gamma);
+}
+
 }  // namespace tsp

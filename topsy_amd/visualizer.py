@@ -1,17 +1,18 @@
 """Headless Visualizer: the orchestrator surface of reference src/topsy/visualizer.py:31-602 for
 the accelerated path -- data loader -> resident particle buffers -> SPH renderer -> colormap.
 
-Windowing, overlays (colorbar / scalebar / status text / crosshairs), the recorder and view
-synchronisation are out of scope; what the UI layers call on the orchestrator
--- rotate / scale / position_offset / quantity_name / render_mode / invalidate / draw /
-colormap_autorange / get_sph_image / get_sph_presentation_image / get_depth_image / save -- is here
-with the reference's semantics, so those layers can sit on top unchanged.
+Windowing, the recorder and view synchronisation are out of scope; what the UI
+layers call on the orchestrator -- rotate / scale / position_offset / quantity_name / render_mode /
+invalidate / draw / colormap_autorange / get_sph_image / get_sph_presentation_image / get_depth_image /
+save -- is here with the reference's semantics, so those layers can sit on top unchanged.
+get_presentation_image composes the full frame of any size on the GPU (tsp_present): the colormapped
+image with the colorbar, scale bar, crosshairs, simulation cube and status line of topsy_amd/overlays.py.
 """
 import logging
 
 import numpy as np
 
-from . import colormap, config, loader, particle_buffers, periodic_sph, sph
+from . import colormap, config, loader, overlays, particle_buffers, periodic_sph, sph
 from .drawreason import DrawReason
 
 logger = logging.getLogger(__name__)
@@ -24,6 +25,10 @@ _UNSUPPORTED_MODES = {
 
 class VisualizerBase:
     device = None      # kept for signature compatibility; the GPU is owned by particle_buffers.context
+    show_status = True     # layers of get_presentation_image, the reference's defaults (visualizer.py:34,53-60)
+    show_colorbar = True
+    show_scalebar = True
+    crosshairs_visible = False
 
     def __init__(self, data_loader_class=loader.TestDataLoader, data_loader_args=(), data_loader_kwargs={},
                  *, render_resolution=config.DEFAULT_RESOLUTION, periodic_tiling=False,
@@ -53,6 +58,9 @@ class VisualizerBase:
         if periodic_tiling and not self.periodicity_scale:
             raise ValueError("periodic_tiling needs a data loader with a finite periodicity scale")
         self._pending_draw = None
+        self._colorbar = overlays.ColorbarOverlay()
+        self._scalebar = overlays.ScalebarOverlay(self.data_loader.get_position_units())
+        self._status = overlays.StatusLine()
         self._initialize_sph_and_colormap(colormap_name)
 
     # -- mode plumbing (reference visualizer.py:96-120, 170-186, 203-231) ----------------------
@@ -244,6 +252,48 @@ class VisualizerBase:
         res = self._render_resolution
         self._colormap.set_scaling(res, res, self._sph.last_render_mass_scale)
         return self._colormap.encode_render_pass(None, None)
+
+    def get_presentation_image(self, resolution=(640, 480)):
+        """The full frame, (H, W, 4) uint8 (float16 for rgb-hdr) for resolution = (W, H): the image colormapped onto the canvas
+        with the colorbar, scale bar, crosshairs, simulation cube and status line on top (reference visualizer.py:480-491,
+        367-384), composed on the GPU in one pass (tsp_present)."""
+        width, height = (int(v) for v in resolution)
+        if not (1 <= width <= 16384 and 1 <= height <= 16384):
+            raise ValueError(f"resolution {resolution} outside 1 .. 16384 pixels per side")
+        self.render_sph(DrawReason.EXPORT)
+        self._colormap.set_scaling(width, height, self._sph.last_render_mass_scale)
+        ctx = self._sph._context
+        base = self._colormap.present_base(ctx)
+        layers = self._presentation_layers(width, height)
+        self._last_presentation = (base, layers)      # what the frame was composed from (tests restate it)
+        return ctx.present(width, height, base, layers)
+
+    def _presentation_layers(self, width, height):
+        """The layers in the reference's order (visualizer.py:367-384): colorbar, scale bar, crosshairs, cube, status line."""
+        layers = []
+        if self.show_colorbar and self._colormap.colormap_kind() != "rgb":        # no colorbar for rgb maps (:327-335)
+            p = self._colormap.get_parameters()
+            layers.append(self._colorbar.layer(p["vmin"], p["vmax"], p["colormap_name"], self._get_colorbar_label(), width, height))
+        if self.show_scalebar:
+            layers += self._scalebar.layers(self.scale, width, height)
+        if self.crosshairs_visible:
+            layers.append(overlays.crosshairs_layer())
+        if self._periodic_tiling:
+            layers.append(overlays.simcube_layer(self.data_loader.get_periodicity_scale(), self._sph._transform[0], width, height))
+        if self.show_status:
+            self._status.update(self._sph)
+            layers.append(self._status.layer(width, height))
+        # a canvas a few pixels high gives the colorbar figure no pixels at all: such a layer has nothing to draw
+        return [L for L in layers if L["kind"] != "quad" or min(L["texture"].shape[:2]) > 0]
+
+    def _get_colorbar_label(self):
+        """The quantity's label, marked as a log10 when the map is logarithmic (reference visualizer.py:341-346)."""
+        prefix = r"$\log_{10}$ " if self._colormap.get_parameter("log") else ""
+        return prefix + self.data_loader.get_quantity_label(self.quantity_name)
+
+    def display_status(self, text, timeout=0.5):
+        """Show `text` in the status line of the next frames for `timeout` seconds (reference visualizer.py:426-428)."""
+        self._status.display(text, timeout)
 
     def get_depth_image(self):
         depth = self._sph.get_depth_image()
