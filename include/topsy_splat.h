@@ -80,7 +80,8 @@ const char *tsp_last_error(void);
  * 106: new entry point tsp_smoothing_lengths (k-nearest-neighbour smoothing lengths); nothing else changed.
  * 107: surface rendering: tsp_set_sphere_mips, tsp_density_order_stats, tsp_render_surface, tsp_surface_present and the
  * struct tsp_surface_params; nothing else changed.
- * 108: frame composition: tsp_present and the structs tsp_present_base / tsp_present_layer; nothing else changed. */
+ * 108: frame composition: tsp_present and the structs tsp_present_base / tsp_present_layer; nothing else changed.
+ * 109: movie frames: tsp_present_yuv420 (the tsp_present frame as I420 planes); nothing else changed. */
 int tsp_version(void);
 int tsp_stats_size(void);
 
@@ -363,6 +364,23 @@ typedef struct tsp_present_layer {
 } tsp_present_layer;
 int tsp_present(tsp_context *ctx, int width, int height, const tsp_present_base *base, const tsp_present_layer *layers,
                 int n_layers, void *out, double *gpu_ms_out);
+
+/* tsp_present_yuv420: the frame tsp_present composes (same base, layers, rules and limits, bit for bit), converted on the device
+ * to I420 ("yuv420p") -- what a movie encoder reads (reference recorder/__init__.py _replay draws this frame for every movie frame).
+ * out: the W x H Y plane, then the (W/2) x (H/2) U plane, then the V plane (W * H * 3 / 2 bytes), all row-major, row 0 at the top.
+ * Integer arithmetic only, `>>` an arithmetic shift (floor); alpha is ignored (the reference drops it, it does not composite).
+ * With R, G, B the bytes of a pixel,
+ *     Y = ((47 R + 157 G + 16 B + 128) >> 8) + 16                          (every pixel)
+ * and for every 2 x 2 block, with the rounded means r = (R00 + R01 + R10 + R11 + 2) >> 2 (g, b alike),
+ *     U = ((-26 r - 86 g + 112 b + 128) >> 8) + 128,   V = ((112 r - 102 g - 10 b + 128) >> 8) + 128.
+ * These are the BT.709 limited-range ("tv") coefficients rounded so that every grey has U = V = 128 and white has Y = 235; for
+ * every input Y lies in [16, 235] and U, V in [16, 240], so nothing is clamped.  Worked values (R, G, B -> Y, U, V): black -> 16,
+ * 128, 128; white -> 235, 128, 128; (128, 128, 128) -> 126, 128, 128; red -> 63, 102, 240; green -> 172, 42, 26; blue -> 32, 240, 118.
+ * TSP_EINVAL, nothing written, when W or H is odd or outside [2, 16384], when the map is TSP_PRESENT_RGB_HDR, and wherever
+ * tsp_present refuses.  A failed call leaves the accumulator, the presentation image and `out` untouched.  Per-call device memory
+ * as tsp_present, plus the planes.  gpu_ms_out (or NULL): GPU time of the composition and the conversion together. */
+int tsp_present_yuv420(tsp_context *ctx, int width, int height, const tsp_present_base *base, const tsp_present_layer *layers,
+                       int n_layers, uint8_t *out, double *gpu_ms_out);
 
 /* On-device autorange support (replaces the image read-back + host
  * np.percentile of Colormap.autorange_vmin_vmax / _autorange_using_values, reference

@@ -66,6 +66,14 @@ def SurfaceView(visualizer, **colormap_params):
     return surface.SurfaceView(visualizer, **colormap_params)
 
 
+def __getattr__(name):
+    """topsy_amd.VisualizationRecorder (movie recording and export, topsy_amd/recorder), imported on first use."""
+    if name == "VisualizationRecorder":
+        from .recorder import VisualizationRecorder
+        return VisualizationRecorder
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
+
+
 def synthetic_on_device(n_total, first=0, count=None, h_cap=0.0, **kwargs):
     """Visualizer over a device-generated shard of the synthetic snapshot (1e8-1e9 particles)."""
     from . import visualizer, loader

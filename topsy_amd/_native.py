@@ -16,7 +16,7 @@ MODE_WEIGHTED, MODE_DEPTH, MODE_RGB = 0, 1, 2
 PIPE_DEFAULT, PIPE_GENERIC = 0, 1
 SAMPLE_BILINEAR_MIP0, SAMPLE_BILINEAR_MIP = 0x10, 0x20      # diagnostic sampling rules (generic kernel)
 UNIQUE_ID_BYTES = 128
-ABI_VERSION = 108            # include/topsy_splat.h: tsp_version()
+ABI_VERSION = 109            # include/topsy_splat.h: tsp_version()
 PRESENT_SCALAR, PRESENT_BIVARIATE, PRESENT_RGB, PRESENT_RGB_HDR = 0, 1, 2, 3
 LAYER_QUAD, LAYER_LINES = 0, 1
 
@@ -117,6 +117,8 @@ SIGNATURES = {
     "tsp_surface_present": (ctypes.c_int, [_ctx, ctypes.c_void_p, _fp, _u8p, ctypes.POINTER(ctypes.c_double)]),
     "tsp_present": (ctypes.c_int, [_ctx, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
                                    ctypes.POINTER(ctypes.c_double)]),
+    "tsp_present_yuv420": (ctypes.c_int, [_ctx, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, _u8p,
+                                          ctypes.POINTER(ctypes.c_double)]),
     "tsp_content_sort": (ctypes.c_int, [_ctx, ctypes.c_int, ctypes.c_float, _i64p, _i64p]),
     "tsp_content_values": (ctypes.c_int, [_ctx, _i64p, ctypes.c_int, _fp]),
     "tsp_get_stats": (ctypes.c_int, [_ctx, ctypes.POINTER(Stats)]),
@@ -531,6 +533,35 @@ class Context:
         "gamma" (rgb).  A layer is a dict with "kind" "quad" (texture (th, tw, 4) float32, clip (x0, y0, w, h), tex (u0, v0, du,
         dv), offsets (n, 2), weights (n,)) or "lines" (starts / ends (n, 4), transform (4, 4) row-major, color (4,), width).
         Returns uint8, or float16 for "rgb-hdr".  `timings`, a list, receives the composition kernel's GPU ms."""
+        b, arr, keep = self._present_args(base, layers)
+        W, H = int(width), int(height)
+        hdr = b.map == PRESENT_RGB_HDR
+        out = np.empty((max(H, 0), max(W, 0), 4), dtype=np.float16 if hdr else np.uint8)
+        ms = ctypes.c_double(0.0)
+        _check(self._lib.tsp_present(self._h, W, H, ctypes.byref(b), arr, len(layers), out.ctypes.data, ctypes.byref(ms)))
+        if timings is not None:
+            timings[:] = [ms.value]
+        return out
+
+    def present_yuv420(self, width, height, base, layers=(), timings=None):
+        """The frame of present(width, height, base, layers) as I420 planes (tsp_present_yuv420): uint8 arrays Y (height,
+        width), U and V (height / 2, width / 2).  width and height must be even; the "rgb-hdr" map has no 8-bit frame.
+        `timings`, a list, receives the GPU ms of the composition and the conversion together."""
+        b, arr, keep = self._present_args(base, layers)
+        W, H = int(width), int(height)
+        n = max(W, 0) * max(H, 0)
+        out = np.empty(n + 2 * (max(W, 0) // 2) * (max(H, 0) // 2), dtype=np.uint8)
+        ms = ctypes.c_double(0.0)
+        _check(self._lib.tsp_present_yuv420(self._h, W, H, ctypes.byref(b), arr, len(layers), out.ctypes.data_as(_u8p),
+                                            ctypes.byref(ms)))
+        if timings is not None:
+            timings[:] = [ms.value]
+        c = (W // 2) * (H // 2)
+        return out[:n].reshape(H, W), out[n:n + c].reshape(H // 2, W // 2), out[n + c:].reshape(H // 2, W // 2)
+
+    @staticmethod
+    def _present_args(base, layers):
+        """The ctypes structs of tsp_present's base and layers, and the arrays they point into (kept alive by the caller)."""
         maps = {"scalar": PRESENT_SCALAR, "bivariate": PRESENT_BIVARIATE, "rgb": PRESENT_RGB, "rgb-hdr": PRESENT_RGB_HDR}
         b = PresentBase()
         b.map = maps[base["map"]]
@@ -574,14 +605,7 @@ class Context:
                 L.width_px = float(np.float32(d["width"]))
             else:
                 raise ValueError(f"unknown layer kind {d['kind']!r}")
-        W, H = int(width), int(height)
-        hdr = b.map == PRESENT_RGB_HDR
-        out = np.empty((max(H, 0), max(W, 0), 4), dtype=np.float16 if hdr else np.uint8)
-        ms = ctypes.c_double(0.0)
-        _check(self._lib.tsp_present(self._h, W, H, ctypes.byref(b), arr, len(layers), out.ctypes.data, ctypes.byref(ms)))
-        if timings is not None:
-            timings[:] = [ms.value]
-        return out
+        return b, arr, keep
 
     # ---- multi-GPU ------------------------------------------------------------------------
     @staticmethod

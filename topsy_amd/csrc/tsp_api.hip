@@ -167,7 +167,7 @@ using namespace tsp;
 extern "C" {
 
 const char *tsp_last_error(void) { return g_err; }
-int tsp_version(void) { return 108; }     // 108: tsp_present; 107: surface rendering; 106: tsp_smoothing_lengths; 101: tsp_stats gained ms_mega, n_mega (16 bytes); 102: the per-kernel fragment counts (32 bytes); 103: n_chunk_culled (8 bytes); 104: matrix-core / kernel-I options removed; 105: kernel M's options removed (kernel G draws the mid footprints)
+int tsp_version(void) { return 109; }     // 109: tsp_present_yuv420; 108: tsp_present; 107: surface rendering; 106: tsp_smoothing_lengths; 101: tsp_stats gained ms_mega, n_mega (16 bytes); 102: the per-kernel fragment counts (32 bytes); 103: n_chunk_culled (8 bytes); 104: matrix-core / kernel-I options removed; 105: kernel M's options removed (kernel G draws the mid footprints)
 int tsp_stats_size(void) { return (int)sizeof(tsp_stats); }
 
 int tsp_device_count(void) {
@@ -760,7 +760,13 @@ int tsp_smoothing_lengths(tsp_context *ctx, int64_t n, const float *x, const flo
 int tsp_present(tsp_context *ctx, int width, int height, const tsp_present_base *base, const tsp_present_layer *layers,
                 int n_layers, void *out, double *gpu_ms_out) {
     TSP_REQUIRE(ctx && base && out, TSP_EINVAL, "NULL argument");
-    return present(ctx, width, height, *base, layers, n_layers, out, gpu_ms_out);
+    return present(ctx, width, height, *base, layers, n_layers, out, gpu_ms_out, false);
+}
+
+int tsp_present_yuv420(tsp_context *ctx, int width, int height, const tsp_present_base *base, const tsp_present_layer *layers,
+                       int n_layers, uint8_t *out, double *gpu_ms_out) {
+    TSP_REQUIRE(ctx && base && out, TSP_EINVAL, "NULL argument");
+    return present(ctx, width, height, *base, layers, n_layers, out, gpu_ms_out, true);
 }
 
 int tsp_tile_periodic(tsp_context *ctx, int n, const float *offsets_xy, const float *weights) {

@@ -237,7 +237,8 @@ int render_surface(tsp_context *ctx, const Camera &cam, float cut, const int64_t
                    int n_ranges, int64_t total, int clear, double *ms_draw, double *ms_resolve);
 int density_order_stats(tsp_context *ctx, const int64_t *ranks, int n_ranks, float *values_out);
 int surface_present(tsp_context *ctx, const tsp_surface_params &prm, float *content_out, uint8_t *rgba8_out, double *ms_out);
-// tsp_present.hip: frame composition (base map + layers on a W x H canvas); per-call memory is DeviceScratch
+// tsp_present.hip: frame composition (base map + layers on a W x H canvas), optionally converted to I420 planes (yuv420);
+// per-call memory is DeviceScratch
 int present(tsp_context *ctx, int W, int H, const tsp_present_base &base, const tsp_present_layer *layers, int n_layers, void *out,
-            double *gpu_ms_out);
+            double *gpu_ms_out, bool yuv420);
 }  // namespace tsp

@@ -10,6 +10,9 @@
 // layer into primitives (pixel-space rectangles, line quads with their edge functions) and a conservative pixel bounding box;
 // a wave covers 64 pixels of one row, so a primitive whose box misses that row segment is skipped on a uniform branch.  The
 // frame is read once and written once; the textures and the table stay in L2.
+//
+// Movie frames (tsp_present_yuv420): a second, small kernel converts the composed RGBA8 staging frame to I420 planes on the
+// device, so the composition kernel is the same and only 1.5 bytes per pixel are copied out.
 #include "tsp_internal.h"
 
 #include <hip/hip_fp16.h>
@@ -164,6 +167,56 @@ __global__ __launch_bounds__(256) void present_kernel(BaseArgs b, const PresentP
     }
 }
 
+// ---- movie frames: the RGBA8 frame to I420 planes (include/topsy_splat.h "tsp_present_yuv420"); integer arithmetic, alpha ignored
+__device__ __forceinline__ uint32_t luma(uint32_t p) {
+    return ((47u * (p & 255u) + 157u * ((p >> 8) & 255u) + 16u * ((p >> 16) & 255u) + 128u) >> 8) + 16u;
+}
+// U | V << 8 of one 2 x 2 block: pixels a, b on the upper row, c, d below; `>>` on a negative int is a floor (arithmetic shift)
+__device__ __forceinline__ uint32_t chroma(uint32_t a, uint32_t b, uint32_t c, uint32_t d) {
+    const int r = (int)(((a & 255u) + (b & 255u) + (c & 255u) + (d & 255u) + 2u) >> 2);
+    const int g = (int)((((a >> 8) & 255u) + ((b >> 8) & 255u) + ((c >> 8) & 255u) + ((d >> 8) & 255u) + 2u) >> 2);
+    const int bl = (int)((((a >> 16) & 255u) + ((b >> 16) & 255u) + ((c >> 16) & 255u) + ((d >> 16) & 255u) + 2u) >> 2);
+    const int u = ((-26 * r - 86 * g + 112 * bl + 128) >> 8) + 128;
+    const int v = ((112 * r - 102 * g - 10 * bl + 128) >> 8) + 128;
+    return (uint32_t)u | ((uint32_t)v << 8);
+}
+
+// One lane per 4 x 2 block (two chroma samples): 16-byte loads of each row, 4-byte luma stores.  W4 = (W % 4 == 0); otherwise
+// W = 2 (mod 4), the odd rows start 8 bytes into a 16-byte line, so the rows come in as 8-byte halves, luma goes out as 2-byte
+// halves, chroma byte by byte, and the last lane of each row pair takes the remaining 2 x 2 block.
+template <bool W4>
+__global__ __launch_bounds__(256) void yuv420_kernel(const uint32_t *__restrict__ rgba, int W, int H, int lanes_per_row,
+                                                     uint8_t *__restrict__ yuv) {
+    const int t = (int)blockIdx.x * 256 + (int)threadIdx.x;
+    const int j = t / lanes_per_row;                         // row pair: rows 2j, 2j + 1; chroma row j
+    if (j >= H / 2) return;
+    const int x = (t - j * lanes_per_row) * 4;
+    const int64_t p0 = (int64_t)(2 * j) * W + x, p1 = p0 + W;
+    const int64_t c = (int64_t)j * (W / 2) + x / 2;
+    uint8_t *__restrict__ Y = yuv;
+    uint8_t *__restrict__ U = yuv + (int64_t)W * H;
+    uint8_t *__restrict__ V = U + (int64_t)(W / 2) * (H / 2);
+    if (W4) {
+        const uint4 a = *reinterpret_cast<const uint4 *>(rgba + p0), b = *reinterpret_cast<const uint4 *>(rgba + p1);
+        *reinterpret_cast<uint32_t *>(Y + p0) = luma(a.x) | (luma(a.y) << 8) | (luma(a.z) << 16) | (luma(a.w) << 24);
+        *reinterpret_cast<uint32_t *>(Y + p1) = luma(b.x) | (luma(b.y) << 8) | (luma(b.z) << 16) | (luma(b.w) << 24);
+        const uint32_t uv0 = chroma(a.x, a.y, b.x, b.y), uv1 = chroma(a.z, a.w, b.z, b.w);
+        *reinterpret_cast<uint16_t *>(U + c) = (uint16_t)((uv0 & 255u) | ((uv1 & 255u) << 8));
+        *reinterpret_cast<uint16_t *>(V + c) = (uint16_t)((uv0 >> 8) | (uv1 & 0xff00u));
+    } else {
+        const int n = x + 4 <= W ? 2 : 1;                    // 2 x 2 blocks of this lane
+        for (int k = 0; k < n; ++k) {
+            const uint2 a = *reinterpret_cast<const uint2 *>(rgba + p0 + 2 * k);
+            const uint2 b = *reinterpret_cast<const uint2 *>(rgba + p1 + 2 * k);
+            *reinterpret_cast<uint16_t *>(Y + p0 + 2 * k) = (uint16_t)(luma(a.x) | (luma(a.y) << 8));
+            *reinterpret_cast<uint16_t *>(Y + p1 + 2 * k) = (uint16_t)(luma(b.x) | (luma(b.y) << 8));
+            const uint32_t uv = chroma(a.x, a.y, b.x, b.y);
+            U[c + k] = (uint8_t)(uv & 255u);
+            V[c + k] = (uint8_t)(uv >> 8);
+        }
+    }
+}
+
 bool finite(float v) { return std::isfinite(v); }
 
 // Conservative pixel box of a primitive spanning [lo, hi] in pixels along one axis: float rounding of the coverage tests
@@ -306,11 +359,13 @@ int check_layer(const tsp_present_layer &L, int index, int64_t &n_prims, int64_t
 }  // namespace
 
 int present(tsp_context *ctx, int W, int H, const tsp_present_base &base, const tsp_present_layer *layers, int n_layers,
-            void *out, double *gpu_ms_out) {
+            void *out, double *gpu_ms_out, bool yuv420) {
     TSP_REQUIRE(W >= 1 && W <= MAX_SIDE && H >= 1 && H <= MAX_SIDE, TSP_EINVAL, "canvas %d x %d outside [1, %d]", W, H, MAX_SIDE);
+    if (yuv420) TSP_REQUIRE(W >= 2 && H >= 2 && W % 2 == 0 && H % 2 == 0, TSP_EINVAL, "4:2:0 needs an even canvas, not %d x %d", W, H);
     TSP_REQUIRE(n_layers >= 0 && n_layers <= MAX_LAYERS && (n_layers == 0 || layers), TSP_EINVAL, "bad layer list (%d layers)", n_layers);
     const int map = base.map;
     TSP_REQUIRE(map >= TSP_PRESENT_SCALAR && map <= TSP_PRESENT_RGB_HDR, TSP_EINVAL, "unknown base map %d", map);
+    if (yuv420) TSP_REQUIRE(map != TSP_PRESENT_RGB_HDR, TSP_EINVAL, "4:2:0 frames are 8-bit: the rgb-hdr map has no such frame");
     if (map == TSP_PRESENT_SCALAR)
         TSP_REQUIRE(base.lut_rgba && base.n_lut >= 2 && base.n_lut <= 65536, TSP_EINVAL, "bad colormap LUT (n=%d)", base.n_lut);
     if (map == TSP_PRESENT_BIVARIATE) TSP_REQUIRE(ctx->lut2d, TSP_ESTATE, "tsp_colormap_set_lut2d must be called first");
@@ -341,9 +396,11 @@ int present(tsp_context *ctx, int W, int H, const tsp_present_base &base, const 
     TSP_HIP(hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
     const bool hdr = map == TSP_PRESENT_RGB_HDR;
-    const size_t out_bytes = (size_t)W * H * (hdr ? 8 : 4);
-    DeviceScratch d_tex, d_prims, d_lut, d_out;
-    PRESENT_ALLOC(d_out, out_bytes);
+    const size_t frame_bytes = (size_t)W * H * (hdr ? 8 : 4);
+    const size_t out_bytes = yuv420 ? (size_t)W * H + 2 * ((size_t)(W / 2) * (H / 2)) : frame_bytes;
+    DeviceScratch d_tex, d_prims, d_lut, d_frame, d_yuv;
+    PRESENT_ALLOC(d_frame, frame_bytes);
+    if (yuv420) PRESENT_ALLOC(d_yuv, out_bytes);
     PRESENT_ALLOC(d_prims, prims.size() * sizeof(PresentPrim));
     PRESENT_ALLOC(d_tex, (size_t)n_texels * sizeof(float4));
     if (map == TSP_PRESENT_SCALAR) PRESENT_ALLOC(d_lut, (size_t)base.n_lut * sizeof(float4));
@@ -383,14 +440,27 @@ int present(tsp_context *ctx, int W, int H, const tsp_present_base &base, const 
     TSP_HIP(hipEventRecord(ctx->ev[3], st));
     if (hdr)
         hipLaunchKernelGGL(present_kernel<true>, grid, dim3(256), 0, st, b, d_prims.as<PresentPrim>(), (int)prims.size(),
-                           d_tex.as<float4>(), d_out.p);
+                           d_tex.as<float4>(), d_frame.p);
     else
         hipLaunchKernelGGL(present_kernel<false>, grid, dim3(256), 0, st, b, d_prims.as<PresentPrim>(), (int)prims.size(),
-                           d_tex.as<float4>(), d_out.p);
+                           d_tex.as<float4>(), d_frame.p);
     TSP_HIP(hipGetLastError());
+    if (yuv420) {
+        const bool w4 = W % 4 == 0;
+        const int lanes_per_row = w4 ? W / 4 : (W + 2) / 4;
+        const int n_lanes = lanes_per_row * (H / 2);        // <= 4096 * 8192
+        const dim3 ygrid((unsigned)((n_lanes + 255) / 256));
+        if (w4)
+            hipLaunchKernelGGL(yuv420_kernel<true>, ygrid, dim3(256), 0, st, d_frame.as<const uint32_t>(), W, H, lanes_per_row,
+                               d_yuv.as<uint8_t>());
+        else
+            hipLaunchKernelGGL(yuv420_kernel<false>, ygrid, dim3(256), 0, st, d_frame.as<const uint32_t>(), W, H, lanes_per_row,
+                               d_yuv.as<uint8_t>());
+        TSP_HIP(hipGetLastError());
+    }
     TSP_HIP(hipEventRecord(ctx->ev[4], st));
     TSP_HIP(hipStreamSynchronize(st));      // the frame is complete before anything of the caller's is written
-    TSP_HIP(hipMemcpyAsync(out, d_out.p, out_bytes, hipMemcpyDeviceToHost, st));
+    TSP_HIP(hipMemcpyAsync(out, yuv420 ? d_yuv.p : d_frame.p, out_bytes, hipMemcpyDeviceToHost, st));
     TSP_HIP(hipStreamSynchronize(st));
     if (gpu_ms_out) {
         float ms = 0.f;

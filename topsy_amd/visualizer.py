@@ -1,12 +1,15 @@
 """Headless Visualizer: the orchestrator surface of reference src/topsy/visualizer.py:31-602 for
 the accelerated path -- data loader -> resident particle buffers -> SPH renderer -> colormap.
 
-Windowing, the recorder and view synchronisation are out of scope; what the UI
-layers call on the orchestrator -- rotate / scale / position_offset / quantity_name / render_mode /
-invalidate / draw / colormap_autorange / get_sph_image / get_sph_presentation_image / get_depth_image /
-save -- is here with the reference's semantics, so those layers can sit on top unchanged.
+Windowing and view synchronisation are out of scope; what the UI layers call on
+the orchestrator -- rotate / scale / position_offset / quantity_name / render_mode / invalidate / draw /
+colormap_autorange / get_sph_image / get_sph_presentation_image / get_depth_image / save -- is here with
+the reference's semantics, so those layers can sit on top unchanged.
 get_presentation_image composes the full frame of any size on the GPU (tsp_present): the colormapped
-image with the colorbar, scale bar, crosshairs, simulation cube and status line of topsy_amd/overlays.py.
+image with the colorbar, scale bar, crosshairs, simulation cube and status line of topsy_amd/overlays.py;
+get_presentation_image_yuv420 returns that frame as the I420 planes a movie encoder reads
+(tsp_present_yuv420).  add_frame_listener lets the movie recorder (topsy_amd/recorder) sample the view
+state at every frame the visualizer produces.
 """
 import logging
 
@@ -61,6 +64,7 @@ class VisualizerBase:
         self._colorbar = overlays.ColorbarOverlay()
         self._scalebar = overlays.ScalebarOverlay(self.data_loader.get_position_units())
         self._status = overlays.StatusLine()
+        self._frame_listeners = []
         self._initialize_sph_and_colormap(colormap_name)
 
     # -- mode plumbing (reference visualizer.py:96-120, 170-186, 203-231) ----------------------
@@ -239,7 +243,22 @@ class VisualizerBase:
         self._pending_draw = None
         if reason != DrawReason.EXPORT and not self._prevent_sph_rendering and self._sph.needs_refine():
             self.invalidate(DrawReason.REFINE)
+        if reason not in (DrawReason.REFINE, DrawReason.PRESENTATION_CHANGE):   # what SynchronizationMixin.draw forwards
+            self._frame_produced()
         return out
+
+    # -- frame listeners (what the reference's view synchronizer tells the recorder) --------------
+    def add_frame_listener(self, callback):
+        """Call callback(visualizer) after every frame: draw for any reason but REFINE and PRESENTATION_CHANGE,
+        get_sph_presentation_image, get_presentation_image and get_presentation_image_yuv420."""
+        self._frame_listeners.append(callback)
+
+    def remove_frame_listener(self, callback):
+        self._frame_listeners.remove(callback)
+
+    def _frame_produced(self):
+        for callback in list(self._frame_listeners):
+            callback(self)
 
     # -- exports (reference visualizer.py:452-570) ---------------------------------------------
     def get_sph_image(self):
@@ -251,12 +270,35 @@ class VisualizerBase:
         self.render_sph(DrawReason.EXPORT)
         res = self._render_resolution
         self._colormap.set_scaling(res, res, self._sph.last_render_mass_scale)
-        return self._colormap.encode_render_pass(None, None)
+        out = self._colormap.encode_render_pass(None, None)
+        self._frame_produced()
+        return out
 
     def get_presentation_image(self, resolution=(640, 480)):
         """The full frame, (H, W, 4) uint8 (float16 for rgb-hdr) for resolution = (W, H): the image colormapped onto the canvas
         with the colorbar, scale bar, crosshairs, simulation cube and status line on top (reference visualizer.py:480-491,
         367-384), composed on the GPU in one pass (tsp_present)."""
+        width, height, ctx, base, layers = self._prepare_presentation(resolution)
+        out = ctx.present(width, height, base, layers)
+        self._frame_produced()
+        return out
+
+    def get_presentation_image_yuv420(self, resolution=(1920, 1080)):
+        """The frame get_presentation_image(resolution) composes, as I420 planes for a movie encoder: uint8 Y (H, W), U and V
+        (H/2, W/2), BT.709 limited range, converted on the GPU (tsp_present_yuv420, include/topsy_splat.h).  W and H must be
+        even; the rgb-hdr canvas has no 8-bit frame (ValueError)."""
+        width, height = (int(v) for v in resolution)
+        if width % 2 or height % 2:
+            raise ValueError(f"4:2:0 frames need an even width and height, not {width} x {height}")
+        if self.canvas_format != "rgba8unorm":
+            raise ValueError(f"4:2:0 frames are 8-bit: the {self._render_mode} canvas ({self.canvas_format}) has none")
+        width, height, ctx, base, layers = self._prepare_presentation(resolution)
+        out = ctx.present_yuv420(width, height, base, layers)
+        self._frame_produced()
+        return out
+
+    def _prepare_presentation(self, resolution):
+        """The EXPORT render, the colormap scaling, the base and the layers of a (W, H) frame."""
         width, height = (int(v) for v in resolution)
         if not (1 <= width <= 16384 and 1 <= height <= 16384):
             raise ValueError(f"resolution {resolution} outside 1 .. 16384 pixels per side")
@@ -266,7 +308,7 @@ class VisualizerBase:
         base = self._colormap.present_base(ctx)
         layers = self._presentation_layers(width, height)
         self._last_presentation = (base, layers)      # what the frame was composed from (tests restate it)
-        return ctx.present(width, height, base, layers)
+        return width, height, ctx, base, layers
 
     def _presentation_layers(self, width, height):
         """The layers in the reference's order (visualizer.py:367-384): colorbar, scale bar, crosshairs, cube, status line."""
