@@ -81,7 +81,8 @@ const char *tsp_last_error(void);
  * 107: surface rendering: tsp_set_sphere_mips, tsp_density_order_stats, tsp_render_surface, tsp_surface_present and the
  * struct tsp_surface_params; nothing else changed.
  * 108: frame composition: tsp_present and the structs tsp_present_base / tsp_present_layer; nothing else changed.
- * 109: movie frames: tsp_present_yuv420 (the tsp_present frame as I420 planes); nothing else changed. */
+ * 109: movie frames: tsp_present_yuv420 (the tsp_present frame as I420 planes); nothing else changed.
+ * 110: new entry point tsp_sph_sum (gather-form SPH sums: densities for snapshots that carry none); nothing else changed. */
 int tsp_version(void);
 int tsp_stats_size(void);
 
@@ -229,6 +230,30 @@ int tsp_tile_periodic(tsp_context *ctx, int n, const float *offsets_xy, const fl
  * a failed allocation returns TSP_ENOMEM. */
 int tsp_smoothing_lengths(tsp_context *ctx, int64_t n, const float *x, const float *y, const float *z,
                           int n_neighbours, float period, float *h_out);
+
+/* Gather-form SPH sum at the particles: with a = mass, the density pynbody derives as snapshot['rho'].
+ * Host arrays in and out, caller's order; uses ctx's device and stream only: resident particles, image, accumulator and
+ * tsp_stats unchanged.  Float32 unless said otherwise, with these operations in this order (no fused multiply-adds):
+ *   - Particle i is valid iff x[i], y[i], z[i] are finite.  A query i is answerable iff it is valid and h[i] is finite and > 0.
+ *     out[i] = NaN for a query that is not answerable.  Invalid particles are nobody's neighbour.  a[j] is used as given (a NaN
+ *     or infinite a[j] propagates into the sums it takes part in).
+ *   - For an answerable i, over every valid j (j = i included):
+ *         dx, dy, dz, d2 exactly as tsp_smoothing_lengths defines them (nearest image when period > 0);
+ *         u = sqrtf(d2) / h[i];  the term exists iff u < 2;
+ *         u2 = u * u;  w = u < 1 ? (1 - 1.5f * u2) + 0.75f * (u2 * u) : 0.25f * ((t * t) * t) with t = 2 - u;
+ *         term = a[j] * w;  S += (double)term  (float64 sum, any order);
+ *     out[i] = (float)(S / (M_PI * (double)((h[i] * h[i]) * h[i]))).
+ *     This is the M4 cubic spline with support 2h in gather form (the query's own h).  With a = mass and h from
+ *     tsp_smoothing_lengths(k) the sum runs over the k - 1 nearest neighbours and the particle itself (the k-th sits at u = 2
+ *     exactly and is excluded).
+ *   - The order of the sum is free but fixed (no atomics in it): the same call on the same input and device returns the same
+ *     bits; for a >= 0 any two orders agree to within one float32 ulp of out[i].
+ * 1 <= n < 2^31, period = 0 (open box) or finite and > 0, no NULL array; anything else returns TSP_EINVAL and writes nothing.
+ * There is no limit on the number of neighbours: the cost is proportional to the candidates scanned, so a caller's own very
+ * large h is slow, not wrong.  Device memory is allocated for the call only (about 56 bytes per particle); a failed allocation
+ * returns TSP_ENOMEM and writes nothing. */
+int tsp_sph_sum(tsp_context *ctx, int64_t n, const float *x, const float *y, const float *z, const float *h,
+                const float *a, float period, float *out);
 
 /* Surface rendering: DepthSPHWithOcclusion + ColorAsSurfaceMap (reference src/topsy/sph.py:448-656, shaders/sph.wgsl:94-122,
  * 149-158, shaders/smooth.wgsl, shaders/surface.wgsl, colormap/surface.py).  Float32 throughout, operations in the order written.

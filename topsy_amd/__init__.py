@@ -30,7 +30,11 @@ def from_arrays(pos, smooth, mass, quantities=None, rgb=None, with_cells=False, 
     """Visualizer over caller-supplied numpy arrays (e.g. taken from a pynbody snapshot).
 
     smooth=None computes the smoothing lengths on the GPU from the n_smooth (default config.SMOOTH_NEIGHBOURS) nearest
-    neighbours, in the periodic box of side periodicity_scale if one is given; vis.data_loader.get_smooth() returns them."""
+    neighbours, in the periodic box of side periodicity_scale if one is given; vis.data_loader.get_smooth() returns them.
+
+    'rho' is always a quantity (vis.quantity_name = "rho"; the bivariate map's default): quantities["rho"] if given, else
+    the SPH density of the particles, computed on the GPU on first use (sph_density) and cached on the loader --
+    vis.data_loader.get_named_quantity("rho") returns it, set_density() restores it from the caller's own cache."""
     from . import visualizer, loader
     return visualizer.Visualizer(data_loader_class=loader.ArrayDataLoader,
                                  data_loader_kwargs={"pos": pos, "smooth": smooth, "mass": mass,
@@ -54,6 +58,65 @@ def smoothing_lengths(pos, n_smooth=config.SMOOTH_NEIGHBOURS, periodicity_scale=
     ctx = _native.Context(1, 2, device_id)
     try:
         return ctx.smoothing_lengths(pos[:, 0], pos[:, 1], pos[:, 2], n_smooth, period)
+    finally:
+        ctx.close()
+
+
+def _sph_arguments(pos, mass, smooth, n_smooth, periodicity_scale, **others):
+    """The arguments of sph_density / sph_mean, checked on the host: float32 arrays of one length, pos (n, 3)."""
+    from . import loader
+    n_smooth, period = loader.check_smoothing_arguments(n_smooth, periodicity_scale)
+    pos = np.asarray(pos, dtype=np.float32)
+    if pos.ndim != 2 or pos.shape[1] != 3:
+        raise ValueError(f"pos must have shape (n, 3), not {pos.shape}")
+    arrays = {"mass": mass, "smooth": smooth, **others}
+    for name, a in arrays.items():
+        if a is None:
+            continue
+        arrays[name] = a = np.asarray(a, dtype=np.float32)
+        if a.shape != (len(pos),):
+            raise ValueError(f"pos and {name} must have the same length: {name} has shape {a.shape}, not ({len(pos)},)")
+    if len(pos) == 0:
+        raise ValueError("pos must have at least one particle")
+    if smooth is None:
+        n_finite = int(np.isfinite(pos).all(axis=1).sum())
+        if n_finite < n_smooth:
+            raise ValueError(f"{n_finite} particles have finite coordinates; n_smooth = {n_smooth} needs at least as many")
+    return pos, arrays, n_smooth, period
+
+
+def sph_density(pos, mass, smooth=None, n_smooth=config.SMOOTH_NEIGHBOURS, periodicity_scale=None, device_id=0):
+    """SPH density at the particles of an (n, 3) position array on GPU `device_id` (C: tsp_sph_sum): the gather sum
+    rho_i = sum_j mass_j W(|r_i - r_j|, smooth_i) with the M4 cubic spline of support 2 smooth_i -- pynbody's snap['rho'].
+    smooth=None computes the smoothing lengths first (as smoothing_lengths does, from n_smooth neighbours) on the same
+    context.  NaN where a coordinate is not finite or smooth is not finite and > 0.  Returns float32 (n,)."""
+    from . import _native
+    pos, arr, n_smooth, period = _sph_arguments(pos, mass, smooth, n_smooth, periodicity_scale)
+    ctx = _native.Context(1, 2, device_id)
+    try:
+        x, y, z = pos[:, 0], pos[:, 1], pos[:, 2]
+        h = ctx.smoothing_lengths(x, y, z, n_smooth, period) if arr["smooth"] is None else arr["smooth"]
+        return ctx.sph_sum(x, y, z, h, arr["mass"], period)
+    finally:
+        ctx.close()
+
+
+def sph_mean(pos, mass, smooth, values, rho=None, n_smooth=config.SMOOTH_NEIGHBOURS, periodicity_scale=None, device_id=0):
+    """SPH interpolant of a per-particle quantity at the particles: sum_j (mass_j values_j / rho_j) W(|r_i - r_j|, smooth_i),
+    the weights formed in float32.  rho=None computes the density first (sph_density), smooth=None the smoothing lengths, on
+    the same context.  Weights of 0/0 or x/0 are the caller's data and propagate.  Returns float32 (n,)."""
+    from . import _native
+    pos, arr, n_smooth, period = _sph_arguments(pos, mass, smooth, n_smooth, periodicity_scale, values=values, rho=rho)
+    if arr["values"] is None:
+        raise ValueError("values must be an array of the same length as pos")
+    ctx = _native.Context(1, 2, device_id)
+    try:
+        x, y, z = pos[:, 0], pos[:, 1], pos[:, 2]
+        h = ctx.smoothing_lengths(x, y, z, n_smooth, period) if arr["smooth"] is None else arr["smooth"]
+        rho = ctx.sph_sum(x, y, z, h, arr["mass"], period) if arr["rho"] is None else arr["rho"]
+        with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+            a = arr["mass"] * arr["values"] / rho
+        return ctx.sph_sum(x, y, z, h, a, period)
     finally:
         ctx.close()
 

@@ -16,7 +16,7 @@ MODE_WEIGHTED, MODE_DEPTH, MODE_RGB = 0, 1, 2
 PIPE_DEFAULT, PIPE_GENERIC = 0, 1
 SAMPLE_BILINEAR_MIP0, SAMPLE_BILINEAR_MIP = 0x10, 0x20      # diagnostic sampling rules (generic kernel)
 UNIQUE_ID_BYTES = 128
-ABI_VERSION = 109            # include/topsy_splat.h: tsp_version()
+ABI_VERSION = 110            # include/topsy_splat.h: tsp_version()
 PRESENT_SCALAR, PRESENT_BIVARIATE, PRESENT_RGB, PRESENT_RGB_HDR = 0, 1, 2, 3
 LAYER_QUAD, LAYER_LINES = 0, 1
 
@@ -110,6 +110,7 @@ SIGNATURES = {
                                              ctypes.c_float, ctypes.c_float, _u8p, _fp]),
     "tsp_tile_periodic": (ctypes.c_int, [_ctx, ctypes.c_int, _fp, _fp]),
     "tsp_smoothing_lengths": (ctypes.c_int, [_ctx, ctypes.c_int64, _fp, _fp, _fp, ctypes.c_int, ctypes.c_float, _fp]),
+    "tsp_sph_sum": (ctypes.c_int, [_ctx, ctypes.c_int64, _fp, _fp, _fp, _fp, _fp, ctypes.c_float, _fp]),
     "tsp_set_sphere_mips": (ctypes.c_int, [_ctx, _fp, ctypes.c_int, ctypes.c_int]),
     "tsp_density_order_stats": (ctypes.c_int, [_ctx, _i64p, ctypes.c_int, _fp]),
     "tsp_render_surface": (ctypes.c_int, [_ctx, _fp, ctypes.c_float, ctypes.c_float, _i64p, _i64p, ctypes.c_int, ctypes.c_int,
@@ -366,6 +367,17 @@ class Context:
         out = np.empty(n, dtype=np.float32)
         _check(self._lib.tsp_smoothing_lengths(self._h, n, _ptr(x), _ptr(y), _ptr(z), int(n_neighbours),
                                                float(np.float32(period or 0.0)), _ptr(out)))
+        return out
+
+    def sph_sum(self, x, y, z, h, a, period=None):
+        """Gather-form SPH sum at caller-ordered float32 particles (tsp_sph_sum): sum_j a[j] W(|r_i - r_j|, h[i]) with the M4
+        spline of support 2 h[i]; a = mass gives the density.  NaN where a coordinate is not finite or h is not finite and > 0.
+        period: the side of a periodic box (None or 0: open).  Uses this context's device only; what is resident stays."""
+        n = len(x)
+        x, y, z, h, a = _f32(x, n, "x"), _f32(y, n, "y"), _f32(z, n, "z"), _f32(h, n, "h"), _f32(a, n, "a")
+        out = np.empty(n, dtype=np.float32)
+        _check(self._lib.tsp_sph_sum(self._h, n, _ptr(x), _ptr(y), _ptr(z), _ptr(h), _ptr(a), float(np.float32(period or 0.0)),
+                                     _ptr(out)))
         return out
 
     # ---- surface (include/topsy_splat.h "Surface rendering") ---------------------------------

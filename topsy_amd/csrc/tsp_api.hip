@@ -167,7 +167,7 @@ using namespace tsp;
 extern "C" {
 
 const char *tsp_last_error(void) { return g_err; }
-int tsp_version(void) { return 109; }     // 109: tsp_present_yuv420; 108: tsp_present; 107: surface rendering; 106: tsp_smoothing_lengths; 101: tsp_stats gained ms_mega, n_mega (16 bytes); 102: the per-kernel fragment counts (32 bytes); 103: n_chunk_culled (8 bytes); 104: matrix-core / kernel-I options removed; 105: kernel M's options removed (kernel G draws the mid footprints)
+int tsp_version(void) { return 110; }     // 110: tsp_sph_sum; 109: tsp_present_yuv420; 108: tsp_present; 107: surface rendering; 106: tsp_smoothing_lengths; 101: tsp_stats gained ms_mega, n_mega (16 bytes); 102: the per-kernel fragment counts (32 bytes); 103: n_chunk_culled (8 bytes); 104: matrix-core / kernel-I options removed; 105: kernel M's options removed (kernel G draws the mid footprints)
 int tsp_stats_size(void) { return (int)sizeof(tsp_stats); }
 
 int tsp_device_count(void) {
@@ -755,6 +755,16 @@ int tsp_smoothing_lengths(tsp_context *ctx, int64_t n, const float *x, const flo
     TSP_REQUIRE(n >= n_neighbours, TSP_EINVAL, "%lld particles, n_neighbours = %d", (long long)n, n_neighbours);
     TSP_HIP(hipSetDevice(ctx->device));
     return smoothing_lengths(ctx, n, x, y, z, n_neighbours, period == 0.0f ? 0.0f : period, h_out);
+}
+
+int tsp_sph_sum(tsp_context *ctx, int64_t n, const float *x, const float *y, const float *z, const float *h, const float *a,
+                float period, float *out) {
+    TSP_REQUIRE(ctx && x && y && z && h && a && out, TSP_EINVAL, "NULL argument");
+    TSP_REQUIRE(n >= 1 && n < (1ll << 31), TSP_EINVAL, "n = %lld outside [1, 2^31)", (long long)n);
+    TSP_REQUIRE(period == 0.0f || (std::isfinite(period) && period > 0.0f), TSP_EINVAL,
+                "period must be 0 (open box) or finite and > 0, not %g", (double)period);
+    TSP_HIP(hipSetDevice(ctx->device));
+    return sph_sum(ctx, n, x, y, z, h, a, period == 0.0f ? 0.0f : period, out);
 }
 
 int tsp_present(tsp_context *ctx, int width, int height, const tsp_present_base *base, const tsp_present_layer *layers,

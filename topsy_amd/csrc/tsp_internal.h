@@ -231,6 +231,8 @@ int content_sort(tsp_context *ctx, int kind, float scale, int64_t *n_finite, int
 int ensure_array(float **p, int64_t n);
 int smoothing_lengths(tsp_context *ctx, int64_t n, const float *x, const float *y, const float *z, int k, float period,
                       float *h_out);   // tsp_smooth.hip: per-call DeviceScratch only, no context state
+int sph_sum(tsp_context *ctx, int64_t n, const float *x, const float *y, const float *z, const float *h, const float *a,
+            float period, float *out);       // tsp_smooth.hip: the gather-form SPH sum on the same index; per-call DeviceScratch only
 // tsp_surface.hip: the occlusion pass + resolve (keys in image64, (q, depth) in image), the rho order statistics and the
 // filter + shading; per-call memory is DeviceScratch
 int render_surface(tsp_context *ctx, const Camera &cam, float cut, const int64_t *h_starts, const int64_t *h_lens,

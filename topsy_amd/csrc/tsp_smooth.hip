@@ -21,6 +21,9 @@
 //   4. h in the caller's order, scattered through the sort's index.
 // One thread per query, queries in Morton order: the lanes of a wave share their cells, so the candidates they stream
 // come from the same cache lines.
+//
+// tsp_sph_sum, the gather-form SPH sum (with a = mass: the density pynbody derives as 'rho'), is a range query of radius 2 h[i]
+// over the same index (step 1 is shared: build_morton_index); its kernel is described at sph_sum_kernel below.
 #include <hipcub/hipcub.hpp>
 
 #include <math.h>
@@ -283,51 +286,202 @@ __global__ __launch_bounds__(256) void smooth_knn_kernel(const float *__restrict
     if ((threadIdx.x & 63) == 0 && evaluated) atomicAdd(n_dist, evaluated);
 }
 
-#define SMOOTH_ALLOC(buf, bytes)                                                                                         \
+// ---- tsp_sph_sum: the gather-form SPH sum over the same index -------------------------------------------------------------
+// gather of the per-particle h and a into Morton order
+__global__ __launch_bounds__(256) void sph_gather_kernel(const float *__restrict__ h, const float *__restrict__ a,
+                                                         const uint32_t *__restrict__ idx, int64_t nv, float *__restrict__ sh,
+                                                         float *__restrict__ sa) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nv; i += (int64_t)gridDim.x * blockDim.x) {
+        const uint32_t j = idx[i];
+        sh[i] = h[j];
+        sa[i] = a[j];
+    }
+}
+
+// The contract's term for a candidate at squared distance d2: float32, these operations in this order; 0 terms when u >= 2.
+__device__ __forceinline__ void sph_term(float d2, float aj, float hq, double &S, unsigned &terms) {
+    const float u = __fdiv_rn(sqrtf(d2), hq);
+    if (u < 2.0f) {
+        const float u2 = u * u;
+        const float t = 2.0f - u;
+        const float w = u < 1.0f ? (1.0f - 1.5f * u2) + 0.75f * (u2 * u) : 0.25f * ((t * t) * t);
+        S += (double)(aj * w);
+        ++terms;
+    }
+}
+
+// A range query of radius 2 h[i] over the octree of key prefixes (the level choice, the runs and the conservative box test of
+// smooth_knn_kernel), every candidate of the surviving runs tested with the contract's own u < 2.
+// Step A, one lane per query in Morton order: the (at most eight) runs of the query, into LDS.
+// Step B, one wave per query: the wave takes the queries of its lanes in turn and scans each one's runs 64 candidates at a time
+// (coalesced loads, every lane busy but in a run's last step); a lane sums its own candidates in a double, the 64 partial sums are
+// added by a butterfly, whose order is fixed, so the same call returns the same bits (no atomics take part in the sum).
+// With one lane per query a wave scanned as long as its longest run at each cell: measured on clustered positions, 21 % of its
+// lanes' steps had a candidate, and every lane streamed cache lines of its own.
+__global__ __launch_bounds__(256) void sph_sum_kernel(const float *__restrict__ sx, const float *__restrict__ sy,
+                                                      const float *__restrict__ sz, const float *__restrict__ sh,
+                                                      const float *__restrict__ sa, const uint64_t *__restrict__ keys,
+                                                      int64_t nv, Grid g, float *__restrict__ out_sorted,
+                                                      unsigned long long *counters) {
+    __shared__ uint32_t run_b[256][8], run_e[256][8];
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int lane = threadIdx.x & 63, wave0 = threadIdx.x & ~63;
+    const float L = g.period;
+    unsigned long long scanned = 0, steps = 0;
+    unsigned terms = 0;
+    float hq = 0.0f, qx = 0.0f, qy = 0.0f, qz = 0.0f, reach2 = 0.0f;
+    bool answerable = false;
+    for (int r = 0; r < 8; ++r) run_b[threadIdx.x][r] = run_e[threadIdx.x][r] = 0;
+    if (i < nv) {
+        hq = sh[i];
+        answerable = __builtin_isfinite(hq) && hq > 0.0f;
+    }
+    if (answerable) {
+        qx = sx[i], qy = sy[i], qz = sz[i];
+        // every term has sqrtf(d2) / hq < 2, so d2 <= reach2 (the slack covers the two roundings; an overflowing reach2
+        // is +inf and rejects nothing, one too small to be formed reliably is not used)
+        const float reach = (2.0f * hq) * CULL_SLACK;
+        const float R = reach + g.eps;
+        reach2 = reach * reach >= 1e-30f ? reach * reach : __builtin_inff();
+        const double cull2 = ((double)reach * (double)reach) * (double)CULL_SLACK;
+        const float q[3] = {grid_coord(qx, L), grid_coord(qy, L), grid_coord(qz, L)};
+        int uq[3], ua[3], ub[3];
+        for (int a = 0; a < 3; ++a) {
+            uq[a] = qclamp(qstep(q[a], g.lo[a], g.inv[a]));
+            ua[a] = qstep(q[a] - R, g.lo[a], g.inv[a]);
+            ub[a] = qstep(q[a] + R, g.lo[a], g.inv[a]);
+            if (L == 0.0f) {
+                ua[a] = qclamp(ua[a]);
+                ub[a] = qclamp(ub[a]);
+            }
+            ua[a] = min(ua[a], uq[a]);
+            ub[a] = max(ub[a], uq[a]);
+        }
+        int s = 0;
+        while (s < QBITS && ((ub[0] >> s) - (ua[0] >> s) > 1 || (ub[1] >> s) - (ua[1] >> s) > 1 || (ub[2] >> s) - (ua[2] >> s) > 1))
+            ++s;
+        const int ncell = 1 << (QBITS - s);
+        int own[3], other[3];
+        for (int a = 0; a < 3; ++a) {
+            own[a] = uq[a] >> s;
+            const int ca = ua[a] >> s, cb = ub[a] >> s;
+            other[a] = (ncell == 1) ? own[a] : (ca != own[a] ? ca : cb);
+        }
+        for (int combo = 0; combo < 8; ++combo) {
+            int c[3];
+            bool skip = false;
+            for (int a = 0; a < 3; ++a) {
+                const bool second = (combo >> a) & 1;
+                if (second && other[a] == own[a]) skip = true;
+                c[a] = second ? other[a] : own[a];
+            }
+            if (skip) continue;
+            const double gx = axis_gap(g, 0, q[0], c[0], s);
+            const double gy = axis_gap(g, 1, q[1], c[1], s);
+            const double gz = axis_gap(g, 2, q[2], c[2], s);
+            if ((gx * gx + gy * gy) + gz * gz > cull2) continue;
+            const uint64_t prefix = morton3((uint32_t)(c[0] & (ncell - 1)), (uint32_t)(c[1] & (ncell - 1)), (uint32_t)(c[2] & (ncell - 1)));
+            const int shift = 3 * s;
+            const int64_t b = key_lower_bound(keys, nv, prefix << shift);
+            const int64_t e = key_lower_bound(keys, nv, (prefix + 1) << shift);
+            run_b[threadIdx.x][combo] = (uint32_t)b;      // (nv < 2^31)
+            run_e[threadIdx.x][combo] = (uint32_t)e;
+            scanned += (unsigned long long)(e - b);
+        }
+    }
+    __syncthreads();
+
+    double S = 0.0;
+    const unsigned long long todo = __ballot(answerable);
+    for (int l = 0; l < 64; ++l) {
+        if (!((todo >> l) & 1)) continue;                   // (uniform over the wave)
+        const float lx = __shfl(qx, l), ly = __shfl(qy, l), lz = __shfl(qz, l), lh = __shfl(hq, l), lreach2 = __shfl(reach2, l);
+        double part = 0.0;
+        for (int r = 0; r < 8; ++r) {
+            const int64_t b = run_b[wave0 + l][r], e = run_e[wave0 + l][r];
+            for (int64_t j = b + lane; j < e; j += 64) {
+                const float d2 = dist2(lx, ly, lz, sx[j], sy[j], sz[j], L);
+                if (d2 <= lreach2) sph_term(d2, sa[j], lh, part, terms);
+            }
+            steps += (unsigned long long)((e - b + 63) >> 6);
+        }
+        for (int off = 32; off; off >>= 1) part += __shfl_xor(part, off);
+        if (lane == l) S = part;
+    }
+    if (i < nv) out_sorted[i] = answerable ? (float)(S / (M_PI * (double)((hq * hq) * hq))) : __builtin_nanf("");
+
+    unsigned long long nterms = terms;
+    for (int off = 32; off; off >>= 1) {
+        scanned += __shfl_xor(scanned, off);
+        nterms += __shfl_xor(nterms, off);
+    }
+    if (lane == 0 && scanned) {
+        atomicAdd(&counters[0], scanned);
+        atomicAdd(&counters[1], nterms);
+        atomicAdd(&counters[2], steps);
+    }
+}
+
+#define SMOOTH_ALLOC(who, buf, bytes)                                                                                    \
     do {                                                                                                                 \
         const hipError_t e_ = (buf).alloc(bytes);                                                                        \
         if (e_ != hipSuccess) {                                                                                          \
             (void)hipGetLastError();                                                                                     \
-            tsp::set_error("tsp_smoothing_lengths: cannot allocate %zu bytes of device memory: %s", (size_t)(bytes),     \
+            tsp::set_error("%s: cannot allocate %zu bytes of device memory: %s", (who), (size_t)(bytes),                 \
                            hipGetErrorString(e_));                                                                       \
             return e_ == hipErrorOutOfMemory ? TSP_ENOMEM : TSP_EHIP;                                                    \
         }                                                                                                                \
     } while (0)
 
-}  // namespace
+// Step 1 of both entry points: the raw positions on the device (dx, dy, dz), the grid, the sorted keys (keys2) with the
+// sort's index (vals2: sorted -> caller's order), and the positions of the nv valid particles in Morton order (sx, sy, sz).
+// vals (n x 4 bytes) is free for the caller's per-query result once the sort is done.
+struct MortonIndex {
+    DeviceScratch dx, dy, dz, keys2, vals, vals2, sx, sy, sz, mm;
+    Grid g = {};
+    int64_t nv = 0;
+    unsigned grid = 0;                       // blocks of the grid-stride kernels
+    unsigned long long *d_count = nullptr;   // [0] valid particles, [1] .. [3] the caller's counters (zeroed)
+};
 
-int smoothing_lengths(tsp_context *ctx, int64_t n, const float *x, const float *y, const float *z, int k, float period,
-                      float *h_out) {
+// min_valid: the call is refused (TSP_EINVAL) when fewer particles have finite coordinates
+int build_morton_index(tsp_context *ctx, const char *who, int64_t n, const float *x, const float *y, const float *z, float period,
+                       int min_valid, MortonIndex &ix) {
     hipStream_t st = ctx->stream;
     const size_t fbytes = (size_t)n * sizeof(float);
-    DeviceScratch dx, dy, dz, keys, keys2, vals, vals2, sx, sy, sz, mm;
-    SMOOTH_ALLOC(dx, fbytes);
-    SMOOTH_ALLOC(dy, fbytes);
-    SMOOTH_ALLOC(dz, fbytes);
-    SMOOTH_ALLOC(mm, 6 * sizeof(unsigned) + 2 * sizeof(unsigned long long));
+    DeviceScratch &dx = ix.dx, &dy = ix.dy, &dz = ix.dz, &keys2 = ix.keys2, &vals = ix.vals, &vals2 = ix.vals2, &sx = ix.sx,
+                  &sy = ix.sy, &sz = ix.sz, &mm = ix.mm;
+    DeviceScratch keys;
+    SMOOTH_ALLOC(who, dx, fbytes);
+    SMOOTH_ALLOC(who, dy, fbytes);
+    SMOOTH_ALLOC(who, dz, fbytes);
+    SMOOTH_ALLOC(who, mm, 6 * sizeof(unsigned) + 4 * sizeof(unsigned long long));
     TSP_HIP(hipMemcpyAsync(dx.p, x, fbytes, hipMemcpyHostToDevice, st));
     TSP_HIP(hipMemcpyAsync(dy.p, y, fbytes, hipMemcpyHostToDevice, st));
     TSP_HIP(hipMemcpyAsync(dz.p, z, fbytes, hipMemcpyHostToDevice, st));
 
-    // 1. bounding box, grid, keys, sort
+    // bounding box, grid, keys, sort
     unsigned *d_mm = mm.as<unsigned>();
-    unsigned long long *d_count = reinterpret_cast<unsigned long long *>(d_mm + 6);   // [0] valid particles, [1] distances
+    unsigned long long *d_count = reinterpret_cast<unsigned long long *>(d_mm + 6);
+    ix.d_count = d_count;
     const unsigned init[6] = {0xffffffffu, 0xffffffffu, 0xffffffffu, 0, 0, 0};
     TSP_HIP(hipMemcpyAsync(d_mm, init, sizeof(init), hipMemcpyHostToDevice, st));
-    TSP_HIP(hipMemsetAsync(d_count, 0, 2 * sizeof(unsigned long long), st));
+    TSP_HIP(hipMemsetAsync(d_count, 0, 4 * sizeof(unsigned long long), st));
     const unsigned grid = (unsigned)std::min<int64_t>((n + 255) / 256, 4096);
+    ix.grid = grid;
     hipLaunchKernelGGL(smooth_bbox_kernel, dim3(grid), dim3(256), 0, st, dx.as<float>(), dy.as<float>(), dz.as<float>(), n, d_mm);
     TSP_HIP(hipGetLastError());
     unsigned hmm[6];
     TSP_HIP(hipMemcpyAsync(hmm, d_mm, sizeof(hmm), hipMemcpyDeviceToHost, st));
     TSP_HIP(hipStreamSynchronize(st));
 
-    Grid g = {};
+    Grid &g = ix.g;
+    g = {};
     g.period = period;
     double maxabs = period;
     for (int a = 0; a < 3; ++a) {
         const float lo = unordered_bits(hmm[a]), hi = unordered_bits(hmm[3 + a]);
-        if (hmm[a] > hmm[3 + a]) break;      // no finite particle at all (refused below)
+        if (hmm[a] > hmm[3 + a]) break;      // no finite particle at all
         maxabs = std::max(maxabs, std::max(fabs((double)lo), fabs((double)hi)));
         const double extent = period > 0.0f ? (double)period : (double)hi - (double)lo;
         g.lo[a] = period > 0.0f ? 0.0f : lo;
@@ -338,10 +492,10 @@ int smoothing_lengths(tsp_context *ctx, int64_t n, const float *x, const float *
     }
     g.eps = (float)(1e-5 * maxabs) + 1e-30f;
 
-    SMOOTH_ALLOC(keys, (size_t)n * sizeof(uint64_t));
-    SMOOTH_ALLOC(keys2, (size_t)n * sizeof(uint64_t));
-    SMOOTH_ALLOC(vals, (size_t)n * sizeof(uint32_t));
-    SMOOTH_ALLOC(vals2, (size_t)n * sizeof(uint32_t));
+    SMOOTH_ALLOC(who, keys, (size_t)n * sizeof(uint64_t));
+    SMOOTH_ALLOC(who, keys2, (size_t)n * sizeof(uint64_t));
+    SMOOTH_ALLOC(who, vals, (size_t)n * sizeof(uint32_t));
+    SMOOTH_ALLOC(who, vals2, (size_t)n * sizeof(uint32_t));
     hipLaunchKernelGGL(smooth_key_kernel, dim3(grid), dim3(256), 0, st, dx.as<float>(), dy.as<float>(), dz.as<float>(), n, g,
                        keys.as<uint64_t>(), vals.as<uint32_t>(), d_count);
     TSP_HIP(hipGetLastError());
@@ -349,25 +503,43 @@ int smoothing_lengths(tsp_context *ctx, int64_t n, const float *x, const float *
     TSP_HIP(hipMemcpyAsync(&nv_u, d_count, sizeof(nv_u), hipMemcpyDeviceToHost, st));
     TSP_HIP(hipStreamSynchronize(st));
     const int64_t nv = (int64_t)nv_u;
-    TSP_REQUIRE(nv >= k, TSP_EINVAL, "tsp_smoothing_lengths: %lld particles have finite coordinates, n_neighbours = %d needs at least as many",
-                (long long)nv, k);
+    ix.nv = nv;
+    TSP_REQUIRE(nv >= min_valid, TSP_EINVAL, "%s: %lld particles have finite coordinates, n_neighbours = %d needs at least as many",
+                who, (long long)nv, min_valid);
     {
         DeviceScratch tmp;
         size_t tmp_bytes = 0;
         TSP_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, keys.as<uint64_t>(), keys2.as<uint64_t>(), vals.as<uint32_t>(),
                                                    vals2.as<uint32_t>(), (int)n, 0, 64, st));
-        SMOOTH_ALLOC(tmp, tmp_bytes);
+        SMOOTH_ALLOC(who, tmp, tmp_bytes);
         TSP_HIP(hipcub::DeviceRadixSort::SortPairs(tmp.p, tmp_bytes, keys.as<uint64_t>(), keys2.as<uint64_t>(), vals.as<uint32_t>(),
                                                    vals2.as<uint32_t>(), (int)n, 0, 64, st));
         TSP_HIP(hipStreamSynchronize(st));
     }
     keys.reset(nullptr);
-    SMOOTH_ALLOC(sx, (size_t)nv * sizeof(float));
-    SMOOTH_ALLOC(sy, (size_t)nv * sizeof(float));
-    SMOOTH_ALLOC(sz, (size_t)nv * sizeof(float));
+    SMOOTH_ALLOC(who, sx, (size_t)nv * sizeof(float));
+    SMOOTH_ALLOC(who, sy, (size_t)nv * sizeof(float));
+    SMOOTH_ALLOC(who, sz, (size_t)nv * sizeof(float));
     hipLaunchKernelGGL(smooth_gather_kernel, dim3(grid), dim3(256), 0, st, dx.as<float>(), dy.as<float>(), dz.as<float>(),
                        vals2.as<uint32_t>(), nv, sx.as<float>(), sy.as<float>(), sz.as<float>());
     TSP_HIP(hipGetLastError());
+    return TSP_OK;
+}
+
+}  // namespace
+
+int smoothing_lengths(tsp_context *ctx, int64_t n, const float *x, const float *y, const float *z, int k, float period,
+                      float *h_out) {
+    hipStream_t st = ctx->stream;
+    const size_t fbytes = (size_t)n * sizeof(float);
+    MortonIndex ix;
+    const int rc = build_morton_index(ctx, "tsp_smoothing_lengths", n, x, y, z, period, k, ix);
+    if (rc != TSP_OK) return rc;
+    DeviceScratch &dx = ix.dx, &keys2 = ix.keys2, &vals = ix.vals, &vals2 = ix.vals2, &sx = ix.sx, &sy = ix.sy, &sz = ix.sz;
+    const Grid &g = ix.g;
+    const int64_t nv = ix.nv;
+    const unsigned grid = ix.grid;
+    unsigned long long *d_count = ix.d_count;
 
     // 2. + 3. one thread per query in Morton order; h_sorted reuses the unsorted index buffer
     float *h_sorted = vals.as<float>();
@@ -395,6 +567,51 @@ int smoothing_lengths(tsp_context *ctx, int64_t n, const float *x, const float *
     if (env && env[0] == '1')
         fprintf(stderr, "tsp_smoothing_lengths: n=%lld valid=%lld k=%d distances=%llu per_query=%.2f\n", (long long)n, (long long)nv,
                 k, n_dist, nv ? (double)n_dist / (double)nv : 0.0);
+    return TSP_OK;
+}
+
+int sph_sum(tsp_context *ctx, int64_t n, const float *x, const float *y, const float *z, const float *h, const float *a,
+            float period, float *out) {
+    hipStream_t st = ctx->stream;
+    const size_t fbytes = (size_t)n * sizeof(float);
+    MortonIndex ix;
+    const int rc = build_morton_index(ctx, "tsp_sph_sum", n, x, y, z, period, 0, ix);
+    if (rc != TSP_OK) return rc;
+    const int64_t nv = ix.nv;
+
+    // h and a into Morton order; the raw y and z buffers are free once the positions are gathered
+    DeviceScratch dh, da;
+    SMOOTH_ALLOC("tsp_sph_sum", dh, fbytes);
+    SMOOTH_ALLOC("tsp_sph_sum", da, fbytes);
+    TSP_HIP(hipMemcpyAsync(dh.p, h, fbytes, hipMemcpyHostToDevice, st));
+    TSP_HIP(hipMemcpyAsync(da.p, a, fbytes, hipMemcpyHostToDevice, st));
+    float *sh = ix.dy.as<float>(), *sa = ix.dz.as<float>();
+    hipLaunchKernelGGL(sph_gather_kernel, dim3(ix.grid), dim3(256), 0, st, dh.as<float>(), da.as<float>(), ix.vals2.as<uint32_t>(), nv,
+                       sh, sa);
+    TSP_HIP(hipGetLastError());
+
+    // queries in Morton order; the sorted result reuses the unsorted index buffer
+    float *out_sorted = ix.vals.as<float>();
+    if (nv > 0) {
+        hipLaunchKernelGGL(sph_sum_kernel, dim3((unsigned)((nv + 255) / 256)), dim3(256), 0, st, ix.sx.as<float>(), ix.sy.as<float>(),
+                           ix.sz.as<float>(), sh, sa, ix.keys2.as<uint64_t>(), nv, ix.g, out_sorted, ix.d_count + 1);
+        TSP_HIP(hipGetLastError());
+    }
+    // back to the caller's order (the raw x buffer is free now); invalid particles get NaN
+    hipLaunchKernelGGL(smooth_scatter_kernel, dim3(ix.grid), dim3(256), 0, st, out_sorted, ix.vals2.as<uint32_t>(), n, nv,
+                       ix.dx.as<float>());
+    TSP_HIP(hipGetLastError());
+    unsigned long long counts[3] = {0, 0, 0};
+    TSP_HIP(hipMemcpyAsync(counts, ix.d_count + 1, sizeof(counts), hipMemcpyDeviceToHost, st));
+    TSP_HIP(hipStreamSynchronize(st));
+    TSP_HIP(hipMemcpy(out, ix.dx.p, fbytes, hipMemcpyDeviceToHost));
+    // measurement aid: TOPSY_SMOOTH_STATS=1 reports the candidates scanned and the terms summed per query, and the share of
+    // the lanes' scan steps that had a candidate (the last step of a run is rarely full)
+    const char *env = getenv("TOPSY_SMOOTH_STATS");
+    if (env && env[0] == '1')
+        fprintf(stderr, "tsp_sph_sum: n=%lld valid=%lld candidates=%llu per_query=%.2f terms=%llu per_query=%.2f lane_use=%.3f\n",
+                (long long)n, (long long)nv, counts[0], nv ? (double)counts[0] / (double)nv : 0.0, counts[1],
+                nv ? (double)counts[1] / (double)nv : 0.0, counts[2] ? (double)counts[0] / (64.0 * (double)counts[2]) : 0.0);
     return TSP_OK;
 }
 

@@ -180,7 +180,12 @@ class ArrayDataLoader(AbstractDataLoader):
 
     smooth=None: the snapshot has no smoothing lengths (dark matter, stars).  The loader then records that it needs them
     (`needs_smoothing`); ParticleBuffers computes them on the GPU from the n_smooth nearest neighbours before the upload
-    (the reference calls pynbody.sph.smooth there, loader.py:222-240) and hands them back through set_smooth()."""
+    (the reference calls pynbody.sph.smooth there, loader.py:222-240) and hands them back through set_smooth().
+
+    'rho' is always a quantity, as it is for every pynbody family (the reference hands any such name to the renderer,
+    loader.py:123-127): quantities["rho"] when the caller supplied one, else the gather-form SPH density of the particles,
+    computed on the GPU at the first get_named_quantity("rho") -- by the visualizer's context once ParticleBuffers has set it
+    (set_density_context), else by a context of its own -- and cached; set_density() restores it from the caller's cache."""
 
     # reference PynbodyDataInMemory.get_rgb_masses (loader.py:115-121): (band, weight) per rgb channel
     RGB_BANDS = (("I", 0.5), ("V", 1.0), ("U", 1.0))
@@ -201,6 +206,8 @@ class ArrayDataLoader(AbstractDataLoader):
         self._mags = None if band_magnitudes is None else {k: np.asarray(v, dtype=np.float64) for k, v in band_magnitudes.items()}
         self._units = units
         self._period = periodicity_scale
+        self._rho = None                 # the computed density ('rho' when the caller supplied none), in this loader's order
+        self._density_context = None
         if self.needs_smoothing:
             if self._pos.ndim != 2 or self._pos.shape[1] != 3:
                 raise ValueError(f"pos must have shape (n, 3), not {self._pos.shape}")
@@ -246,10 +253,48 @@ class ArrayDataLoader(AbstractDataLoader):
         return self._mass
 
     def get_named_quantity(self, name):
+        if name == "rho" and name not in self._quantities:
+            return self._density()
         return self._quantities[name]
 
     def get_quantity_names(self):
-        return list(self._quantities)
+        names = list(self._quantities)
+        return names if "rho" in self._quantities else names + ["rho"]
+
+    def set_density_context(self, context):
+        """The context that computes 'rho' on first use (ParticleBuffers hands over its own; None: one made for the call)."""
+        self._density_context = context
+
+    def set_density(self, rho):
+        """The density 'rho' in this loader's particle order (e.g. from the caller's cache, next to set_smooth): it is then
+        not computed.  A supplied quantities["rho"] is never replaced."""
+        rho = np.asarray(rho, dtype=np.float32)
+        if rho.shape != (len(self),):
+            raise ValueError(f"rho must have shape ({len(self)},), not {rho.shape}")
+        if "rho" in self._quantities:
+            raise ValueError("the caller supplied quantities['rho']; it is used as given")
+        self._rho = rho
+
+    def _density(self):
+        if self._rho is None:
+            period = self._period or 0.0
+            if self._pos.ndim != 2 or self._pos.shape[1] != 3:
+                raise ValueError(f"pos must have shape (n, 3), not {self._pos.shape}")
+            check_smoothing_arguments(self.n_smooth, self._period)
+            ctx = self._density_context
+            own = ctx is None
+            if own:
+                from . import _native
+                ctx = _native.Context(1, 2, self._device if isinstance(self._device, int) else 0)
+            try:
+                x, y, z = self._pos[:, 0], self._pos[:, 1], self._pos[:, 2]
+                if self._smooth is None:
+                    self.set_smooth(ctx.smoothing_lengths(x, y, z, self.n_smooth, period))
+                self._rho = ctx.sph_sum(x, y, z, self._smooth, self._mass, period)
+            finally:
+                if own:
+                    ctx.close()
+        return self._rho
 
     def get_quantity_label(self, quantity_name):
         return "density" if quantity_name is None else quantity_name

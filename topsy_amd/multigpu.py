@@ -201,6 +201,10 @@ class MultiGpuContext:
         every particle in one place.  Touches no shard's particles or image, so it needs no end_frame first."""
         return self.contexts[0].smoothing_lengths(x, y, z, n_neighbours, period)
 
+    def sph_sum(self, x, y, z, h, a, period=None):
+        """The SPH sum over the whole (caller-ordered) snapshot, on the first context like smoothing_lengths."""
+        return self.contexts[0].sph_sum(x, y, z, h, a, period)
+
     def generate_synthetic(self, n_total, first=0, count=None, seed=1337, h_cap=0.0, with_quantity=False, with_rgb=False):
         count = n_total - first if count is None else count
         # the generator's index bijection makes every index range a uniform sample: contiguous shards are balanced

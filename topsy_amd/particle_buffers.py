@@ -60,6 +60,8 @@ class ParticleBuffers:
             pos = ld.get_positions()
             ld.set_smooth(self.context.smoothing_lengths(pos[:, 0], pos[:, 1], pos[:, 2], ld.n_smooth,
                                                          ld.get_periodicity_scale() or 0.0))
+        if hasattr(ld, "set_density_context"):
+            ld.set_density_context(self.context)      # 'rho' of a snapshot that carries none: an SPH sum on this context
         logger.info("Uploading position+smoothing+mass arrays")
         ps = ld.get_pos_smooth()
         self.context.upload_particles(ps[:, 0], ps[:, 1], ps[:, 2], ps[:, 3], ld.get_mass())
