@@ -82,7 +82,8 @@ const char *tsp_last_error(void);
  * struct tsp_surface_params; nothing else changed.
  * 108: frame composition: tsp_present and the structs tsp_present_base / tsp_present_layer; nothing else changed.
  * 109: movie frames: tsp_present_yuv420 (the tsp_present frame as I420 planes); nothing else changed.
- * 110: new entry point tsp_sph_sum (gather-form SPH sums: densities for snapshots that carry none); nothing else changed. */
+ * 110: new entry point tsp_sph_sum (gather-form SPH sums: densities for snapshots that carry none); nothing else changed.
+ * 111: new entry point tsp_content_neg_inf (how many content values of the last tsp_content_sort were -inf); nothing else changed. */
 int tsp_version(void);
 int tsp_stats_size(void);
 
@@ -417,9 +418,16 @@ int tsp_present_yuv420(tsp_context *ctx, int width, int height, const tsp_presen
  * including the fragment-count channel), sorts the FINITE values on the device
  * and reports how many there are and how many of them are <= 0.  tsp_content_values then returns
  * the values at the given ranks of that ascending order (the host needs only a handful: min, max,
- * and the neighbours of each percentile's virtual index). */
+ * and the neighbours of each percentile's virtual index): TSP_EINVAL for a rank outside [0, n_finite),
+ * TSP_ESTATE before the first sort; ranks are checked one by one.  -0.0 sorts before +0.0 and both count
+ * as <= 0; denormal products are kept, not flushed.
+ * What happens to the values that are not finite: NaN and +inf are dropped and counted nowhere (the host
+ * rule ignores them too); -inf is dropped from the sort and from both counts as well, but the host rule
+ * `use_log = not (vals < 0).any()` sees it as a negative value, so the sort counts the -inf values and
+ * tsp_content_neg_inf reports that count for the last tsp_content_sort (TSP_ESTATE before the first). */
 int tsp_content_sort(tsp_context *ctx, int kind, float scale, int64_t *n_finite, int64_t *n_nonpositive);
 int tsp_content_values(tsp_context *ctx, const int64_t *ranks, int n_ranks, float *out);
+int tsp_content_neg_inf(tsp_context *ctx, int64_t *n_neg_inf);
 
 /* Counters of the last tsp_render call (measurement aid). */
 typedef struct {

@@ -16,7 +16,7 @@ MODE_WEIGHTED, MODE_DEPTH, MODE_RGB = 0, 1, 2
 PIPE_DEFAULT, PIPE_GENERIC = 0, 1
 SAMPLE_BILINEAR_MIP0, SAMPLE_BILINEAR_MIP = 0x10, 0x20      # diagnostic sampling rules (generic kernel)
 UNIQUE_ID_BYTES = 128
-ABI_VERSION = 110            # include/topsy_splat.h: tsp_version()
+ABI_VERSION = 111            # include/topsy_splat.h: tsp_version()
 PRESENT_SCALAR, PRESENT_BIVARIATE, PRESENT_RGB, PRESENT_RGB_HDR = 0, 1, 2, 3
 LAYER_QUAD, LAYER_LINES = 0, 1
 
@@ -122,6 +122,7 @@ SIGNATURES = {
                                           ctypes.POINTER(ctypes.c_double)]),
     "tsp_content_sort": (ctypes.c_int, [_ctx, ctypes.c_int, ctypes.c_float, _i64p, _i64p]),
     "tsp_content_values": (ctypes.c_int, [_ctx, _i64p, ctypes.c_int, _fp]),
+    "tsp_content_neg_inf": (ctypes.c_int, [_ctx, _i64p]),
     "tsp_get_stats": (ctypes.c_int, [_ctx, ctypes.POINTER(Stats)]),
     "tsp_set_option": (ctypes.c_int, [_ctx, ctypes.c_char_p, ctypes.c_int64]),
     "tsp_measure_read_bandwidth": (ctypes.c_int, [_ctx, ctypes.c_int64, ctypes.c_int, ctypes.POINTER(ctypes.c_double)]),
@@ -450,6 +451,12 @@ class Context:
         out = np.empty(len(r), dtype=np.float32)
         _check(self._lib.tsp_content_values(self._h, r.ctypes.data_as(_i64p), len(r), _ptr(out)))
         return out
+
+    def content_neg_inf(self):
+        """How many content values of the last content_sort were -inf (dropped from the sort, negative to the autorange)."""
+        n = ctypes.c_int64(0)
+        _check(self._lib.tsp_content_neg_inf(self._h, ctypes.byref(n)))
+        return n.value
 
     def stats(self):
         s = Stats()

@@ -25,7 +25,7 @@ def percentile_from_order_statistics(fetch, first, n, q, transform=None):
     Follows numpy's own arithmetic step by step (numpy/lib/_function_base_impl.py): the divisor 100 takes
     the data dtype, so a Python-float q interpolates in float32 and an array q in float64; virtual index
     (n-1)*q; _lerp with its t >= 0.5 branch.  The device autorange therefore equals the host one bit for
-    bit (tests/test_host_logic.py, tests/test_gpu_visualizer.py)."""
+    bit (tests/test_host_logic.py, tests/test_autorange_cpu.py, tests/test_gpu_postpass.py, tests/test_gpu_visualizer.py)."""
     return _quantile_from_order_statistics(fetch, first, n, q, np.true_divide(q, np.float32(100)), transform)
 
 
@@ -173,7 +173,9 @@ class Colormap(ColormapBase):
 
     def autorange_on_device(self, mass_scale=1.0):
         """autorange_vmin_vmax(get_image()) without reading the image back: the device sorts the finite
-        content values (tsp_content_sort) and the host needs ~8 of them."""
+        content values (tsp_content_sort) and the host needs ~8 of them, plus the number
+        of -inf values the sort dropped (tsp_content_neg_inf).  tests/test_autorange_cpu.py runs this against the host rule on
+        degenerate images without a GPU, tests/test_gpu_postpass.py on the device."""
         ctx = self._input_texture.context
         kind = 1 if self._params["weighted_average"] else 0
         n_fin, n_nonpos = ctx.content_sort(kind, mass_scale)
@@ -186,6 +188,9 @@ class Colormap(ColormapBase):
             else:
                 lo = hi = np.nan
                 any_negative = False
+            # the host rule is (vals < 0).any() over ALL content values: a -inf (ch0 == 0, ch1 < 0) is no order statistic
+            # of the finite values, yet it switches the map to linear
+            any_negative = any_negative or ctx.content_neg_inf() > 0
             if n_pos:
                 lo_log, hi_log = np.log10(fetch([n_nonpos, n_fin - 1]))
             else:

@@ -167,7 +167,7 @@ using namespace tsp;
 extern "C" {
 
 const char *tsp_last_error(void) { return g_err; }
-int tsp_version(void) { return 110; }     // 110: tsp_sph_sum; 109: tsp_present_yuv420; 108: tsp_present; 107: surface rendering; 106: tsp_smoothing_lengths; 101: tsp_stats gained ms_mega, n_mega (16 bytes); 102: the per-kernel fragment counts (32 bytes); 103: n_chunk_culled (8 bytes); 104: matrix-core / kernel-I options removed; 105: kernel M's options removed (kernel G draws the mid footprints)
+int tsp_version(void) { return 111; }     // 111: tsp_content_neg_inf; 110: tsp_sph_sum; 109: tsp_present_yuv420; 108: tsp_present; 107: surface rendering; 106: tsp_smoothing_lengths; 101: tsp_stats gained ms_mega, n_mega (16 bytes); 102: the per-kernel fragment counts (32 bytes); 103: n_chunk_culled (8 bytes); 104: matrix-core / kernel-I options removed; 105: kernel M's options removed (kernel G draws the mid footprints)
 int tsp_stats_size(void) { return (int)sizeof(tsp_stats); }
 
 int tsp_device_count(void) {
@@ -806,6 +806,13 @@ int tsp_content_values(tsp_context *ctx, const int64_t *ranks, int n_ranks, floa
         const uint32_t bits = (key & 0x80000000u) ? (key & 0x7fffffffu) : ~key;   // inverse of the monotone map
         memcpy(&out[i], &bits, 4);
     }
+    return TSP_OK;
+}
+
+int tsp_content_neg_inf(tsp_context *ctx, int64_t *n_neg_inf) {
+    TSP_REQUIRE(ctx && n_neg_inf, TSP_EINVAL, "NULL argument");
+    TSP_REQUIRE(ctx->sort_keys_alt, TSP_ESTATE, "tsp_content_sort has not been called");
+    *n_neg_inf = ctx->sorted_neg_inf;
     return TSP_OK;
 }
 

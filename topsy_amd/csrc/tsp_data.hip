@@ -467,8 +467,8 @@ int reorder_spatial(tsp_context *ctx, int n_strata, uint64_t seed, int64_t *perm
 // ------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void content_key_kernel(const float *__restrict__ img, int64_t npix, int C, int kind,
                                                           float scale, uint32_t *__restrict__ keys,
-                                                          unsigned long long *counts /* [finite, nonpositive] */) {
-    unsigned long long nf = 0, nnp = 0;
+                                                          unsigned long long *counts /* [finite, nonpositive, -inf] */) {
+    unsigned long long nf = 0, nnp = 0, nni = 0;
     const int per_px = (kind == 2) ? 3 : (kind == 3 ? C : 1);
     for (int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x; t < npix * per_px; t += (int64_t)gridDim.x * 256) {
         float v;
@@ -484,14 +484,17 @@ __global__ __launch_bounds__(256) void content_key_kernel(const float *__restric
         keys[t] = fin ? ordered_u32(v) : 0xFFFFFFFFu;
         nf += fin;
         nnp += fin && (v <= 0.0f);
+        nni += (v == -__builtin_inff());                        // dropped from the sort, but "negative" to the host's log / linear rule
     }
     for (int o = 32; o; o >>= 1) {
         nf += __shfl_xor((long long)nf, o);
         nnp += __shfl_xor((long long)nnp, o);
+        nni += __shfl_xor((long long)nni, o);
     }
     if ((threadIdx.x & 63) == 0) {
         if (nf) atomicAdd(&counts[0], nf);
         if (nnp) atomicAdd(&counts[1], nnp);
+        if (nni) atomicAdd(&counts[2], nni);
     }
 }
 
@@ -509,16 +512,17 @@ int content_sort(tsp_context *ctx, int kind, float scale, int64_t *n_finite, int
         if (rc) return rc;
     }
     unsigned long long *counts = reinterpret_cast<unsigned long long *>(ctx->counters);   // scratch: reuse the counter block
-    TSP_HIP(hipMemsetAsync(counts, 0, 2 * sizeof(unsigned long long), st));
+    TSP_HIP(hipMemsetAsync(counts, 0, 3 * sizeof(unsigned long long), st));
     const unsigned grid = (unsigned)std::min<int64_t>((n + 255) / 256, (int64_t)ctx->cu_count * 8);
     hipLaunchKernelGGL(content_key_kernel, dim3(grid), dim3(256), 0, st, ctx->image, npix, ctx->C, kind, scale, ctx->sort_keys, counts);
     TSP_HIP(hipGetLastError());
     size_t tmp_bytes = ctx->sort_tmp_bytes;
     TSP_HIP(hipcub::DeviceRadixSort::SortKeys(ctx->sort_tmp, tmp_bytes, ctx->sort_keys, ctx->sort_keys_alt, n, 0, 32, st));
-    unsigned long long hc[2];
+    unsigned long long hc[3];
     TSP_HIP(hipMemcpyAsync(hc, counts, sizeof(hc), hipMemcpyDeviceToHost, st));
     TSP_HIP(hipStreamSynchronize(st));
     ctx->sorted_count = (int64_t)hc[0];
+    ctx->sorted_neg_inf = (int64_t)hc[2];
     *n_finite = (int64_t)hc[0];
     *n_nonpositive = (int64_t)hc[1];
     return TSP_OK;

@@ -126,6 +126,7 @@ struct tsp_context {
     void *sort_tmp = nullptr;
     size_t sort_tmp_bytes = 0;
     int64_t sort_capacity = 0, sorted_count = 0;
+    int64_t sorted_neg_inf = 0;       // content values equal to -inf that the last tsp_content_sort dropped
     tsp_stats stats = {};
     std::vector<int64_t> cell_offsets;     // first index of every (stratum, Morton cell) run of the last reorder_spatial, then n
     int cell_bits = 0;                     // the cells form a (2^cell_bits)^3 grid over the bounding box

@@ -141,7 +141,7 @@ class MultiGpuContext:
     # forwarded: it has a sharded implementation below or does not exist on several GPUs.
     _ROOT_OPERATIONS = ("read_image", "colormap_scalar", "colormap_rgb", "colormap_set_lut2d", "colormap_bivariate",
                         "colormap_bivariate_host", "colormap_scalar_host", "colormap_rgb_host", "content_sort",
-                        "content_values", "tile_periodic", "measure_read_bandwidth", "present",
+                        "content_values", "content_neg_inf", "tile_periodic", "measure_read_bandwidth", "present",
                         "present_yuv420")
 
     def __getattr__(self, name):
