@@ -205,6 +205,22 @@ def device_count():
     return load_library().tsp_device_count()
 
 
+def _ranges(starts, lens):
+    """(starts pointer, lens pointer, count, the arrays the pointers lend from) of a render call's ranges; None = no ranges."""
+    if starts is None:
+        return None, None, 0, None
+    s = np.ascontiguousarray(starts, dtype=np.int64)
+    l = np.ascontiguousarray(lens, dtype=np.int64)
+    if s.shape != l.shape or s.ndim != 1:
+        raise ValueError("starts and lens must be 1-D arrays of equal length")
+    if len(s) == 0:
+        # an empty selection (e.g. view culling picked no cell of this block) draws nothing: hand the library one
+        # explicit zero-length range so that it can never be read as "no ranges given = all particles"
+        s = np.zeros(1, dtype=np.int64)
+        l = np.zeros(1, dtype=np.int64)
+    return s.ctypes.data_as(_i64p), l.ctypes.data_as(_i64p), len(s), (s, l)
+
+
 class Context:
     """One GPU renderer: R x R x C float32 target + resident SoA particles (include/topsy_splat.h)."""
 
@@ -318,20 +334,7 @@ class Context:
         """One synchronous render block; returns GPU milliseconds (hipEvent pair)."""
         M = _f32(np.asarray(matrix, dtype=np.float32).reshape(16), 16, "matrix")
         ms = ctypes.c_double(0.0)
-        if starts is None:
-            sp = lp = None
-            nr = 0
-        else:
-            s = np.ascontiguousarray(starts, dtype=np.int64)
-            l = np.ascontiguousarray(lens, dtype=np.int64)
-            if s.shape != l.shape or s.ndim != 1:
-                raise ValueError("starts and lens must be 1-D arrays of equal length")
-            if len(s) == 0:
-                # an empty selection (e.g. view culling picked no cell of this block) draws nothing: hand the library one
-                # explicit zero-length range so that it can never be read as "no ranges given = all particles"
-                s = np.zeros(1, dtype=np.int64)
-                l = np.zeros(1, dtype=np.int64)
-            sp, lp, nr = s.ctypes.data_as(_i64p), l.ctypes.data_as(_i64p), len(s)
+        sp, lp, nr, _keep = _ranges(starts, lens)
         _check(self._lib.tsp_render(self._h, _ptr(M), float(scale_factor), sp, lp, nr, int(bool(clear)), int(mode),
                                     int(flags), ctypes.byref(ms)))
         self.active_channels = 4 if mode == MODE_RGB else 2
@@ -397,18 +400,7 @@ class Context:
         """The occlusion pass: (q, depth) of the front-most sphere per pixel becomes the 2-channel image; returns GPU ms."""
         M = _f32(np.asarray(matrix, dtype=np.float32).reshape(16), 16, "matrix")
         ms = ctypes.c_double(0.0)
-        if starts is None:
-            sp = lp = None
-            nr = 0
-        else:
-            s = np.ascontiguousarray(starts, dtype=np.int64)
-            l = np.ascontiguousarray(lens, dtype=np.int64)
-            if s.shape != l.shape or s.ndim != 1:
-                raise ValueError("starts and lens must be 1-D arrays of equal length")
-            if len(s) == 0:
-                s = np.zeros(1, dtype=np.int64)
-                l = np.zeros(1, dtype=np.int64)
-            sp, lp, nr = s.ctypes.data_as(_i64p), l.ctypes.data_as(_i64p), len(s)
+        sp, lp, nr, _keep = _ranges(starts, lens)
         _check(self._lib.tsp_render_surface(self._h, _ptr(M), float(scale_factor), float(np.float32(density_cut)), sp, lp, nr,
                                             int(bool(clear)), ctypes.byref(ms)))
         self.active_channels = 2
@@ -750,15 +742,7 @@ class Group:
     def render(self, matrix, scale_factor, starts=None, lens=None, clear=True, mode=MODE_WEIGHTED, flags=PIPE_DEFAULT):
         M = _f32(np.asarray(matrix, dtype=np.float32).reshape(16), 16, "matrix")
         ms = ctypes.c_double(0.0)
-        if starts is None:
-            sp = lp = None
-            nr = 0
-        else:
-            s = np.ascontiguousarray(starts, dtype=np.int64)
-            l = np.ascontiguousarray(lens, dtype=np.int64)
-            if len(s) == 0:
-                s, l = np.zeros(1, dtype=np.int64), np.zeros(1, dtype=np.int64)
-            sp, lp, nr = s.ctypes.data_as(_i64p), l.ctypes.data_as(_i64p), len(s)
+        sp, lp, nr, _keep = _ranges(starts, lens)
         _check(self._lib.tsp_group_render(self._g, _ptr(M), float(scale_factor), sp, lp, nr, int(bool(clear)), int(mode), int(flags),
                                           ctypes.byref(ms)))
         self.root.active_channels = 4 if mode == MODE_RGB else 2

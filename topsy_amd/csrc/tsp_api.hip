@@ -160,6 +160,42 @@ static void free_particles(tsp_context *ctx) {
     ctx->cell_bits = 0;
 }
 
+// clips the ranges (starts, lens) of a render call to [0, n) and drops the empty ones (an indirect draw with instance_count 0
+// draws nothing); no ranges = every particle.  Returns the particles they hold in *total.
+static int clip_ranges(const tsp_context *ctx, const int64_t *starts, const int64_t *lens, int n_ranges, std::vector<int64_t> &s,
+                       std::vector<int64_t> &l, int64_t *total) {
+    if (!starts) {
+        if (ctx->p.n > 0) { s.push_back(0); l.push_back(ctx->p.n); }
+    } else {
+        for (int i = 0; i < n_ranges; ++i) {
+            TSP_REQUIRE(lens[i] >= 0, TSP_EINVAL, "range %d has negative length %lld", i, (long long)lens[i]);
+            // clip without forming starts + lens (a caller may pass INT64_MAX for "to the end")
+            int64_t b = starts[i], len = lens[i];
+            if (b < 0) {
+                len = (len > -b) ? len + b : 0;      // b > INT64_MIN + len, no overflow
+                b = 0;
+            }
+            if (b >= ctx->p.n || len == 0) continue;
+            if (len > ctx->p.n - b) len = ctx->p.n - b;
+            s.push_back(b);
+            l.push_back(len);
+        }
+    }
+    *total = 0;
+    for (int64_t v : l) *total += v;
+    return TSP_OK;
+}
+
+static Camera make_camera(const tsp_context *ctx, const float *M, float scale_factor) {
+    Camera cam;
+    for (int i = 0; i < 12; ++i) cam.m[i] = M[i];
+    cam.sf = scale_factor;
+    cam.R = ctx->R;
+    cam.Rf = (float)ctx->R;
+    cam.halfR = 0.5f * cam.Rf;
+    return cam;
+}
+
 }  // namespace tsp
 
 using namespace tsp;
@@ -489,37 +525,13 @@ static int render_block(tsp_context *ctx, const float *M, float scale_factor, co
     TSP_REQUIRE(n_ranges >= 0 && (n_ranges == 0 || (starts && lens) || (!starts && !lens)), TSP_EINVAL, "bad ranges");
     TSP_HIP(hipSetDevice(ctx->device));
 
-    // clip the ranges to [0, n) and drop empties (an indirect draw with instance_count 0 draws nothing)
     std::vector<int64_t> s, l;
-    if (!starts) {
-        if (ctx->p.n > 0) { s.push_back(0); l.push_back(ctx->p.n); }
-    } else {
-        for (int i = 0; i < n_ranges; ++i) {
-            TSP_REQUIRE(lens[i] >= 0, TSP_EINVAL, "range %d has negative length %lld", i, (long long)lens[i]);
-            // clip without forming starts + lens (a caller may pass INT64_MAX for "to the end")
-            int64_t b = starts[i], len = lens[i];
-            if (b < 0) {
-                len = (len > -b) ? len + b : 0;      // b > INT64_MIN + len, no overflow
-                b = 0;
-            }
-            if (b >= ctx->p.n || len == 0) continue;
-            if (len > ctx->p.n - b) len = ctx->p.n - b;
-            s.push_back(b);
-            l.push_back(len);
-        }
-    }
-    const int nr = (int)s.size();
     int64_t total = 0;
-    for (int i = 0; i < nr; ++i) total += l[i];
+    if (int rc = clip_ranges(ctx, starts, lens, n_ranges, s, l, &total)) return rc;
+    const int nr = (int)s.size();
+    const Camera cam = make_camera(ctx, M, scale_factor);
 
-    Camera cam;
-    for (int i = 0; i < 12; ++i) cam.m[i] = M[i];
-    cam.sf = scale_factor;
-    cam.R = ctx->R;
-    cam.Rf = (float)ctx->R;
-    cam.halfR = 0.5f * cam.Rf;
-
-    TSP_HIP(hipEventRecord(ctx->ev[0], ctx->stream));
+    TSP_HIP(hipEventRecord(ctx->ev[EV_RENDER_BEGIN], ctx->stream));
     if (clear)
         TSP_HIP(hipMemsetAsync(ctx->image64, 0, (size_t)ctx->R * ctx->R * ctx->C * sizeof(double), ctx->stream));
     TSP_HIP(hipMemsetAsync(ctx->counters, 0, sizeof(Counters), ctx->stream));
@@ -558,10 +570,10 @@ static int render_block(tsp_context *ctx, const float *M, float scale_factor, co
     if (rc) return rc;
     if ((rc = launch_image_convert(ctx, true))) return rc;     // round the float64 master image once
     ctx->image_is_reduced = false;                             // `image` is this rank's partial image again
-    TSP_HIP(hipEventRecord(ctx->ev[1], ctx->stream));
+    TSP_HIP(hipEventRecord(ctx->ev[EV_RENDER_END], ctx->stream));
     TSP_HIP(hipStreamSynchronize(ctx->stream));
     float ms = 0.f;
-    TSP_HIP(hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]));
+    TSP_HIP(hipEventElapsedTime(&ms, ctx->ev[EV_RENDER_BEGIN], ctx->ev[EV_RENDER_END]));
     ctx->stats.ms_total = ms;
     Counters hc;
     TSP_HIP(hipMemcpy(&hc, ctx->counters, sizeof(hc), hipMemcpyDeviceToHost));
@@ -677,8 +689,22 @@ int tsp_colormap_bivariate(tsp_context *ctx, float vmin, float vmax, float densi
     return TSP_OK;
 }
 
-static int ensure_scratch(tsp_context *ctx, size_t bytes) {
-    if (ctx->scratch_bytes < bytes) return alloc_group(ctx, {{"colormap_scratch", &ctx->scratch, bytes}}, {{&ctx->scratch_bytes, (int64_t)bytes}});
+// Host-image colormaps: the context's scratch holds the input and up to two outputs behind it, each at a 256-byte boundary.
+struct HostStage { float *in; uint8_t *out8; float *outf; };
+static int stage_host_image(tsp_context *ctx, size_t in_bytes, size_t out8_bytes, size_t outf_bytes, HostStage &hs) {
+    const size_t a_in = (in_bytes + 255) & ~(size_t)255, a_o8 = (out8_bytes + 255) & ~(size_t)255, bytes = a_in + a_o8 + outf_bytes;
+    if (ctx->scratch_bytes < bytes)
+        if (int rc = alloc_group(ctx, {{"colormap_scratch", &ctx->scratch, bytes}}, {{&ctx->scratch_bytes, (int64_t)bytes}})) return rc;
+    hs.in = (float *)ctx->scratch;
+    hs.out8 = (uint8_t *)ctx->scratch + a_in;
+    hs.outf = (float *)(hs.out8 + a_o8);
+    return TSP_OK;
+}
+// the outputs the caller asked for back to the host, then the stream is drained
+static int unstage_host_image(tsp_context *ctx, const HostStage &hs, uint8_t *out8, size_t out8_bytes, float *outf, size_t outf_bytes) {
+    if (out8) TSP_HIP(hipMemcpyAsync(out8, hs.out8, out8_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    if (outf) TSP_HIP(hipMemcpyAsync(outf, hs.outf, outf_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    TSP_HIP(hipStreamSynchronize(ctx->stream));
     return TSP_OK;
 }
 
@@ -689,17 +715,14 @@ int tsp_colormap_scalar_host(tsp_context *ctx, const float *img, int H, int W, i
     TSP_HIP(hipSetDevice(ctx->device));
     const int64_t npix = (int64_t)H * W;
     const size_t in_bytes = (size_t)npix * C * sizeof(float), out_bytes = (size_t)npix * 4;
-    int rc = ensure_scratch(ctx, in_bytes + out_bytes + 256);
+    HostStage hs;
+    int rc = stage_host_image(ctx, in_bytes, out_bytes, 0, hs);
     if (rc) return rc;
     if ((rc = ensure_lut(ctx, lut_rgba, n_lut))) return rc;
-    float *d_in = (float *)ctx->scratch;
-    uint8_t *d_out = (uint8_t *)ctx->scratch + ((in_bytes + 255) & ~(size_t)255);
-    TSP_HIP(hipMemcpyAsync(d_in, img, in_bytes, hipMemcpyHostToDevice, ctx->stream));
-    if ((rc = launch_colormap_scalar(ctx, d_in, npix, C, ctx->lut, n_lut, vmin, vmax, log_scale, weighted, d_out)))
+    TSP_HIP(hipMemcpyAsync(hs.in, img, in_bytes, hipMemcpyHostToDevice, ctx->stream));
+    if ((rc = launch_colormap_scalar(ctx, hs.in, npix, C, ctx->lut, n_lut, vmin, vmax, log_scale, weighted, hs.out8)))
         return rc;
-    TSP_HIP(hipMemcpyAsync(out_rgba, d_out, out_bytes, hipMemcpyDeviceToHost, ctx->stream));
-    TSP_HIP(hipStreamSynchronize(ctx->stream));
-    return TSP_OK;
+    return unstage_host_image(ctx, hs, out_rgba, out_bytes, nullptr, 0);
 }
 
 int tsp_colormap_bivariate_host(tsp_context *ctx, const float *img, int H, int W, int C, float vmin, float vmax,
@@ -710,16 +733,13 @@ int tsp_colormap_bivariate_host(tsp_context *ctx, const float *img, int H, int W
     TSP_HIP(hipSetDevice(ctx->device));
     const int64_t npix = (int64_t)H * W;
     const size_t in_bytes = (size_t)npix * C * sizeof(float), out_bytes = (size_t)npix * 4;
-    int rc = ensure_scratch(ctx, in_bytes + out_bytes + 256);
+    HostStage hs;
+    int rc = stage_host_image(ctx, in_bytes, out_bytes, 0, hs);
     if (rc) return rc;
-    float *d_in = (float *)ctx->scratch;
-    uint8_t *d_out = (uint8_t *)ctx->scratch + ((in_bytes + 255) & ~(size_t)255);
-    TSP_HIP(hipMemcpyAsync(d_in, img, in_bytes, hipMemcpyHostToDevice, ctx->stream));
-    if ((rc = launch_colormap_bivariate(ctx, d_in, npix, C, vmin, vmax, density_vmin, density_vmax, log_scale, weighted, d_out)))
+    TSP_HIP(hipMemcpyAsync(hs.in, img, in_bytes, hipMemcpyHostToDevice, ctx->stream));
+    if ((rc = launch_colormap_bivariate(ctx, hs.in, npix, C, vmin, vmax, density_vmin, density_vmax, log_scale, weighted, hs.out8)))
         return rc;
-    TSP_HIP(hipMemcpyAsync(out_rgba, d_out, out_bytes, hipMemcpyDeviceToHost, ctx->stream));
-    TSP_HIP(hipStreamSynchronize(ctx->stream));
-    return TSP_OK;
+    return unstage_host_image(ctx, hs, out_rgba, out_bytes, nullptr, 0);
 }
 
 int tsp_colormap_rgb_host(tsp_context *ctx, const float *img, int H, int W, int C, float vmin, float vmax, float gamma,
@@ -728,21 +748,15 @@ int tsp_colormap_rgb_host(tsp_context *ctx, const float *img, int H, int W, int 
     TSP_REQUIRE(H > 0 && W > 0 && C >= 3, TSP_EINVAL, "bad image shape %dx%dx%d", H, W, C);
     TSP_HIP(hipSetDevice(ctx->device));
     const int64_t npix = (int64_t)H * W;
-    const size_t in_bytes = ((size_t)npix * C * sizeof(float) + 255) & ~(size_t)255;
-    const size_t o8 = ((size_t)npix * 4 + 255) & ~(size_t)255, of = (size_t)npix * 16;
-    int rc = ensure_scratch(ctx, in_bytes + o8 + of);
+    const size_t in_bytes = (size_t)npix * C * sizeof(float), o8 = (size_t)npix * 4, of = (size_t)npix * 16;
+    HostStage hs;
+    int rc = stage_host_image(ctx, in_bytes, o8, of, hs);
     if (rc) return rc;
-    float *d_in = (float *)ctx->scratch;
-    uint8_t *d_o8 = (uint8_t *)ctx->scratch + in_bytes;
-    float *d_of = (float *)((uint8_t *)ctx->scratch + in_bytes + o8);
-    TSP_HIP(hipMemcpyAsync(d_in, img, (size_t)npix * C * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
-    if ((rc = launch_colormap_rgb(ctx, d_in, npix, C, vmin, vmax, gamma, out_rgba8 ? d_o8 : nullptr,
-                                  out_rgba_f32 ? d_of : nullptr)))
+    TSP_HIP(hipMemcpyAsync(hs.in, img, in_bytes, hipMemcpyHostToDevice, ctx->stream));
+    if ((rc = launch_colormap_rgb(ctx, hs.in, npix, C, vmin, vmax, gamma, out_rgba8 ? hs.out8 : nullptr,
+                                  out_rgba_f32 ? hs.outf : nullptr)))
         return rc;
-    if (out_rgba8) TSP_HIP(hipMemcpyAsync(out_rgba8, d_o8, (size_t)npix * 4, hipMemcpyDeviceToHost, ctx->stream));
-    if (out_rgba_f32) TSP_HIP(hipMemcpyAsync(out_rgba_f32, d_of, of, hipMemcpyDeviceToHost, ctx->stream));
-    TSP_HIP(hipStreamSynchronize(ctx->stream));
-    return TSP_OK;
+    return unstage_host_image(ctx, hs, out_rgba8, o8, out_rgba_f32, of);
 }
 
 int tsp_smoothing_lengths(tsp_context *ctx, int64_t n, const float *x, const float *y, const float *z, int n_neighbours,
@@ -845,32 +859,10 @@ int tsp_render_surface(tsp_context *ctx, const float *M, float scale_factor, flo
     TSP_REQUIRE(ctx->have_sphere_mips, TSP_ESTATE, "tsp_set_sphere_mips must be called before tsp_render_surface");
     TSP_REQUIRE(clear || ctx->surface_keys, TSP_ESTATE, "clear = 0 continues a surface image; the accumulator holds none");
     TSP_HIP(hipSetDevice(ctx->device));
-    // clip the ranges to [0, n) as tsp_render does
     std::vector<int64_t> s, l;
-    if (!starts) {
-        if (ctx->p.n > 0) { s.push_back(0); l.push_back(ctx->p.n); }
-    } else {
-        for (int i = 0; i < n_ranges; ++i) {
-            TSP_REQUIRE(lens[i] >= 0, TSP_EINVAL, "range %d has negative length %lld", i, (long long)lens[i]);
-            int64_t b = starts[i], len = lens[i];
-            if (b < 0) {
-                len = (len > -b) ? len + b : 0;
-                b = 0;
-            }
-            if (b >= ctx->p.n || len == 0) continue;
-            if (len > ctx->p.n - b) len = ctx->p.n - b;
-            s.push_back(b);
-            l.push_back(len);
-        }
-    }
     int64_t total = 0;
-    for (int64_t v : l) total += v;
-    Camera cam;
-    for (int i = 0; i < 12; ++i) cam.m[i] = M[i];
-    cam.sf = scale_factor;
-    cam.R = ctx->R;
-    cam.Rf = (float)ctx->R;
-    cam.halfR = 0.5f * cam.Rf;
+    if (int rc = clip_ranges(ctx, starts, lens, n_ranges, s, l, &total)) return rc;
+    const Camera cam = make_camera(ctx, M, scale_factor);
     double ms_draw = 0.0, ms_resolve = 0.0;
     const int rc = render_surface(ctx, cam, density_cut, s.data(), l.data(), (int)s.size(), total, clear, &ms_draw, &ms_resolve);
     if (rc) return rc;

@@ -106,16 +106,16 @@ int tsp_comm_reduce_image(tsp_context *ctx, int root, double *gpu_ms_out) {
                 "the render target was already reduced for this frame (call tsp_render before reducing again)");
     TSP_HIP(hipSetDevice(ctx->device));
     const size_t count = (size_t)ctx->R * ctx->R * ctx->C;
-    TSP_HIP(hipEventRecord(ctx->ev[4], ctx->stream));
+    TSP_HIP(hipEventRecord(ctx->ev[EV_T4], ctx->stream));
     if (root < 0)
         TSP_NCCL(g_rccl.AllReduce(ctx->image, ctx->image, count, ncclFloat, ncclSum, (ncclComm_t)ctx->comm, ctx->stream));
     else
         TSP_NCCL(g_rccl.Reduce(ctx->image, ctx->image, count, ncclFloat, ncclSum, root, (ncclComm_t)ctx->comm, ctx->stream));
-    TSP_HIP(hipEventRecord(ctx->ev[5], ctx->stream));
+    TSP_HIP(hipEventRecord(ctx->ev[EV_T5], ctx->stream));
     TSP_HIP(hipStreamSynchronize(ctx->stream));
     ctx->image_is_reduced = true;
     float ms = 0.f;
-    TSP_HIP(hipEventElapsedTime(&ms, ctx->ev[4], ctx->ev[5]));
+    TSP_HIP(hipEventElapsedTime(&ms, ctx->ev[EV_T4], ctx->ev[EV_T5]));
     if (gpu_ms_out) *gpu_ms_out = ms;
     return TSP_OK;
 }

@@ -579,13 +579,13 @@ int measure_read_bandwidth(tsp_context *ctx, int64_t bytes, int iters, double *g
             else hipLaunchKernelGGL((read_sum_kernel<8, true>), dim3(grid), dim3(256), 0, ctx->stream, buf, bytes / 16, sink);
         };
         launch();
-        TSP_HIP(hipEventRecord(ctx->ev[2], ctx->stream));
+        TSP_HIP(hipEventRecord(ctx->ev[EV_T2], ctx->stream));
         for (int it = 0; it < iters; ++it) launch();
-        TSP_HIP(hipEventRecord(ctx->ev[3], ctx->stream));
+        TSP_HIP(hipEventRecord(ctx->ev[EV_T3], ctx->stream));
         TSP_HIP(hipStreamSynchronize(ctx->stream));
         TSP_HIP(hipGetLastError());
         float ms = 0.f;
-        TSP_HIP(hipEventElapsedTime(&ms, ctx->ev[2], ctx->ev[3]));
+        TSP_HIP(hipEventElapsedTime(&ms, ctx->ev[EV_T2], ctx->ev[EV_T3]));
         best = std::max(best, (double)bytes * iters / (ms * 1e-3) / 1e9);
     }
     *gbps_out = best;

@@ -93,6 +93,24 @@ struct Workspace {     // per-context scratch of the three-class pipeline (grown
     int count_R = 0;                    // resolution count_diff / count_band are sized for (0: not allocated)
 };
 
+// The context's timing events by what they delimit.  A render block (run_pipeline, inside tsp_render's pair) marks its kernels;
+// every other call that times itself uses the neutral EV_T* marks, which share the first events: such calls never run inside
+// a render block.
+enum {
+    EV_RENDER_BEGIN, EV_RENDER_END,         // tsp_render: the whole call
+    EV_S_BEGIN, EV_S_END,                   // kernel S (every attempt records them: the last one counts)
+    EV_MID_BEGIN, EV_MID_END,               // kernels N and G, on their stream (EV_MID_END is also what `stream` waits for when they overlap H2)
+    EV_BLOCK_END,                           // after the last launch of the block
+    EV_CULL_BEGIN,                          // before the culling passes: kernel S's time starts here when they run
+    EV_S_DONE,                              // overlap_mid_huge: what the second stream waits for
+    EV_HUGE_BEGIN, EV_HUGE_END,             // kernel H2 (its launcher records EV_HUGE_END again after every launch)
+    EV_COUNT,
+    EV_T0 = 0, EV_T1, EV_T2, EV_T3, EV_T4, EV_T5      // call-local marks (tsp_surface / tsp_present / tsp_data / tsp_comm)
+};
+// bits of tsp_context::kernel_attr_done
+constexpr uint32_t attr_bit_stream(int mode) { return 1u << mode; }          // kernel S of a mode
+constexpr uint32_t attr_bit_bins(int nw) { return 1u << (8 + nw); }          // the strip-bin passes by weight floats per record
+
 }  // namespace tsp
 
 struct tsp_context {
@@ -101,7 +119,7 @@ struct tsp_context {
     bool use_quantity = true;
     hipStream_t stream = nullptr;
     hipStream_t stream2 = nullptr;    // option overlap_mid_huge: kernel G runs here, concurrently with kernel H2 on `stream`
-    hipEvent_t ev[12] = {};
+    hipEvent_t ev[tsp::EV_COUNT] = {};    // indexed by the EV_* names above
     float *image = nullptr;           // R*R*C float32 render target (what read-back, colormap and reduce see)
     double *image64 = nullptr;        // float64 master copy every kernel accumulates into (rounded once per render)
     double *image64_entry = nullptr;  // image64 as tsp_render found it: what a failed block puts back (the call draws all of a block or none of it)
@@ -138,7 +156,7 @@ struct tsp_context {
     float p_small = 16.0f;             // footprints narrower than this many pixels are splatted by kernel S (mips 3 and 2; <= 16: its texel columns are packed 16 x 4 bits)
     int64_t huge_band_budget = 6ll << 30;   // bytes the band bins of the huge records may take (n_bands x n_huge records); above it kernel H2 scans one list
     int huge_variant = 1;             // kernel H2's strip shape / occupancy: 1 = auto (density: 64x32 strips at 8 waves/SIMD from 7e5 records, 64x16 below; two channels 64x16 at 7; rgb at 5), 2 / 4-7 = A/B builds
-    int h2_walk = 1;                  // kernel H2's row walk in the single-channel 8-waves/SIMD builds: 1 = hand-allocated asm (tsp_gather.hip), 0 = the C++ walk (A/B and parity)
+    int h2_walk = 1;                  // kernel H2's row walk in the single-channel 8-waves/SIMD builds: 1 = hand-allocated asm (tsp_huge.hip), 0 = the C++ walk (A/B and parity)
     int huge_split = 0;              // workgroups per image tile of kernel H2 (0 = auto)
     int reorder_interleave = 2;     // tsp_reorder_spatial's arrangement inside every 512-particle block: 0 Morton order, 1 transposed 64 x 8, 2 by descending smoothing length (tsp_data.hip)
     int stream_blocks_per_cu = 0;    // kernel S: persistent workgroups per CU (0 = what the occupancy query reports)

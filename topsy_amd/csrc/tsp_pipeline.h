@@ -1,6 +1,8 @@
 // tsp_pipeline.h -- what the translation units of the splat pipeline share: tile constants, the float64 atomic helpers,
-// the argument block of the tile kernels, and the launcher of the tile-gather kernels (tsp_gather.hip).
+// the argument block of the tile kernels, and the launchers of the tile-gather kernels (tsp_huge.hip, tsp_mid.hip).
 #pragma once
+#include <type_traits>
+
 #include "tsp_internal.h"
 
 namespace tsp {
@@ -49,13 +51,34 @@ __device__ __forceinline__ int mipq_offset(int lvl) { return lvl == 0 ? 0 : (lvl
 
 // DPP modifier: every lane reads the operand from lane t of its own quad
 #define TSP_DPP_QUAD(t) "quad_perm:[" #t "," #t "," #t "," #t "] row_mask:0xf bank_mask:0xf"
+// the FMAs of the strip walks of kernels H2, N and G (tsp_huge.hip, tsp_mid.hip): a row factor as the DPP operand / in place
+template <int T> __device__ __forceinline__ void fmac_quad(float &acc, float rowval, float v) {
+    static_assert(T >= 0 && T < 4, "quad lane");
+    if (T == 0) asm volatile("v_fmac_f32_dpp %0, %1, %2 " TSP_DPP_QUAD(0) : "+v"(acc) : "v"(rowval), "v"(v));
+    if (T == 1) asm volatile("v_fmac_f32_dpp %0, %1, %2 " TSP_DPP_QUAD(1) : "+v"(acc) : "v"(rowval), "v"(v));
+    if (T == 2) asm volatile("v_fmac_f32_dpp %0, %1, %2 " TSP_DPP_QUAD(2) : "+v"(acc) : "v"(rowval), "v"(v));
+    if (T == 3) asm volatile("v_fmac_f32_dpp %0, %1, %2 " TSP_DPP_QUAD(3) : "+v"(acc) : "v"(rowval), "v"(v));
+}
+template <int T> __device__ __forceinline__ float mul_quad(float rowval, float v) {
+    float r;
+    if (T == 0) asm volatile("v_mul_f32_dpp %0, %1, %2 " TSP_DPP_QUAD(0) : "=v"(r) : "v"(rowval), "v"(v));
+    if (T == 1) asm volatile("v_mul_f32_dpp %0, %1, %2 " TSP_DPP_QUAD(1) : "=v"(r) : "v"(rowval), "v"(v));
+    if (T == 2) asm volatile("v_mul_f32_dpp %0, %1, %2 " TSP_DPP_QUAD(2) : "=v"(r) : "v"(rowval), "v"(v));
+    if (T == 3) asm volatile("v_mul_f32_dpp %0, %1, %2 " TSP_DPP_QUAD(3) : "=v"(r) : "v"(rowval), "v"(v));
+    return r;
+}
+__device__ __forceinline__ void fmac_plain(float &acc, float x, float y) {     // tied operand: the accumulator stays in place
+    asm volatile("v_fmac_f32_e32 %0, %1, %2" : "+v"(acc) : "v"(x), "v"(y));
+}
+
+constexpr int H2T = 256;             // threads per workgroup of kernels H2, N and G: 4 waves (H2: 2 x 2 strips sharing one pair table)
 
 __device__ __forceinline__ void latomic_add(double *addr, float v) {
     __hip_atomic_fetch_add(addr, (double)v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
 }
 
 #ifndef TSP_FOLD_EVERY
-#define TSP_FOLD_EVERY 2048    // footprints a float32 accumulator of kernels G / H2 holds before it goes to the float64 target (512 until the end of round 5)
+#define TSP_FOLD_EVERY 2048    // footprints a float32 accumulator of kernels N / G / H2 holds before it goes to the float64 target (512 until the end of round 5)
 #endif
 #ifndef TSP_HDEAL
 #define TSP_HDEAL 16
@@ -74,19 +97,36 @@ struct TileArgs {
     float disc_k2;     // (0.5235)^2 when the LUT is zero outside the inscribed disc (exact corner culling), else 0
     // kernel H2: the huge records binned by image band (huge_band_fill_kernel): band b (rows [b, b + 1) * HBAND_H) holds
     // hband_count[b] records at geom + b * hband_stride (w likewise); nullptr = one list for every tile (geom, n_records)
-    // (kernel G: exact-size bins, band b starts at record hband_base[b])
+    // (kernels N and G: exact-size bins, band b starts at record hband_base[b])
     const int *hband_count; long long hband_stride; const long long *hband_base;
-    // kernel G: the mid records binned by tile (hband_count[t] records from record hband_base[t] on); workgroup i draws work item i =
+    // kernels N and G: the mid records binned by tile (hband_count[t] records from record hband_base[t] on); workgroup i draws work item i =
     // GCHUNK consecutive records of tile item_tile[i]'s bin (that tile's items start at item_base[tile]; item_base[n_tiles] = their number)
     int n_tiles; const int *item_tile; const int *item_base; int item_records;      // item_records: records per work item (a power of two)
 };
 
-// Kernel H2 (tsp_gather.hip) for the footprints >= 64 px of one render block (the records kernel S appended to the huge list).
-// Records ctx->ev[10] after the launch (per-kernel time: ev[9] .. ev[10]).
+// A run-time flag / mode as a compile-time constant: f receives std::true_type or std::false_type (a std::integral_constant of
+// the mode) and names its template arguments with decltype(x)::value.  with_bool<false> passes false_type whatever the flag:
+// for a variant that is not built.
+template <bool BUILT = true, class F> auto with_bool(bool b, F &&f) {
+    if constexpr (BUILT) { if (b) return f(std::true_type{}); }
+    return f(std::false_type{});
+}
+template <class F> int with_mode(int mode, F &&f) {
+    switch (mode) {
+        case TSP_MODE_WEIGHTED: return f(std::integral_constant<int, TSP_MODE_WEIGHTED>{});
+        case TSP_MODE_DEPTH: return f(std::integral_constant<int, TSP_MODE_DEPTH>{});
+        case TSP_MODE_RGB: return f(std::integral_constant<int, TSP_MODE_RGB>{});
+    }
+    set_error("bad mode %d", mode);
+    return TSP_EINVAL;
+}
+
+// Kernel H2 (tsp_huge.hip) for the footprints >= 64 px of one render block (the records kernel S appended to the huge list).
+// Records EV_HUGE_END after the launch (per-kernel time: EV_HUGE_BEGIN .. EV_HUGE_END).
 int launch_gather_kernels(tsp_context *ctx, TileArgs ta, int mode, bool second_channel, const float4 *huge_geom, const float *huge_w,
                           long long n_huge);
 
-// Kernel G (tsp_gather.hip): the MID records of one render block as a register gather; launched on `st`.
+// Kernels N and G (tsp_mid.hip): the MID records of one render block as a register gather; launched on `st`.
 int launch_mid_gather(tsp_context *ctx, TileArgs ta, int mode, bool second_channel, const float4 *mid_geom, const float *mid_w,
                       long long n_mid, hipStream_t st);
 

@@ -13,9 +13,9 @@
 //             are rasterised at once (ds_add_f64), flushed with one global atomic per touched
 //             pixel.  All other footprints are not rasterised here: their projected records
 //             (pcx, pcy, P, weights) are appended to the MID list or the HUGE list (P >= 64 px).
-//   kernel G  (tsp_gather.hip) draws the MID list (nearest sampling): the records binned per 64-px
+//   kernel G  (tsp_mid.hip) draws the MID list (nearest sampling): the records binned per 64-px
 //             pixel strip, equal work items, one per wave, accumulators in registers.
-//   kernel H2 (tsp_gather.hip) takes the footprints >= 64 px (bilinear sampling): per-wave pixel strips held in
+//   kernel H2 (tsp_huge.hip) takes the footprints >= 64 px (bilinear sampling): per-wave pixel strips held in
 //             registers, records scanned per wave, no atomics in the loop.
 //
 // All of them add into the float64 render target with device-scope atomics only at flush time.
@@ -840,10 +840,10 @@ static int run_pipeline(tsp_context *ctx, const Camera &cam, const int64_t *h_st
     const int WCr = (MODE == TSP_MODE_RGB) ? 4 : (second_channel ? 2 : 1);
     const int WIN = (WCr == 1) ? WinSize<1>::value : WinSize<C>::value;
     const size_t smem_s = (size_t)WCr * WIN * WIN * sizeof(double) + T23_FLOATS * sizeof(float);
-    if (!(ctx->kernel_attr_done & (1u << MODE))) {
+    if (!(ctx->kernel_attr_done & attr_bit_stream(MODE))) {
         TSP_HIP(hipFuncSetAttribute((const void *)splat_stream_kernel<MODE, C>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)((size_t)C * WinSize<C>::value * WinSize<C>::value * sizeof(double) + T23_FLOATS * sizeof(float))));
         TSP_HIP(hipFuncSetAttribute((const void *)splat_stream_kernel<MODE, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)((size_t)WinSize<1>::value * WinSize<1>::value * sizeof(double) + T23_FLOATS * sizeof(float))));
-        ctx->kernel_attr_done |= 1u << MODE;
+        ctx->kernel_attr_done |= attr_bit_stream(MODE);
     }
 
     // Chunk culling (option chunk_cull, on by default): one small kernel lists the chunks whose bounds can reach the view; kernel S
@@ -852,7 +852,7 @@ static int run_pipeline(tsp_context *ctx, const Camera &cam, const int64_t *h_st
     const bool cull = ctx->chunk_cull && n_chunks >= 4096;
     unsigned long long cull_info_h[2] = {0, 0};
     ctx->chunk_culled_particles = 0;
-    TSP_HIP(hipEventRecord(ctx->ev[7], st));      // (the culling passes, and the block bounds when they are stale, count as kernel S's time)
+    TSP_HIP(hipEventRecord(ctx->ev[EV_CULL_BEGIN], st));      // (the culling passes, and the block bounds when they are stale, count as kernel S's time)
     if (cull) {
         if ((rc = ensure_block_bounds(ctx))) return rc;
         if (!ws.cull_info && (rc = alloc_group(ctx, {{"cull_info", (void **)&ws.cull_info, 2 * sizeof(unsigned long long)}}, {}))) return rc;
@@ -898,11 +898,11 @@ static int run_pipeline(tsp_context *ctx, const Camera &cam, const int64_t *h_st
         sa.cnt = ctx->counters; sa.p_small = ctx->p_small;
         sa.count_frag = ctx->count_fragments ? 1 : 0;
         sa.emit_small = (attempt == 0 && !ctx->debug_no_raster) ? 1 : 0;
-        TSP_HIP(hipEventRecord(ctx->ev[2], st));
+        TSP_HIP(hipEventRecord(ctx->ev[EV_S_BEGIN], st));
         if (WCr == 1) hipLaunchKernelGGL((splat_stream_kernel<MODE, 1>), dim3(grid_s), dim3(SBLOCK), smem_s, st, sa);
         else hipLaunchKernelGGL((splat_stream_kernel<MODE, C>), dim3(grid_s), dim3(SBLOCK), smem_s, st, sa);
         TSP_HIP(hipGetLastError());
-        TSP_HIP(hipEventRecord(ctx->ev[3], st));
+        TSP_HIP(hipEventRecord(ctx->ev[EV_S_END], st));
         // the record counts size the two tile launches (and reveal a list overflow)
         TSP_HIP(hipMemcpyAsync(&hc, ctx->counters, sizeof(hc), hipMemcpyDeviceToHost, st));
         if (cull && attempt == 0) TSP_HIP(hipMemcpyAsync(cull_info_h, ws.cull_info, sizeof(cull_info_h), hipMemcpyDeviceToHost, st));
@@ -940,8 +940,8 @@ static int run_pipeline(tsp_context *ctx, const Camera &cam, const int64_t *h_st
     // two streams (no gain measured: both are bound by the vector units).
     hipStream_t st_mid = ctx->overlap_mid_huge ? ctx->stream2 : st;
     if (ctx->overlap_mid_huge) {
-        TSP_HIP(hipEventRecord(ctx->ev[8], st));
-        TSP_HIP(hipStreamWaitEvent(st_mid, ctx->ev[8], 0));
+        TSP_HIP(hipEventRecord(ctx->ev[EV_S_DONE], st));
+        TSP_HIP(hipStreamWaitEvent(st_mid, ctx->ev[EV_S_DONE], 0));
     }
     if ((rc = check_workspace(ctx))) return rc;
     if (ctx->debug_fail_stage == 1) { ctx->debug_fail_stage = 0; TSP_REQUIRE(false, TSP_ENOMEM, "injected failure after kernel S (debug_fail_stage)"); }
@@ -953,17 +953,17 @@ static int run_pipeline(tsp_context *ctx, const Camera &cam, const int64_t *h_st
     const long long huge_slice = ctx->slice_records > 0 ? ctx->slice_records : (1ll << 30);
     const float4 *mid_geom = (const float4 *)ws.mid_geom, *huge_geom = (const float4 *)ws.huge_geom;
     const float *mid_w = (const float *)ws.mid_w, *huge_w = (const float *)ws.huge_w;
-    TSP_HIP(hipEventRecord(ctx->ev[4], st_mid));
+    TSP_HIP(hipEventRecord(ctx->ev[EV_MID_BEGIN], st_mid));
     for (long long o = 0; o < n_mid; o += mid_slice)
         if ((rc = launch_mid_gather(ctx, ta, MODE, second_channel, mid_geom + o, mid_w + o * NWr, std::min(mid_slice, n_mid - o), st_mid))) return rc;
-    TSP_HIP(hipEventRecord(ctx->ev[5], st_mid));
+    TSP_HIP(hipEventRecord(ctx->ev[EV_MID_END], st_mid));
     if (ctx->debug_fail_stage == 2) { ctx->debug_fail_stage = 0; TSP_REQUIRE(false, TSP_ENOMEM, "injected failure after kernel G (debug_fail_stage)"); }
-    TSP_HIP(hipEventRecord(ctx->ev[9], st));
-    TSP_HIP(hipEventRecord(ctx->ev[10], st));      // (kernel H2's launcher records it again after its launch)
+    TSP_HIP(hipEventRecord(ctx->ev[EV_HUGE_BEGIN], st));
+    TSP_HIP(hipEventRecord(ctx->ev[EV_HUGE_END], st));      // (kernel H2's launcher records it again after its launch)
     for (long long o = 0; o < n_huge; o += huge_slice)
         if ((rc = launch_gather_kernels(ctx, ta, MODE, second_channel, huge_geom + o, huge_w + o * NWr, std::min(huge_slice, n_huge - o)))) return rc;
     if (MODE == TSP_MODE_RGB && (n_mid > 0 || n_huge > 0)) {
-        if (ctx->overlap_mid_huge) TSP_HIP(hipStreamWaitEvent(st, ctx->ev[5], 0));
+        if (ctx->overlap_mid_huge) TSP_HIP(hipStreamWaitEvent(st, ctx->ev[EV_MID_END], 0));
         // (the rectangle counts are 32-bit: one pass while both lists are single slices, else one pass per slice)
         if (n_mid <= mid_slice && n_huge <= huge_slice) {
             if ((rc = add_rect_counts(ctx, mid_geom, n_mid, huge_geom, n_huge))) return rc;
@@ -974,26 +974,20 @@ static int run_pipeline(tsp_context *ctx, const Camera &cam, const int64_t *h_st
                 if ((rc = add_rect_counts(ctx, nullptr, 0, huge_geom + o, std::min(huge_slice, n_huge - o)))) return rc;
         }
     }
-    TSP_HIP(hipEventRecord(ctx->ev[6], st));
-    if (ctx->overlap_mid_huge) TSP_HIP(hipStreamWaitEvent(st, ctx->ev[5], 0));     // join: later work on `st` sees both
+    TSP_HIP(hipEventRecord(ctx->ev[EV_BLOCK_END], st));
+    if (ctx->overlap_mid_huge) TSP_HIP(hipStreamWaitEvent(st, ctx->ev[EV_MID_END], 0));     // join: later work on `st` sees both
     TSP_HIP(hipStreamSynchronize(st));
     float ms = 0.f;
-    TSP_HIP(hipEventElapsedTime(&ms, ctx->ev[cull ? 7 : 2], ctx->ev[3])); ctx->stats.ms_stream = ms;
-    TSP_HIP(hipEventElapsedTime(&ms, ctx->ev[4], ctx->ev[5])); ctx->stats.ms_mid = ms;
-    TSP_HIP(hipEventElapsedTime(&ms, ctx->ev[9], ctx->ev[10])); ctx->stats.ms_huge = ms;
+    TSP_HIP(hipEventElapsedTime(&ms, ctx->ev[cull ? EV_CULL_BEGIN : EV_S_BEGIN], ctx->ev[EV_S_END])); ctx->stats.ms_stream = ms;
+    TSP_HIP(hipEventElapsedTime(&ms, ctx->ev[EV_MID_BEGIN], ctx->ev[EV_MID_END])); ctx->stats.ms_mid = ms;
+    TSP_HIP(hipEventElapsedTime(&ms, ctx->ev[EV_HUGE_BEGIN], ctx->ev[EV_HUGE_END])); ctx->stats.ms_huge = ms;
     ctx->stats.ms_mega = 0.0;
     return TSP_OK;
 }
 
 int launch_pipeline(tsp_context *ctx, const Camera &cam, const int64_t *h_starts, const int64_t *h_lens, int n_ranges,
                     int64_t total, int mode) {
-    switch (mode) {
-        case TSP_MODE_WEIGHTED: return run_pipeline<TSP_MODE_WEIGHTED>(ctx, cam, h_starts, h_lens, n_ranges, total);
-        case TSP_MODE_DEPTH: return run_pipeline<TSP_MODE_DEPTH>(ctx, cam, h_starts, h_lens, n_ranges, total);
-        case TSP_MODE_RGB: return run_pipeline<TSP_MODE_RGB>(ctx, cam, h_starts, h_lens, n_ranges, total);
-    }
-    set_error("bad mode %d", mode);
-    return TSP_EINVAL;
+    return with_mode(mode, [&](auto M) { return run_pipeline<decltype(M)::value>(ctx, cam, h_starts, h_lens, n_ranges, total); });
 }
 
 }  // namespace tsp

@@ -437,7 +437,7 @@ int present(tsp_context *ctx, int W, int H, const tsp_present_base &base, const 
     b.weighted = base.weighted ? 1 : 0;
 
     const dim3 grid((unsigned)((W + 63) / 64), (unsigned)((H + 3) / 4));
-    TSP_HIP(hipEventRecord(ctx->ev[3], st));
+    TSP_HIP(hipEventRecord(ctx->ev[EV_T3], st));
     if (hdr)
         hipLaunchKernelGGL(present_kernel<true>, grid, dim3(256), 0, st, b, d_prims.as<PresentPrim>(), (int)prims.size(),
                            d_tex.as<float4>(), d_frame.p);
@@ -458,13 +458,13 @@ int present(tsp_context *ctx, int W, int H, const tsp_present_base &base, const 
                                d_yuv.as<uint8_t>());
         TSP_HIP(hipGetLastError());
     }
-    TSP_HIP(hipEventRecord(ctx->ev[4], st));
+    TSP_HIP(hipEventRecord(ctx->ev[EV_T4], st));
     TSP_HIP(hipStreamSynchronize(st));      // the frame is complete before anything of the caller's is written
     TSP_HIP(hipMemcpyAsync(out, yuv420 ? d_yuv.p : d_frame.p, out_bytes, hipMemcpyDeviceToHost, st));
     TSP_HIP(hipStreamSynchronize(st));
     if (gpu_ms_out) {
         float ms = 0.f;
-        TSP_HIP(hipEventElapsedTime(&ms, ctx->ev[3], ctx->ev[4]));
+        TSP_HIP(hipEventElapsedTime(&ms, ctx->ev[EV_T3], ctx->ev[EV_T4]));
         *gpu_ms_out = ms;
     }
     return TSP_OK;

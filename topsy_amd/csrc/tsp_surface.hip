@@ -183,7 +183,7 @@ int render_surface(tsp_context *ctx, const Camera &cam, float cut, const int64_t
     TSP_HIP(hipMemcpyAsync(d_ranges.p, pack.data(), pack.size() * sizeof(int64_t), hipMemcpyHostToDevice, st));
     TSP_HIP(hipMemsetAsync(d_count.p, 0, sizeof(unsigned long long), st));
     unsigned long long *keys = reinterpret_cast<unsigned long long *>(ctx->image64);
-    TSP_HIP(hipEventRecord(ctx->ev[0], st));
+    TSP_HIP(hipEventRecord(ctx->ev[EV_T0], st));
     if (clear) TSP_HIP(hipMemsetAsync(keys, 0, (size_t)npix * sizeof(unsigned long long), st));
     Particles parts = ctx->p;
     if (!ctx->use_quantity) parts.q = nullptr;
@@ -194,18 +194,18 @@ int render_surface(tsp_context *ctx, const Camera &cam, float cut, const int64_t
                            cut, sphere, keys, d_count.as<unsigned long long>());
         TSP_HIP(hipGetLastError());
     }
-    TSP_HIP(hipEventRecord(ctx->ev[1], st));
+    TSP_HIP(hipEventRecord(ctx->ev[EV_T1], st));
     const unsigned pgrid = (unsigned)std::min<int64_t>((npix + 255) / 256, (int64_t)ctx->cu_count * 16);
     hipLaunchKernelGGL(surface_resolve_kernel, dim3(pgrid), dim3(256), 0, st, parts, cam, cut, sphere,
                        (const unsigned long long *)keys, reinterpret_cast<float2 *>(ctx->image));
     TSP_HIP(hipGetLastError());
-    TSP_HIP(hipEventRecord(ctx->ev[2], st));
+    TSP_HIP(hipEventRecord(ctx->ev[EV_T2], st));
     unsigned long long drawn = 0;
     TSP_HIP(hipMemcpyAsync(&drawn, d_count.p, sizeof(drawn), hipMemcpyDeviceToHost, st));
     TSP_HIP(hipStreamSynchronize(st));
     float a = 0.f, b = 0.f;
-    TSP_HIP(hipEventElapsedTime(&a, ctx->ev[0], ctx->ev[1]));
-    TSP_HIP(hipEventElapsedTime(&b, ctx->ev[1], ctx->ev[2]));
+    TSP_HIP(hipEventElapsedTime(&a, ctx->ev[EV_T0], ctx->ev[EV_T1]));
+    TSP_HIP(hipEventElapsedTime(&b, ctx->ev[EV_T1], ctx->ev[EV_T2]));
     *ms_draw = a;
     *ms_resolve = b;
     ctx->stats = tsp_stats{};
@@ -393,12 +393,12 @@ int surface_present(tsp_context *ctx, const tsp_surface_params &prm, float *cont
     const size_t lds = (size_t)(W * W + nk * nk) * sizeof(float);
     if (lds > 65536)     // (at most 94.6 KB: half <= 50)
         TSP_HIP(hipFuncSetAttribute((const void *)bilateral_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    TSP_HIP(hipEventRecord(ctx->ev[3], st));
+    TSP_HIP(hipEventRecord(ctx->ev[EV_T3], st));
     const unsigned tiles = (unsigned)((R + FT - 1) / FT);
     hipLaunchKernelGGL(bilateral_kernel, dim3(tiles, tiles), dim3(256), lds, st, reinterpret_cast<const float2 *>(ctx->image),
                        filtered.as<float2>(), R, half, ss, rs);
     TSP_HIP(hipGetLastError());
-    TSP_HIP(hipEventRecord(ctx->ev[4], st));
+    TSP_HIP(hipEventRecord(ctx->ev[EV_T4], st));
     if (rgba8_out) {
         ShadeParams sp;
         sp.depth_scale = prm.depth_scale;
@@ -418,14 +418,14 @@ int surface_present(tsp_context *ctx, const tsp_surface_params &prm, float *cont
                            reinterpret_cast<uint32_t *>(ctx->out8));
         TSP_HIP(hipGetLastError());
     }
-    TSP_HIP(hipEventRecord(ctx->ev[5], st));
+    TSP_HIP(hipEventRecord(ctx->ev[EV_T5], st));
     if (content_out) TSP_HIP(hipMemcpyAsync(content_out, filtered.p, (size_t)npix * sizeof(float2), hipMemcpyDeviceToHost, st));
     if (rgba8_out) TSP_HIP(hipMemcpyAsync(rgba8_out, ctx->out8, (size_t)npix * 4, hipMemcpyDeviceToHost, st));
     TSP_HIP(hipStreamSynchronize(st));
     if (ms_out) {
         float a = 0.f, b = 0.f;
-        TSP_HIP(hipEventElapsedTime(&a, ctx->ev[3], ctx->ev[4]));
-        TSP_HIP(hipEventElapsedTime(&b, ctx->ev[4], ctx->ev[5]));
+        TSP_HIP(hipEventElapsedTime(&a, ctx->ev[EV_T3], ctx->ev[EV_T4]));
+        TSP_HIP(hipEventElapsedTime(&b, ctx->ev[EV_T4], ctx->ev[EV_T5]));
         ms_out[0] = a;
         ms_out[1] = b;
     }
