@@ -83,7 +83,9 @@ const char *tsp_last_error(void);
  * 108: frame composition: tsp_present and the structs tsp_present_base / tsp_present_layer; nothing else changed.
  * 109: movie frames: tsp_present_yuv420 (the tsp_present frame as I420 planes); nothing else changed.
  * 110: new entry point tsp_sph_sum (gather-form SPH sums: densities for snapshots that carry none); nothing else changed.
- * 111: new entry point tsp_content_neg_inf (how many content values of the last tsp_content_sort were -inf); nothing else changed. */
+ * 111: new entry point tsp_content_neg_inf (how many content values of the last tsp_content_sort were -inf); nothing else changed.
+ * 112: surface frames: tsp_present_surface and tsp_present_surface_yuv420 (the lit surface composed onto a canvas of any size under
+ * the layers of tsp_present, and that frame as I420 planes); no struct changed, nothing else changed. */
 int tsp_version(void);
 int tsp_stats_size(void);
 
@@ -407,6 +409,47 @@ int tsp_present(tsp_context *ctx, int width, int height, const tsp_present_base 
  * as tsp_present, plus the planes.  gpu_ms_out (or NULL): GPU time of the composition and the conversion together. */
 int tsp_present_yuv420(tsp_context *ctx, int width, int height, const tsp_present_base *base, const tsp_present_layer *layers,
                        int n_layers, uint8_t *out, double *gpu_ms_out);
+
+/* tsp_present_surface: the surface map as the base of a composed frame -- what the reference draws in render_mode "surface", where
+ * ColorAsSurfaceMap is one more colormap pass onto the canvas, under the same overlays (visualizer.py:367-384, 396;
+ * colormap/surface.py:357-365; shaders/surface.wgsl:28-123).  The active image must be the 2-channel (q, depth) image of
+ * tsp_render_surface.  Float32 throughout, the operations in the order written, no fused multiply-adds; restated in numpy by
+ * tests/surface_present_ref.py.
+ *
+ * Filtered image.  F is the bilaterally filtered 2-channel image exactly as tsp_surface_present computes it (same ss, rs, kernel
+ * size, bits), held in device memory for the call only.
+ *
+ * Canvas geometry.  S, k, ox, oy, xc, yc, ax, ay are those of "Frame composition".  sample(x, y) is that section's base-layer rule
+ * applied to both channels of F at the texel-space coordinates (x, y): for k <= 1 the linear rule (tx = x - 0.5f, ty = y - 0.5f,
+ * its lerp with the f == 0 case, clamp-to-edge), for k > 1 F[clamp((int)floorf(y), 0, R-1)][clamp((int)floorf(x), 0, R-1)].
+ *
+ * Sample spacing.  The reference's texelSize is (1 / W, 1 / H) of the canvas in texture coordinates, and one texture coordinate is
+ * R texels, so with du = (float)R / (float)W and dv = (float)R / (float)H:
+ *     c = sample(ax, ay),  l = sample(ax - du, ay),  r = sample(ax + du, ay),  u = sample(ax, ay - dv),  d = sample(ax, ay + dv),
+ *     Dc = c.depth * depth_scale, and Dl, Dr, Du, Dd alike.
+ *
+ * Normal and lighting.  n = normalize(-((Dr - Dl) * 0.5f), -((Dd - Du) * 0.5f), 1.0f / (float)W); its length, the division of each
+ * component by it, n.L, max(n.L, 0), the material from c.q (log scale, NaN -> 0, the LUT lerp), (diffuse + ambient) *
+ * (clamp(Dc, 0, 0.5) * 2), alpha 1 and the rounding to bytes are exactly the shading of tsp_surface_present.
+ *
+ * Identity.  At W = H = R: k = 1, du = dv = 1, every tx and ty is an integer, the lerp returns the texel itself and clamp-to-edge
+ * is the neighbour clamp of the shading, so without layers the frame is tsp_surface_present's rgba8_out bit for bit.
+ *
+ * Layers, blending, per-primitive quantisation and limits are those of tsp_present on the rgba8unorm canvas; out_rgba8 is
+ * H x W x 4 uint8.  tsp_present_surface_yuv420 converts that frame as tsp_present_yuv420 does (even W, H in [2, 16384]); out is
+ * W * H * 3 / 2 bytes.
+ *
+ * TSP_EINVAL, nothing written, wherever tsp_surface_present or tsp_present refuse -- the active image is not 2-channel,
+ * smoothing_scale is not finite, weighted_average without a LUT of 2..65536 entries, the canvas or layer limits -- and when
+ * depth_scale, a component of light_direction, light_color or ambient_color, or (with weighted_average) vmin or vmax is not
+ * finite.  A failed call leaves the accumulator, the presentation image and `out` untouched; a successful one leaves the image
+ * and the accumulator unchanged.  Per-call device memory as tsp_present, plus F (8 bytes per pixel of the image) and the LUT
+ * (TSP_ENOMEM on failure).  ms_out (or NULL): two values, the GPU milliseconds of the filter and of the composition (for
+ * tsp_present_surface_yuv420: the composition and the conversion together). */
+int tsp_present_surface(tsp_context *ctx, int width, int height, const tsp_surface_params *params, const tsp_present_layer *layers,
+                        int n_layers, uint8_t *out_rgba8, double *ms_out);
+int tsp_present_surface_yuv420(tsp_context *ctx, int width, int height, const tsp_surface_params *params,
+                               const tsp_present_layer *layers, int n_layers, uint8_t *out, double *ms_out);
 
 /* On-device autorange support (replaces the image read-back + host
  * np.percentile of Colormap.autorange_vmin_vmax / _autorange_using_values, reference

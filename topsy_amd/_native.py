@@ -16,7 +16,7 @@ MODE_WEIGHTED, MODE_DEPTH, MODE_RGB = 0, 1, 2
 PIPE_DEFAULT, PIPE_GENERIC = 0, 1
 SAMPLE_BILINEAR_MIP0, SAMPLE_BILINEAR_MIP = 0x10, 0x20      # diagnostic sampling rules (generic kernel)
 UNIQUE_ID_BYTES = 128
-ABI_VERSION = 111            # include/topsy_splat.h: tsp_version()
+ABI_VERSION = 112            # include/topsy_splat.h: tsp_version()
 PRESENT_SCALAR, PRESENT_BIVARIATE, PRESENT_RGB, PRESENT_RGB_HDR = 0, 1, 2, 3
 LAYER_QUAD, LAYER_LINES = 0, 1
 
@@ -120,6 +120,10 @@ SIGNATURES = {
                                    ctypes.POINTER(ctypes.c_double)]),
     "tsp_present_yuv420": (ctypes.c_int, [_ctx, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, _u8p,
                                           ctypes.POINTER(ctypes.c_double)]),
+    "tsp_present_surface": (ctypes.c_int, [_ctx, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, _u8p,
+                                           ctypes.POINTER(ctypes.c_double)]),
+    "tsp_present_surface_yuv420": (ctypes.c_int, [_ctx, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
+                                                  _u8p, ctypes.POINTER(ctypes.c_double)]),
     "tsp_content_sort": (ctypes.c_int, [_ctx, ctypes.c_int, ctypes.c_float, _i64p, _i64p]),
     "tsp_content_values": (ctypes.c_int, [_ctx, _i64p, ctypes.c_int, _fp]),
     "tsp_content_neg_inf": (ctypes.c_int, [_ctx, _i64p]),
@@ -406,11 +410,10 @@ class Context:
         self.active_channels = 2
         return ms.value
 
-    def surface_present(self, smoothing_scale=0.01, depth_scale=1.0, light_direction=(0.0, 0.0, 1.0), light_color=(1.0, 1.0, 1.0),
-                        ambient_color=(0.2, 0.2, 0.2), vmin=0.0, vmax=1.0, weighted_average=False, log=False, lut_rgba=None,
-                        content=True, rgba=True, timings=None):
-        """Bilateral filter of the (q, depth) image, then the lit shading.  Returns (content (R, R, 2) float32 or None,
-        rgba (R, R, 4) uint8 or None); `timings`, a list, receives [filter ms, shading ms]."""
+    @staticmethod
+    def _surface_params(smoothing_scale=0.01, depth_scale=1.0, light_direction=(0.0, 0.0, 1.0), light_color=(1.0, 1.0, 1.0),
+                        ambient_color=(0.2, 0.2, 0.2), vmin=0.0, vmax=1.0, weighted_average=False, log=False, lut_rgba=None):
+        """struct tsp_surface_params of a surface presentation, and the LUT array it points into (kept alive by the caller)."""
         p = SurfaceParams()
         p.smoothing_scale = float(smoothing_scale)
         p.depth_scale = float(depth_scale)
@@ -423,6 +426,15 @@ class Context:
         if weighted_average:
             lut = _f32(lut_rgba, name="lut")
             p.lut_rgba, p.n_lut = _ptr(lut), lut.size // 4
+        return p, lut
+
+    def surface_present(self, smoothing_scale=0.01, depth_scale=1.0, light_direction=(0.0, 0.0, 1.0), light_color=(1.0, 1.0, 1.0),
+                        ambient_color=(0.2, 0.2, 0.2), vmin=0.0, vmax=1.0, weighted_average=False, log=False, lut_rgba=None,
+                        content=True, rgba=True, timings=None):
+        """Bilateral filter of the (q, depth) image, then the lit shading.  Returns (content (R, R, 2) float32 or None,
+        rgba (R, R, 4) uint8 or None); `timings`, a list, receives [filter ms, shading ms]."""
+        p, _lut = self._surface_params(smoothing_scale, depth_scale, light_direction, light_color, ambient_color, vmin, vmax,
+                                       weighted_average, log, lut_rgba)
         R = self.resolution
         c = np.empty((R, R, 2), dtype=np.float32) if content else None
         o = np.empty((R, R, 4), dtype=np.uint8) if rgba else None
@@ -431,6 +443,37 @@ class Context:
         if timings is not None:
             timings[:] = [ms[0], ms[1]]
         return c, o
+
+    def present_surface(self, width, height, params=None, layers=(), timings=None):
+        """Compose a (height, width, 4) uint8 frame with the lit surface as its base (tsp_present_surface): the (q, depth) image
+        filtered, shaded from five samples per canvas pixel, then `layers` in order.  params: a dict of surface_present's
+        keywords (smoothing_scale, depth_scale, light_direction, light_color, ambient_color, vmin, vmax, weighted_average, log,
+        lut_rgba); layers as present takes them.  `timings`, a list, receives [filter ms, composition ms]."""
+        p, _lut = self._surface_params(**(params or {}))
+        arr, _keep = self._layer_args(layers)
+        W, H = int(width), int(height)
+        out = np.empty((max(H, 0), max(W, 0), 4), dtype=np.uint8)
+        ms = (ctypes.c_double * 2)()
+        _check(self._lib.tsp_present_surface(self._h, W, H, ctypes.byref(p), arr, len(layers), out.ctypes.data_as(_u8p), ms))
+        if timings is not None:
+            timings[:] = [ms[0], ms[1]]
+        return out
+
+    def present_surface_yuv420(self, width, height, params=None, layers=(), timings=None):
+        """The frame of present_surface(width, height, params, layers) as I420 planes (tsp_present_surface_yuv420): uint8 arrays
+        Y (height, width), U and V (height / 2, width / 2); width and height must be even.  `timings`, a list, receives
+        [filter ms, composition + conversion ms]."""
+        p, _lut = self._surface_params(**(params or {}))
+        arr, _keep = self._layer_args(layers)
+        W, H = int(width), int(height)
+        n = max(W, 0) * max(H, 0)
+        out = np.empty(n + 2 * (max(W, 0) // 2) * (max(H, 0) // 2), dtype=np.uint8)
+        ms = (ctypes.c_double * 2)()
+        _check(self._lib.tsp_present_surface_yuv420(self._h, W, H, ctypes.byref(p), arr, len(layers), out.ctypes.data_as(_u8p), ms))
+        if timings is not None:
+            timings[:] = [ms[0], ms[1]]
+        c = (W // 2) * (H // 2)
+        return out[:n].reshape(H, W), out[n:n + c].reshape(H // 2, W // 2), out[n + c:].reshape(H // 2, W // 2)
 
     def content_sort(self, kind, scale=1.0):
         """Sort the finite content values on the device; returns (n_finite, n_nonpositive)."""
@@ -586,6 +629,13 @@ class Context:
             lut = _f32(base["lut"], name="lut")
             keep.append(lut)
             b.lut_rgba, b.n_lut = _ptr(lut), lut.size // 4
+        arr, layer_keep = Context._layer_args(layers)
+        return b, arr, keep + layer_keep
+
+    @staticmethod
+    def _layer_args(layers):
+        """The tsp_present_layer array of `layers`, and the arrays it points into (kept alive by the caller)."""
+        keep = []
         arr = (PresentLayer * max(1, len(layers)))()
         for L, d in zip(arr, layers):
             if d["kind"] == "quad":
@@ -616,7 +666,7 @@ class Context:
                 L.width_px = float(np.float32(d["width"]))
             else:
                 raise ValueError(f"unknown layer kind {d['kind']!r}")
-        return b, arr, keep
+        return arr, keep
 
     # ---- multi-GPU ------------------------------------------------------------------------
     @staticmethod

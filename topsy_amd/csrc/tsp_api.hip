@@ -203,7 +203,7 @@ using namespace tsp;
 extern "C" {
 
 const char *tsp_last_error(void) { return g_err; }
-int tsp_version(void) { return 111; }     // 111: tsp_content_neg_inf; 110: tsp_sph_sum; 109: tsp_present_yuv420; 108: tsp_present; 107: surface rendering; 106: tsp_smoothing_lengths; 101: tsp_stats gained ms_mega, n_mega (16 bytes); 102: the per-kernel fragment counts (32 bytes); 103: n_chunk_culled (8 bytes); 104: matrix-core / kernel-I options removed; 105: kernel M's options removed (kernel G draws the mid footprints)
+int tsp_version(void) { return 112; }     // 112: tsp_present_surface, tsp_present_surface_yuv420; 111: tsp_content_neg_inf; 110: tsp_sph_sum; 109: tsp_present_yuv420; 108: tsp_present; 107: surface rendering; 106: tsp_smoothing_lengths; 101: tsp_stats gained ms_mega, n_mega (16 bytes); 102: the per-kernel fragment counts (32 bytes); 103: n_chunk_culled (8 bytes); 104: matrix-core / kernel-I options removed; 105: kernel M's options removed (kernel G draws the mid footprints)
 int tsp_stats_size(void) { return (int)sizeof(tsp_stats); }
 
 int tsp_device_count(void) {
@@ -876,15 +876,48 @@ int tsp_render_surface(tsp_context *ctx, const float *M, float scale_factor, flo
     return TSP_OK;
 }
 
+// what every surface presentation needs of the image and the parameters; `shading`: the LUT is read
+static int check_surface_params(const tsp_context *ctx, const tsp_surface_params *params, bool shading) {
+    TSP_REQUIRE(ctx->C == 2, TSP_EINVAL, "surface presentation needs a 2-channel (q, depth) image, the active one has %d", ctx->C);
+    TSP_REQUIRE(std::isfinite(params->smoothing_scale), TSP_EINVAL, "smoothing_scale must be finite");
+    TSP_REQUIRE(!shading || !params->weighted_average || (params->lut_rgba && params->n_lut >= 2 && params->n_lut <= 65536),
+                TSP_EINVAL, "weighted_average needs a colormap LUT of 2 to 65536 entries");
+    return TSP_OK;
+}
+
 int tsp_surface_present(tsp_context *ctx, const tsp_surface_params *params, float *content_out, uint8_t *rgba8_out,
                         double *ms_out) {
     TSP_REQUIRE(ctx && params, TSP_EINVAL, "NULL argument");
-    TSP_REQUIRE(ctx->C == 2, TSP_EINVAL, "surface presentation needs a 2-channel (q, depth) image, the active one has %d", ctx->C);
-    TSP_REQUIRE(std::isfinite(params->smoothing_scale), TSP_EINVAL, "smoothing_scale must be finite");
-    TSP_REQUIRE(!rgba8_out || !params->weighted_average || (params->lut_rgba && params->n_lut >= 2 && params->n_lut <= 65536),
-                TSP_EINVAL, "weighted_average needs a colormap LUT of 2 to 65536 entries");
+    if (int rc = check_surface_params(ctx, params, rgba8_out != nullptr)) return rc;
     TSP_HIP(hipSetDevice(ctx->device));
     return surface_present(ctx, *params, content_out, rgba8_out, ms_out);
+}
+
+// a composed surface frame also refuses a light or a material range that is not finite
+static int check_surface_frame(const tsp_context *ctx, const tsp_surface_params *params) {
+    if (int rc = check_surface_params(ctx, params, true)) return rc;
+    bool ok = std::isfinite(params->depth_scale);
+    for (int k = 0; k < 3; ++k)
+        ok = ok && std::isfinite(params->light_direction[k]) && std::isfinite(params->light_color[k]) &&
+             std::isfinite(params->ambient_color[k]);
+    TSP_REQUIRE(ok, TSP_EINVAL, "depth_scale, light_direction, light_color and ambient_color must be finite");
+    TSP_REQUIRE(!params->weighted_average || (std::isfinite(params->vmin) && std::isfinite(params->vmax)), TSP_EINVAL,
+                "the material range [vmin, vmax] must be finite");
+    return TSP_OK;
+}
+
+int tsp_present_surface(tsp_context *ctx, int width, int height, const tsp_surface_params *params, const tsp_present_layer *layers,
+                        int n_layers, uint8_t *out_rgba8, double *ms_out) {
+    TSP_REQUIRE(ctx && params && out_rgba8, TSP_EINVAL, "NULL argument");
+    if (int rc = check_surface_frame(ctx, params)) return rc;
+    return present_surface(ctx, width, height, *params, layers, n_layers, out_rgba8, ms_out, false);
+}
+
+int tsp_present_surface_yuv420(tsp_context *ctx, int width, int height, const tsp_surface_params *params,
+                               const tsp_present_layer *layers, int n_layers, uint8_t *out, double *ms_out) {
+    TSP_REQUIRE(ctx && params && out, TSP_EINVAL, "NULL argument");
+    if (int rc = check_surface_frame(ctx, params)) return rc;
+    return present_surface(ctx, width, height, *params, layers, n_layers, out, ms_out, true);
 }
 
 int tsp_get_stats(tsp_context *ctx, tsp_stats *out) {

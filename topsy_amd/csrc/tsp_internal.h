@@ -258,8 +258,15 @@ int render_surface(tsp_context *ctx, const Camera &cam, float cut, const int64_t
                    int n_ranges, int64_t total, int clear, double *ms_draw, double *ms_resolve);
 int density_order_stats(tsp_context *ctx, const int64_t *ranks, int n_ranks, float *values_out);
 int surface_present(tsp_context *ctx, const tsp_surface_params &prm, float *content_out, uint8_t *rgba8_out, double *ms_out);
+// the two halves of it that the surface base of the frame composition shares: the bilateral filter of ctx->image into `filtered`
+// (R * R float2, launched on ctx->stream) and the shading parameters for a normal whose z is 1 / width
+int launch_bilateral(tsp_context *ctx, double smoothing_scale, float2 *filtered);
+ShadeParams shade_params(const tsp_surface_params &prm, int width);
 // tsp_present.hip: frame composition (base map + layers on a W x H canvas), optionally converted to I420 planes (yuv420);
-// per-call memory is DeviceScratch
+// per-call memory is DeviceScratch.  present_surface: the same with the lit surface as the base (the filter, then the shading
+// from five samples of the filtered image per canvas pixel); ms_out = [filter, composition (+ conversion)]
 int present(tsp_context *ctx, int W, int H, const tsp_present_base &base, const tsp_present_layer *layers, int n_layers, void *out,
             double *gpu_ms_out, bool yuv420);
+int present_surface(tsp_context *ctx, int W, int H, const tsp_surface_params &prm, const tsp_present_layer *layers, int n_layers,
+                    void *out, double *ms_out, bool yuv420);
 }  // namespace tsp

@@ -270,4 +270,51 @@ __device__ __forceinline__ float map_rgb_channel(float value, float vmin, float 
     return canon_powf(x, gamma);
 }
 
+// ------------------------------------------------------------------------------------------
+// the lit shading of the surface map (surface.wgsl:28-123), shared by tsp_surface_present's shading kernel (tsp_surface.hip)
+// and the surface base of the frame composition (tsp_present.hip)
+// ------------------------------------------------------------------------------------------
+struct ShadeParams {
+    float depth_scale, vmin, vmax, nz;      // nz: the normal's z before normalisation, texelSize.x = 1 / (image or canvas width)
+    float L[3], lc[3], amb[3];
+    int weighted, log_scale, n_lut;
+};
+
+// q: the material quantity of the pixel; Dc and its four neighbours: depths already multiplied by depth_scale
+__device__ __forceinline__ uint32_t surface_shade_rgba8(float q, float Dc, float Dl, float Dr, float Du, float Dd, const ShadeParams &sp,
+                                                        const float4 *__restrict__ lut) {
+    const float nx0 = -((Dr - Dl) * 0.5f), ny0 = -((Dd - Du) * 0.5f), nz0 = sp.nz;
+    const float len = sqrtf((nx0 * nx0 + ny0 * ny0) + nz0 * nz0);
+    const float nx = nx0 / len, ny = ny0 / len, nz = nz0 / len;
+    float ndl = (nx * sp.L[0] + ny * sp.L[1]) + nz * sp.L[2];
+    ndl = ndl > 0.0f ? ndl : 0.0f;
+    float mat[3] = {1.0f, 1.0f, 1.0f};
+    if (sp.weighted) {
+        float v = q;
+        if (sp.log_scale) v = canon_log10f(v);
+        float u = (v - sp.vmin) / (sp.vmax - sp.vmin);
+        u = (u != u) ? 0.0f : u;
+        u = u < 0.0f ? 0.0f : (u > 1.0f ? 1.0f : u);
+        const float cc = u * (float)sp.n_lut - 0.5f;
+        const float c0 = __builtin_floorf(cc);
+        const float f = cc - c0;
+        const int i0 = clampi((int)c0, 0, sp.n_lut - 1), i1 = clampi((int)c0 + 1, 0, sp.n_lut - 1);
+        const float g = 1.0f - f;
+        const float4 a = lut[i0], b = lut[i1];
+        mat[0] = a.x * g + b.x * f;
+        mat[1] = a.y * g + b.y * f;
+        mat[2] = a.z * g + b.z * f;
+    }
+    float k = Dc < 0.0f ? 0.0f : (Dc > 0.5f ? 0.5f : Dc);
+    k = k * 2.0f;
+    uint32_t rgb[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const float diffuse = (sp.lc[c] * ndl) * mat[c];
+        const float ambient = sp.amb[c] * mat[c];
+        rgb[c] = unorm8((diffuse + ambient) * k);
+    }
+    return rgb[0] | (rgb[1] << 8) | (rgb[2] << 16) | (255u << 24);
+}
+
 }  // namespace tsp

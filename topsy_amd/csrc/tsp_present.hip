@@ -11,6 +11,12 @@
 // a wave covers 64 pixels of one row, so a primitive whose box misses that row segment is skipped on a uniform branch.  The
 // frame is read once and written once; the textures and the table stay in L2.
 //
+// Surface base (tsp_present_surface): the kernel is a template over its base, so the lit surface is an instantiation of its own
+// and the code of the four maps is what it was.  The (q, depth) image is filtered into a per-call scratch by the bilateral kernel
+// of tsp_surface.hip; every lane then samples the filtered image five times (centre and one canvas pixel to each side, the base
+// layer's sampling rule on both channels) and shades with the arithmetic of tsp_surface_present (surface_shade_rgba8,
+// tsp_math.h).  The filtered image is 8 bytes per texel and stays in L2.
+//
 // Movie frames (tsp_present_yuv420): a second, small kernel converts the composed RGBA8 staging frame to I420 planes on the
 // device, so the composition kernel is the same and only 1.5 bytes per pixel are copied out.
 #include "tsp_internal.h"
@@ -18,6 +24,7 @@
 #include <hip/hip_fp16.h>
 
 #include <cmath>
+#include <type_traits>
 
 namespace tsp {
 
@@ -87,8 +94,46 @@ __device__ __forceinline__ float unorm_to_float(uint32_t px, int sh) { return (f
 // out = src * src.a + dst * (1 - src.a), colour and alpha (overlay.py _blending)
 __device__ __forceinline__ float blend1(float s, float sa, float d, float oma) { return s * sa + d * oma; }
 
-template <bool HDR>
-__global__ __launch_bounds__(256) void present_kernel(BaseArgs b, const PresentPrim *__restrict__ prims, int n_prims,
+// ---- surface base: the filtered (q, depth) image F shaded from five samples per canvas pixel (include/topsy_splat.h
+// "tsp_present_surface"), on the rgba8unorm canvas
+struct SurfaceArgs {
+    const float2 *F;
+    int R, W, H;
+    float k, ox, oy;
+    float du, dv;               // one canvas pixel in texels of F: (float)R / (float)W, (float)R / (float)H
+    int linear;                 // k <= 1
+    ShadeParams sp;
+    const float4 *lut;          // the material's 1-D LUT (weighted_average)
+};
+
+// both channels of F at texel-space (tx, ty) by the base layer's rule
+__device__ __forceinline__ float2 sample_surface(const SurfaceArgs &a, float tx, float ty) {
+    if (a.linear) {
+        const Tap sx = linear_tap(tx, a.R), sy = linear_tap(ty, a.R);
+        const float2 p = a.F[(int64_t)sy.i0 * a.R + sx.i0], q = a.F[(int64_t)sy.i0 * a.R + sx.i1];
+        const float2 r = a.F[(int64_t)sy.i1 * a.R + sx.i0], s = a.F[(int64_t)sy.i1 * a.R + sx.i1];
+        return make_float2(lerp0(lerp0(p.x, q.x, sx.f), lerp0(r.x, s.x, sx.f), sy.f),
+                           lerp0(lerp0(p.y, q.y, sx.f), lerp0(r.y, s.y, sx.f), sy.f));
+    }
+    const int i = clampi((int)__builtin_floorf(tx), 0, a.R - 1), j = clampi((int)__builtin_floorf(ty), 0, a.R - 1);
+    return a.F[(int64_t)j * a.R + i];
+}
+
+__device__ __forceinline__ uint32_t surface_base_rgba8(const SurfaceArgs &a, float xc, float yc) {
+    const float ax = (xc - a.ox) * a.k, ay = (yc - a.oy) * a.k;
+    const float2 c = sample_surface(a, ax, ay);
+    const float Dc = c.y * a.sp.depth_scale;
+    const float Dl = sample_surface(a, ax - a.du, ay).y * a.sp.depth_scale;
+    const float Dr = sample_surface(a, ax + a.du, ay).y * a.sp.depth_scale;
+    const float Du = sample_surface(a, ax, ay - a.dv).y * a.sp.depth_scale;
+    const float Dd = sample_surface(a, ax, ay + a.dv).y * a.sp.depth_scale;
+    return surface_shade_rgba8(c.x, Dc, Dl, Dr, Du, Dd, a.sp, a.lut);
+}
+
+// One pixel per lane: its base colour (Base = BaseArgs: the four maps; SurfaceArgs: the lit surface, HDR = false), the primitives
+// in draw order, the single write.
+template <bool HDR, typename Base>
+__global__ __launch_bounds__(256) void present_kernel(Base b, const PresentPrim *__restrict__ prims, int n_prims,
                                                       const float4 *__restrict__ tex, void *__restrict__ out) {
     const int lane = threadIdx.x & 63;
     const int y = blockIdx.y * 4 + (threadIdx.x >> 6);      // wave-uniform
@@ -97,28 +142,32 @@ __global__ __launch_bounds__(256) void present_kernel(BaseArgs b, const PresentP
     if (y >= b.H || x >= b.W) return;
     const float xc = (float)x + 0.5f, yc = (float)y + 0.5f;
 
-    // ---- base layer: sample the raw channels, then map
-    const float ax = (xc - b.ox) * b.k, ay = (yc - b.oy) * b.k;
-    float4 v;
-    if (b.linear) {
-        v = bilinear(b.img, b.C, b.R, b.R, ax, ay);
-    } else {
-        const int i = clampi((int)__builtin_floorf(ax), 0, b.R - 1), j = clampi((int)__builtin_floorf(ay), 0, b.R - 1);
-        v = load_texel(b.img, b.C, (int64_t)j * b.R + i);
-    }
     uint32_t px8 = 0;
     float4 pxf = make_float4(0.f, 0.f, 0.f, 1.f);
-    if (b.map == TSP_PRESENT_SCALAR) {
-        px8 = map_scalar_rgba8(v.x, v.y, b.lut, b.n_lut, b.vmin, b.range, b.log_scale, b.weighted);
-    } else if (b.map == TSP_PRESENT_BIVARIATE) {
-        px8 = map_bivariate_rgba8(v.x, v.y, b.lut, b.n_lut, b.vmin, b.range, b.dvmin, b.drange, b.log_scale, b.weighted);
+    if constexpr (std::is_same<Base, SurfaceArgs>::value) {
+        px8 = surface_base_rgba8(b, xc, yc);
     } else {
-        const float c0 = map_rgb_channel(v.x, b.vmin, b.range, b.gamma);
-        const float c1 = map_rgb_channel(v.y, b.vmin, b.range, b.gamma);
-        const float c2 = map_rgb_channel(v.z, b.vmin, b.range, b.gamma);
-        if (HDR) pxf = make_float4(__half2float(__float2half_rn(c0)), __half2float(__float2half_rn(c1)),
-                                   __half2float(__float2half_rn(c2)), 1.0f);
-        else px8 = unorm8(c0) | (unorm8(c1) << 8) | (unorm8(c2) << 16) | (255u << 24);
+        // ---- base layer: sample the raw channels, then map
+        const float ax = (xc - b.ox) * b.k, ay = (yc - b.oy) * b.k;
+        float4 v;
+        if (b.linear) {
+            v = bilinear(b.img, b.C, b.R, b.R, ax, ay);
+        } else {
+            const int i = clampi((int)__builtin_floorf(ax), 0, b.R - 1), j = clampi((int)__builtin_floorf(ay), 0, b.R - 1);
+            v = load_texel(b.img, b.C, (int64_t)j * b.R + i);
+        }
+        if (b.map == TSP_PRESENT_SCALAR) {
+            px8 = map_scalar_rgba8(v.x, v.y, b.lut, b.n_lut, b.vmin, b.range, b.log_scale, b.weighted);
+        } else if (b.map == TSP_PRESENT_BIVARIATE) {
+            px8 = map_bivariate_rgba8(v.x, v.y, b.lut, b.n_lut, b.vmin, b.range, b.dvmin, b.drange, b.log_scale, b.weighted);
+        } else {
+            const float c0 = map_rgb_channel(v.x, b.vmin, b.range, b.gamma);
+            const float c1 = map_rgb_channel(v.y, b.vmin, b.range, b.gamma);
+            const float c2 = map_rgb_channel(v.z, b.vmin, b.range, b.gamma);
+            if (HDR) pxf = make_float4(__half2float(__float2half_rn(c0)), __half2float(__float2half_rn(c1)),
+                                       __half2float(__float2half_rn(c2)), 1.0f);
+            else px8 = unorm8(c0) | (unorm8(c1) << 8) | (unorm8(c2) << 16) | (255u << 24);
+        }
     }
 
     // ---- the primitives, in draw order
@@ -356,20 +405,30 @@ int check_layer(const tsp_present_layer &L, int index, int64_t &n_prims, int64_t
         }                                                                                                               \
     } while (0)
 
-}  // namespace
-
-int present(tsp_context *ctx, int W, int H, const tsp_present_base &base, const tsp_present_layer *layers, int n_layers,
-            void *out, double *gpu_ms_out, bool yuv420) {
+// One frame: exactly one of `base` (the four maps of tsp_present) and `surf` (the lit surface) is given.  ms_out: base: the
+// composition (+ conversion); surf: [filter, composition (+ conversion)].
+int compose(tsp_context *ctx, int W, int H, const tsp_present_base *base, const tsp_surface_params *surf,
+            const tsp_present_layer *layers, int n_layers, void *out, double *ms_out, bool yuv420) {
     TSP_REQUIRE(W >= 1 && W <= MAX_SIDE && H >= 1 && H <= MAX_SIDE, TSP_EINVAL, "canvas %d x %d outside [1, %d]", W, H, MAX_SIDE);
     if (yuv420) TSP_REQUIRE(W >= 2 && H >= 2 && W % 2 == 0 && H % 2 == 0, TSP_EINVAL, "4:2:0 needs an even canvas, not %d x %d", W, H);
     TSP_REQUIRE(n_layers >= 0 && n_layers <= MAX_LAYERS && (n_layers == 0 || layers), TSP_EINVAL, "bad layer list (%d layers)", n_layers);
-    const int map = base.map;
-    TSP_REQUIRE(map >= TSP_PRESENT_SCALAR && map <= TSP_PRESENT_RGB_HDR, TSP_EINVAL, "unknown base map %d", map);
-    if (yuv420) TSP_REQUIRE(map != TSP_PRESENT_RGB_HDR, TSP_EINVAL, "4:2:0 frames are 8-bit: the rgb-hdr map has no such frame");
-    if (map == TSP_PRESENT_SCALAR)
-        TSP_REQUIRE(base.lut_rgba && base.n_lut >= 2 && base.n_lut <= 65536, TSP_EINVAL, "bad colormap LUT (n=%d)", base.n_lut);
-    if (map == TSP_PRESENT_BIVARIATE) TSP_REQUIRE(ctx->lut2d, TSP_ESTATE, "tsp_colormap_set_lut2d must be called first");
-    if (map >= TSP_PRESENT_RGB) TSP_REQUIRE(ctx->C == 4, TSP_EINVAL, "rgb maps need a 4-channel image");
+    const int map = base ? base->map : -1;
+    const float *h_lut = nullptr;       // the 1-D LUT of the call, if its base has one
+    int n_lut = 0;
+    if (base) {
+        TSP_REQUIRE(map >= TSP_PRESENT_SCALAR && map <= TSP_PRESENT_RGB_HDR, TSP_EINVAL, "unknown base map %d", map);
+        if (yuv420) TSP_REQUIRE(map != TSP_PRESENT_RGB_HDR, TSP_EINVAL, "4:2:0 frames are 8-bit: the rgb-hdr map has no such frame");
+        if (map == TSP_PRESENT_SCALAR) {
+            TSP_REQUIRE(base->lut_rgba && base->n_lut >= 2 && base->n_lut <= 65536, TSP_EINVAL, "bad colormap LUT (n=%d)", base->n_lut);
+            h_lut = base->lut_rgba;
+            n_lut = base->n_lut;
+        }
+        if (map == TSP_PRESENT_BIVARIATE) TSP_REQUIRE(ctx->lut2d, TSP_ESTATE, "tsp_colormap_set_lut2d must be called first");
+        if (map >= TSP_PRESENT_RGB) TSP_REQUIRE(ctx->C == 4, TSP_EINVAL, "rgb maps need a 4-channel image");
+    } else if (surf->weighted_average) {     // (checked by the caller: 2..65536 entries)
+        h_lut = surf->lut_rgba;
+        n_lut = surf->n_lut;
+    }
     int64_t n_prims = 0, n_texels = 0;
     for (int l = 0; l < n_layers; ++l) {
         const int rc = check_layer(layers[l], l, n_prims, n_texels);
@@ -398,12 +457,13 @@ int present(tsp_context *ctx, int W, int H, const tsp_present_base &base, const 
     const bool hdr = map == TSP_PRESENT_RGB_HDR;
     const size_t frame_bytes = (size_t)W * H * (hdr ? 8 : 4);
     const size_t out_bytes = yuv420 ? (size_t)W * H + 2 * ((size_t)(W / 2) * (H / 2)) : frame_bytes;
-    DeviceScratch d_tex, d_prims, d_lut, d_frame, d_yuv;
+    DeviceScratch d_tex, d_prims, d_lut, d_frame, d_yuv, d_filtered;
     PRESENT_ALLOC(d_frame, frame_bytes);
     if (yuv420) PRESENT_ALLOC(d_yuv, out_bytes);
     PRESENT_ALLOC(d_prims, prims.size() * sizeof(PresentPrim));
     PRESENT_ALLOC(d_tex, (size_t)n_texels * sizeof(float4));
-    if (map == TSP_PRESENT_SCALAR) PRESENT_ALLOC(d_lut, (size_t)base.n_lut * sizeof(float4));
+    if (h_lut) PRESENT_ALLOC(d_lut, (size_t)n_lut * sizeof(float4));
+    if (surf) PRESENT_ALLOC(d_filtered, (size_t)ctx->R * ctx->R * sizeof(float2));
 
     for (int l = 0; l < n_layers; ++l)
         if (tex_at[l] >= 0)
@@ -411,39 +471,59 @@ int present(tsp_context *ctx, int W, int H, const tsp_present_base &base, const 
                                    (size_t)layers[l].tex_width * layers[l].tex_height * sizeof(float4), hipMemcpyHostToDevice, st));
     if (!prims.empty())
         TSP_HIP(hipMemcpyAsync(d_prims.p, prims.data(), prims.size() * sizeof(PresentPrim), hipMemcpyHostToDevice, st));
-    if (map == TSP_PRESENT_SCALAR)
-        TSP_HIP(hipMemcpyAsync(d_lut.p, base.lut_rgba, (size_t)base.n_lut * sizeof(float4), hipMemcpyHostToDevice, st));
+    if (h_lut) TSP_HIP(hipMemcpyAsync(d_lut.p, h_lut, (size_t)n_lut * sizeof(float4), hipMemcpyHostToDevice, st));
 
-    BaseArgs b;
-    b.img = ctx->image;
-    b.R = ctx->R;
-    b.C = ctx->C;
-    b.W = W;
-    b.H = H;
     const int S = W > H ? W : H;
-    b.k = (float)ctx->R / (float)S;
-    b.ox = 0.5f * (float)(W - S);
-    b.oy = 0.5f * (float)(H - S);
-    b.linear = b.k <= 1.0f;
-    b.map = map;
-    b.lut = map == TSP_PRESENT_SCALAR ? d_lut.as<float4>() : reinterpret_cast<const float4 *>(ctx->lut2d);
-    b.n_lut = map == TSP_PRESENT_SCALAR ? base.n_lut : ctx->lut2d_n;
-    b.vmin = base.vmin;
-    b.range = base.vmax - base.vmin;
-    b.dvmin = base.density_vmin;
-    b.drange = base.density_vmax - base.density_vmin;
-    b.gamma = base.gamma;
-    b.log_scale = base.log_scale ? 1 : 0;
-    b.weighted = base.weighted ? 1 : 0;
-
+    const float k = (float)ctx->R / (float)S, ox = 0.5f * (float)(W - S), oy = 0.5f * (float)(H - S);
     const dim3 grid((unsigned)((W + 63) / 64), (unsigned)((H + 3) / 4));
-    TSP_HIP(hipEventRecord(ctx->ev[EV_T3], st));
-    if (hdr)
-        hipLaunchKernelGGL(present_kernel<true>, grid, dim3(256), 0, st, b, d_prims.as<PresentPrim>(), (int)prims.size(),
+    if (surf) {
+        TSP_HIP(hipEventRecord(ctx->ev[EV_T2], st));
+        if (int rc = launch_bilateral(ctx, surf->smoothing_scale, d_filtered.as<float2>())) return rc;
+        TSP_HIP(hipEventRecord(ctx->ev[EV_T3], st));
+        SurfaceArgs a;
+        a.F = d_filtered.as<float2>();
+        a.R = ctx->R;
+        a.W = W;
+        a.H = H;
+        a.k = k;
+        a.ox = ox;
+        a.oy = oy;
+        a.du = (float)ctx->R / (float)W;
+        a.dv = (float)ctx->R / (float)H;
+        a.linear = k <= 1.0f;
+        a.sp = shade_params(*surf, W);
+        a.lut = d_lut.as<float4>();
+        hipLaunchKernelGGL((present_kernel<false, SurfaceArgs>), grid, dim3(256), 0, st, a, d_prims.as<PresentPrim>(), (int)prims.size(),
                            d_tex.as<float4>(), d_frame.p);
-    else
-        hipLaunchKernelGGL(present_kernel<false>, grid, dim3(256), 0, st, b, d_prims.as<PresentPrim>(), (int)prims.size(),
-                           d_tex.as<float4>(), d_frame.p);
+    } else {
+        BaseArgs b;
+        b.img = ctx->image;
+        b.R = ctx->R;
+        b.C = ctx->C;
+        b.W = W;
+        b.H = H;
+        b.k = k;
+        b.ox = ox;
+        b.oy = oy;
+        b.linear = b.k <= 1.0f;
+        b.map = map;
+        b.lut = map == TSP_PRESENT_SCALAR ? d_lut.as<float4>() : reinterpret_cast<const float4 *>(ctx->lut2d);
+        b.n_lut = map == TSP_PRESENT_SCALAR ? n_lut : ctx->lut2d_n;
+        b.vmin = base->vmin;
+        b.range = base->vmax - base->vmin;
+        b.dvmin = base->density_vmin;
+        b.drange = base->density_vmax - base->density_vmin;
+        b.gamma = base->gamma;
+        b.log_scale = base->log_scale ? 1 : 0;
+        b.weighted = base->weighted ? 1 : 0;
+        TSP_HIP(hipEventRecord(ctx->ev[EV_T3], st));
+        if (hdr)
+            hipLaunchKernelGGL((present_kernel<true, BaseArgs>), grid, dim3(256), 0, st, b, d_prims.as<PresentPrim>(), (int)prims.size(),
+                               d_tex.as<float4>(), d_frame.p);
+        else
+            hipLaunchKernelGGL((present_kernel<false, BaseArgs>), grid, dim3(256), 0, st, b, d_prims.as<PresentPrim>(), (int)prims.size(),
+                               d_tex.as<float4>(), d_frame.p);
+    }
     TSP_HIP(hipGetLastError());
     if (yuv420) {
         const bool w4 = W % 4 == 0;
@@ -462,12 +542,28 @@ int present(tsp_context *ctx, int W, int H, const tsp_present_base &base, const 
     TSP_HIP(hipStreamSynchronize(st));      // the frame is complete before anything of the caller's is written
     TSP_HIP(hipMemcpyAsync(out, yuv420 ? d_yuv.p : d_frame.p, out_bytes, hipMemcpyDeviceToHost, st));
     TSP_HIP(hipStreamSynchronize(st));
-    if (gpu_ms_out) {
+    if (ms_out) {
         float ms = 0.f;
+        if (surf) {
+            TSP_HIP(hipEventElapsedTime(&ms, ctx->ev[EV_T2], ctx->ev[EV_T3]));
+            *ms_out++ = ms;
+        }
         TSP_HIP(hipEventElapsedTime(&ms, ctx->ev[EV_T3], ctx->ev[EV_T4]));
-        *gpu_ms_out = ms;
+        *ms_out = ms;
     }
     return TSP_OK;
+}
+
+}  // namespace
+
+int present(tsp_context *ctx, int W, int H, const tsp_present_base &base, const tsp_present_layer *layers, int n_layers,
+            void *out, double *gpu_ms_out, bool yuv420) {
+    return compose(ctx, W, H, &base, nullptr, layers, n_layers, out, gpu_ms_out, yuv420);
+}
+
+int present_surface(tsp_context *ctx, int W, int H, const tsp_surface_params &prm, const tsp_present_layer *layers, int n_layers,
+                    void *out, double *ms_out, bool yuv420) {
+    return compose(ctx, W, H, nullptr, &prm, layers, n_layers, out, ms_out, yuv420);
 }
 
 }  // namespace tsp

@@ -321,12 +321,6 @@ __global__ __launch_bounds__(256) void bilateral_kernel(const float2 *__restrict
 // ------------------------------------------------------------------------------------------------
 // shading (surface.wgsl:28-123)
 // ------------------------------------------------------------------------------------------------
-struct ShadeParams {
-    float depth_scale, vmin, vmax, inv_R;
-    float L[3], lc[3], amb[3];
-    int weighted, log_scale, n_lut;
-};
-
 __global__ __launch_bounds__(256) void surface_shade_kernel(const float2 *__restrict__ F, int R, ShadeParams sp,
                                                             const float4 *__restrict__ lut, uint32_t *__restrict__ out) {
     const int64_t npix = (int64_t)R * R;
@@ -338,81 +332,61 @@ __global__ __launch_bounds__(256) void surface_shade_kernel(const float2 *__rest
         const float Dr = F[(size_t)j * R + min(i + 1, R - 1)].y * sp.depth_scale;
         const float Du = F[(size_t)max(j - 1, 0) * R + i].y * sp.depth_scale;
         const float Dd = F[(size_t)min(j + 1, R - 1) * R + i].y * sp.depth_scale;
-        const float nx0 = -((Dr - Dl) * 0.5f), ny0 = -((Dd - Du) * 0.5f), nz0 = sp.inv_R;
-        const float len = sqrtf((nx0 * nx0 + ny0 * ny0) + nz0 * nz0);
-        const float nx = nx0 / len, ny = ny0 / len, nz = nz0 / len;
-        float ndl = (nx * sp.L[0] + ny * sp.L[1]) + nz * sp.L[2];
-        ndl = ndl > 0.0f ? ndl : 0.0f;
-        float mat[3] = {1.0f, 1.0f, 1.0f};
-        if (sp.weighted) {
-            float v = c.x;
-            if (sp.log_scale) v = canon_log10f(v);
-            float u = (v - sp.vmin) / (sp.vmax - sp.vmin);
-            u = (u != u) ? 0.0f : u;
-            u = u < 0.0f ? 0.0f : (u > 1.0f ? 1.0f : u);
-            const float cc = u * (float)sp.n_lut - 0.5f;
-            const float c0 = __builtin_floorf(cc);
-            const float f = cc - c0;
-            const int i0 = clampi((int)c0, 0, sp.n_lut - 1), i1 = clampi((int)c0 + 1, 0, sp.n_lut - 1);
-            const float g = 1.0f - f;
-            const float4 a = lut[i0], b = lut[i1];
-            mat[0] = a.x * g + b.x * f;
-            mat[1] = a.y * g + b.y * f;
-            mat[2] = a.z * g + b.z * f;
-        }
-        float k = Dc < 0.0f ? 0.0f : (Dc > 0.5f ? 0.5f : Dc);
-        k = k * 2.0f;
-        uint32_t rgb[3];
-#pragma unroll
-        for (int q = 0; q < 3; ++q) {
-            const float diffuse = (sp.lc[q] * ndl) * mat[q];
-            const float ambient = sp.amb[q] * mat[q];
-            rgb[q] = unorm8((diffuse + ambient) * k);
-        }
-        out[t] = rgb[0] | (rgb[1] << 8) | (rgb[2] << 16) | (255u << 24);
+        out[t] = surface_shade_rgba8(c.x, Dc, Dl, Dr, Du, Dd, sp, lut);
     }
+}
+
+ShadeParams shade_params(const tsp_surface_params &prm, int width) {
+    ShadeParams sp;
+    sp.depth_scale = prm.depth_scale;
+    sp.vmin = prm.vmin;
+    sp.vmax = prm.vmax;
+    sp.nz = 1.0f / (float)width;       // texelSize.x
+    for (int q = 0; q < 3; ++q) {
+        sp.L[q] = prm.light_direction[q];
+        sp.lc[q] = prm.light_color[q];
+        sp.amb[q] = prm.ambient_color[q];
+    }
+    sp.weighted = prm.weighted_average ? 1 : 0;
+    sp.log_scale = prm.log_scale ? 1 : 0;
+    sp.n_lut = prm.weighted_average ? prm.n_lut : 0;
+    return sp;
+}
+
+int launch_bilateral(tsp_context *ctx, double smoothing_scale, float2 *filtered) {
+    const int R = ctx->R;
+    // filter parameters as colormap/surface.py:259-287 forms them (float64, stored as float32; kernel_size from the float32)
+    const double sig = smoothing_scale < 1e-5 ? 1e-5 : smoothing_scale;
+    const float ss = (float)(sig * (double)R), rs = (float)(sig * 2.0);
+    const float ss4 = ss * 4.0f;
+    const int n_pix = ss4 >= 100.0f ? 100 : (int)ss4 + 1;     // min(int(ss * 4) + 1, MAX_SURFACE_SMOOTH_PIXELS = 100)
+    const int half = n_pix / 2;
+    const int W = FT + 2 * half, nk = 2 * half + 1;
+    const size_t lds = (size_t)(W * W + nk * nk) * sizeof(float);
+    if (lds > 65536)     // (at most 94.6 KB: half <= 50)
+        TSP_HIP(hipFuncSetAttribute((const void *)bilateral_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    const unsigned tiles = (unsigned)((R + FT - 1) / FT);
+    hipLaunchKernelGGL(bilateral_kernel, dim3(tiles, tiles), dim3(256), lds, ctx->stream, reinterpret_cast<const float2 *>(ctx->image),
+                       filtered, R, half, ss, rs);
+    TSP_HIP(hipGetLastError());
+    return TSP_OK;
 }
 
 int surface_present(tsp_context *ctx, const tsp_surface_params &prm, float *content_out, uint8_t *rgba8_out, double *ms_out) {
     const int R = ctx->R;
     const int64_t npix = (int64_t)R * R;
     hipStream_t st = ctx->stream;
-    // filter parameters as colormap/surface.py:259-287 forms them (float64, stored as float32; kernel_size from the float32)
-    const double sig = prm.smoothing_scale < 1e-5 ? 1e-5 : prm.smoothing_scale;
-    const float ss = (float)(sig * (double)R), rs = (float)(sig * 2.0);
-    const float ss4 = ss * 4.0f;
-    const int n_pix = ss4 >= 100.0f ? 100 : (int)ss4 + 1;     // min(int(ss * 4) + 1, MAX_SURFACE_SMOOTH_PIXELS = 100)
-    const int half = n_pix / 2;
     DeviceScratch filtered, lut;
     TSP_HIP(filtered.alloc((size_t)npix * sizeof(float2)));
     if (rgba8_out && prm.weighted_average) {
         TSP_HIP(lut.alloc((size_t)prm.n_lut * sizeof(float4)));
         TSP_HIP(hipMemcpyAsync(lut.p, prm.lut_rgba, (size_t)prm.n_lut * sizeof(float4), hipMemcpyHostToDevice, st));
     }
-    const int W = FT + 2 * half, nk = 2 * half + 1;
-    const size_t lds = (size_t)(W * W + nk * nk) * sizeof(float);
-    if (lds > 65536)     // (at most 94.6 KB: half <= 50)
-        TSP_HIP(hipFuncSetAttribute((const void *)bilateral_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     TSP_HIP(hipEventRecord(ctx->ev[EV_T3], st));
-    const unsigned tiles = (unsigned)((R + FT - 1) / FT);
-    hipLaunchKernelGGL(bilateral_kernel, dim3(tiles, tiles), dim3(256), lds, st, reinterpret_cast<const float2 *>(ctx->image),
-                       filtered.as<float2>(), R, half, ss, rs);
-    TSP_HIP(hipGetLastError());
+    if (int rc = launch_bilateral(ctx, prm.smoothing_scale, filtered.as<float2>())) return rc;
     TSP_HIP(hipEventRecord(ctx->ev[EV_T4], st));
     if (rgba8_out) {
-        ShadeParams sp;
-        sp.depth_scale = prm.depth_scale;
-        sp.vmin = prm.vmin;
-        sp.vmax = prm.vmax;
-        sp.inv_R = 1.0f / (float)R;       // texelSize.x
-        for (int q = 0; q < 3; ++q) {
-            sp.L[q] = prm.light_direction[q];
-            sp.lc[q] = prm.light_color[q];
-            sp.amb[q] = prm.ambient_color[q];
-        }
-        sp.weighted = prm.weighted_average ? 1 : 0;
-        sp.log_scale = prm.log_scale ? 1 : 0;
-        sp.n_lut = prm.weighted_average ? prm.n_lut : 0;
+        const ShadeParams sp = shade_params(prm, R);
         const unsigned grid = (unsigned)std::min<int64_t>((npix + 255) / 256, (int64_t)ctx->cu_count * 16);
         hipLaunchKernelGGL(surface_shade_kernel, dim3(grid), dim3(256), 0, st, filtered.as<float2>(), R, sp, lut.as<float4>(),
                            reinterpret_cast<uint32_t *>(ctx->out8));
