@@ -85,7 +85,8 @@ const char *tsp_last_error(void);
  * 110: new entry point tsp_sph_sum (gather-form SPH sums: densities for snapshots that carry none); nothing else changed.
  * 111: new entry point tsp_content_neg_inf (how many content values of the last tsp_content_sort were -inf); nothing else changed.
  * 112: surface frames: tsp_present_surface and tsp_present_surface_yuv420 (the lit surface composed onto a canvas of any size under
- * the layers of tsp_present, and that frame as I420 planes); no struct changed, nothing else changed. */
+ * the layers of tsp_present, and that frame as I420 planes); no struct changed, nothing else changed.
+ * 113: new entry point tsp_shrink_sphere_center and the struct tsp_center_info (a snapshot's centre); nothing else changed. */
 int tsp_version(void);
 int tsp_stats_size(void);
 
@@ -257,6 +258,44 @@ int tsp_smoothing_lengths(tsp_context *ctx, int64_t n, const float *x, const flo
  * returns TSP_ENOMEM and writes nothing. */
 int tsp_sph_sum(tsp_context *ctx, int64_t n, const float *x, const float *y, const float *z, const float *h,
                 const float *a, float period, float *out);
+
+/* The shrinking-sphere centre of a snapshot (Power et al. 2003): what pynbody.analysis.halo.center computes by default and the
+ * reference asks for when it centres a snapshot at load (PynbodyDataLoader._perform_centering, src/topsy/loader.py:201-217, with
+ * center = "all" or "zoom").  Host arrays in, caller's order; uses ctx's device and stream only: resident particles, image,
+ * accumulator and tsp_stats unchanged.  Float64 throughout unless said otherwise (no fused multiply-adds):
+ *   - Valid particles.  Particle i is valid iff x[i], y[i], z[i], mass[i] are finite and mass[i] > 0.  With mass_cut_factor > 0 it
+ *     must also satisfy (double)mass[i] < (double)mass_cut_factor * (double)m_min, where m_min is the smallest mass among the
+ *     otherwise valid particles (the reference's "zoom" rule, mass < 1.01 * mass.min()); mass_cut_factor == 0: no selection.
+ *   - Initial centre.  c = sum m p / sum m over the valid particles (m = (double)mass[i], p = the (double) coordinates).
+ *   - Initial radius.  r = r_start if r_start > 0, else ((double)max x - (double)min x) / 2 over the valid particles (pynbody's
+ *     rough estimate).
+ *   - Loop, until max_iterations updates have been done:
+ *       1. r_try = r * shrink_factor;
+ *       2. the inside set: the valid i with d2 < r_try * r_try (strict), where dx = (double)x[i] - c[0] (dy, dz alike) and
+ *          d2 = (dx * dx + dy * dy) + dz * dz;
+ *       3. fewer than min_particles members: stop, c and r stay;
+ *       4. else c += sum m (dx, dy, dz) / sum m over the set, r = r_try, one more iteration.
+ *     The displacements are summed from the current centre, so the rounding error is proportional to r and not to |p|: a
+ *     snapshot sitting at 1e4 with structure at 1e-2 is centred as well as one at the origin.
+ *   - Outputs.  center_out = the final c.  info_out (optional): n_valid, iterations = the updates done, radius = the final r,
+ *     n_inside and mass_inside = the count and sum m of the last accepted inside set -- of all valid particles when no update
+ *     happened; reserved = 0.
+ *   - The order of every sum is free but fixed (no floating-point atomics; per-wave and per-workgroup partial sums are combined in
+ *     a fixed order): the same call on the same input and device returns the same bits.  Counts are integers.
+ * 1 <= n < 2^31, no NULL array or center_out, 0 < shrink_factor < 1, min_particles >= 1, 0 <= max_iterations <= 256, r_start = 0
+ * or finite and > 0, mass_cut_factor = 0 or finite and > 1, at least one valid particle; anything else returns TSP_EINVAL and
+ * writes nothing.  pynbody's defaults: shrink_factor 0.7, min_particles 100.  Not provided: periodic wrapping of the displacements.
+ * Device memory is allocated for the call only (about 16 bytes per particle); a failed allocation returns TSP_ENOMEM and writes
+ * nothing.  The cost is one 16-byte-per-particle pass per iteration, less the blocks of 1024 consecutive particles whose bounding
+ * box lies outside the sphere: those are not read (identical results; pays with a spatial order of the arrays). */
+typedef struct {
+    int64_t n_valid, n_inside;
+    int32_t iterations, reserved;
+    double radius, mass_inside;
+} tsp_center_info;
+int tsp_shrink_sphere_center(tsp_context *ctx, int64_t n, const float *x, const float *y, const float *z, const float *mass,
+                             float mass_cut_factor, double r_start, double shrink_factor, int64_t min_particles,
+                             int max_iterations, double center_out[3], tsp_center_info *info_out);
 
 /* Surface rendering: DepthSPHWithOcclusion + ColorAsSurfaceMap (reference src/topsy/sph.py:448-656, shaders/sph.wgsl:94-122,
  * 149-158, shaders/smooth.wgsl, shaders/surface.wgsl, colormap/surface.py).  Float32 throughout, operations in the order written.

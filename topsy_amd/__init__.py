@@ -26,7 +26,7 @@ def test(nparticle=config.TEST_DATA_NUM_PARTICLES_DEFAULT, **kwargs):
 
 
 def from_arrays(pos, smooth, mass, quantities=None, rgb=None, with_cells=False, n_smooth=None, periodicity_scale=None,
-                **kwargs):
+                center="none", **kwargs):
     """Visualizer over caller-supplied numpy arrays (e.g. taken from a pynbody snapshot).
 
     smooth=None computes the smoothing lengths on the GPU from the n_smooth (default config.SMOOTH_NEIGHBOURS) nearest
@@ -34,12 +34,17 @@ def from_arrays(pos, smooth, mass, quantities=None, rgb=None, with_cells=False, 
 
     'rho' is always a quantity (vis.quantity_name = "rho"; the bivariate map's default): quantities["rho"] if given, else
     the SPH density of the particles, computed on the GPU on first use (sph_density) and cached on the loader --
-    vis.data_loader.get_named_quantity("rho") returns it, set_density() restores it from the caller's own cache."""
+    vis.data_loader.get_named_quantity("rho") returns it, set_density() restores it from the caller's own cache.
+
+    center: where the view opens -- "none" (the origin), "all" (the shrinking-sphere centre of the particles, found on the GPU:
+    shrink_sphere_center), "zoom" (that of the lightest mass species) or three coordinates.  vis.data_loader.get_initial_center()
+    returns it, set_initial_center() restores it from the caller's own cache."""
     from . import visualizer, loader
     return visualizer.Visualizer(data_loader_class=loader.ArrayDataLoader,
                                  data_loader_kwargs={"pos": pos, "smooth": smooth, "mass": mass,
                                                      "quantities": quantities, "rgb": rgb, "with_cells": with_cells,
-                                                     "n_smooth": n_smooth, "periodicity_scale": periodicity_scale},
+                                                     "n_smooth": n_smooth, "periodicity_scale": periodicity_scale,
+                                                     "center": center},
                                  **kwargs)
 
 
@@ -117,6 +122,35 @@ def sph_mean(pos, mass, smooth, values, rho=None, n_smooth=config.SMOOTH_NEIGHBO
         with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
             a = arr["mass"] * arr["values"] / rho
         return ctx.sph_sum(x, y, z, h, a, period)
+    finally:
+        ctx.close()
+
+
+def shrink_sphere_center(pos, mass, select="all", r_start=None, shrink_factor=0.7, min_particles=100, device_id=0):
+    """Shrinking-sphere centre (Power et al. 2003; pynbody.analysis.halo.center's default) of an (n, 3) position array on GPU
+    `device_id` (C: tsp_shrink_sphere_center): starting from the centre of mass and a sphere of radius r_start (None: half the
+    x extent), the centre moves to the mass-weighted mean of the particles inside a sphere shrunk by shrink_factor per step,
+    until fewer than min_particles are inside.  select="zoom" uses the lightest mass species only (mass < 1.01 * mass.min(),
+    the reference's center="zoom").  Particles with a non-finite coordinate or a mass that is not finite and > 0 take no part.
+    Returns (center float64 (3,), dict(n_valid, n_inside, iterations, radius, mass_inside)).
+    Out of scope: periodic wrapping of the displacements, "halo-N" centres (they need a halo catalogue)."""
+    from . import _native, loader
+    cut, r0, shrink, min_particles = loader.check_center_arguments(select, r_start, shrink_factor, min_particles)
+    pos = np.asarray(pos, dtype=np.float32)
+    if pos.ndim != 2 or pos.shape[1] != 3:
+        raise ValueError(f"pos must have shape (n, 3), not {pos.shape}")
+    mass = np.asarray(mass, dtype=np.float32)
+    if mass.shape != (len(pos),):
+        raise ValueError(f"pos and mass must have the same length: mass has shape {mass.shape}, not ({len(pos)},)")
+    if len(pos) == 0:
+        raise ValueError("pos must have at least one particle")
+    with np.errstate(invalid="ignore"):
+        if not (np.isfinite(pos).all(axis=1) & np.isfinite(mass) & (mass > 0)).any():
+            raise ValueError("no particle has finite coordinates and a finite mass > 0")
+    ctx = _native.Context(1, 2, device_id)
+    try:
+        return ctx.shrink_sphere_center(pos[:, 0], pos[:, 1], pos[:, 2], mass, mass_cut_factor=cut, r_start=r0,
+                                        shrink_factor=shrink, min_particles=min_particles)
     finally:
         ctx.close()
 

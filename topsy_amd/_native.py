@@ -16,7 +16,8 @@ MODE_WEIGHTED, MODE_DEPTH, MODE_RGB = 0, 1, 2
 PIPE_DEFAULT, PIPE_GENERIC = 0, 1
 SAMPLE_BILINEAR_MIP0, SAMPLE_BILINEAR_MIP = 0x10, 0x20      # diagnostic sampling rules (generic kernel)
 UNIQUE_ID_BYTES = 128
-ABI_VERSION = 112            # include/topsy_splat.h: tsp_version()
+ABI_VERSION = 112            # the oldest tsp_version() whose structs this binding matches; entry points added since
+                             # (113: tsp_shrink_sphere_center) are required by name in load_library()
 PRESENT_SCALAR, PRESENT_BIVARIATE, PRESENT_RGB, PRESENT_RGB_HDR = 0, 1, 2, 3
 LAYER_QUAD, LAYER_LINES = 0, 1
 
@@ -44,6 +45,12 @@ class PresentLayer(ctypes.Structure):
                 ("instance_offsets", ctypes.POINTER(ctypes.c_float)), ("instance_weights", ctypes.POINTER(ctypes.c_float)),
                 ("n_segments", ctypes.c_int), ("starts", ctypes.POINTER(ctypes.c_float)), ("ends", ctypes.POINTER(ctypes.c_float)),
                 ("transform", ctypes.c_float * 16), ("color", ctypes.c_float * 4), ("width_px", ctypes.c_float)]
+
+
+class CenterInfo(ctypes.Structure):
+    """struct tsp_center_info."""
+    _fields_ = [("n_valid", ctypes.c_int64), ("n_inside", ctypes.c_int64), ("iterations", ctypes.c_int32),
+                ("reserved", ctypes.c_int32), ("radius", ctypes.c_double), ("mass_inside", ctypes.c_double)]
 
 
 class BackendUnavailable(RuntimeError):
@@ -111,6 +118,9 @@ SIGNATURES = {
     "tsp_tile_periodic": (ctypes.c_int, [_ctx, ctypes.c_int, _fp, _fp]),
     "tsp_smoothing_lengths": (ctypes.c_int, [_ctx, ctypes.c_int64, _fp, _fp, _fp, ctypes.c_int, ctypes.c_float, _fp]),
     "tsp_sph_sum": (ctypes.c_int, [_ctx, ctypes.c_int64, _fp, _fp, _fp, _fp, _fp, ctypes.c_float, _fp]),
+    "tsp_shrink_sphere_center": (ctypes.c_int, [_ctx, ctypes.c_int64, _fp, _fp, _fp, _fp, ctypes.c_float, ctypes.c_double,
+                                                ctypes.c_double, ctypes.c_int64, ctypes.c_int, ctypes.POINTER(ctypes.c_double),
+                                                ctypes.POINTER(CenterInfo)]),
     "tsp_set_sphere_mips": (ctypes.c_int, [_ctx, _fp, ctypes.c_int, ctypes.c_int]),
     "tsp_density_order_stats": (ctypes.c_int, [_ctx, _i64p, ctypes.c_int, _fp]),
     "tsp_render_surface": (ctypes.c_int, [_ctx, _fp, ctypes.c_float, ctypes.c_float, _i64p, _i64p, ctypes.c_int, ctypes.c_int,
@@ -387,6 +397,23 @@ class Context:
         _check(self._lib.tsp_sph_sum(self._h, n, _ptr(x), _ptr(y), _ptr(z), _ptr(h), _ptr(a), float(np.float32(period or 0.0)),
                                      _ptr(out)))
         return out
+
+    def shrink_sphere_center(self, x, y, z, mass, mass_cut_factor=0.0, r_start=0.0, shrink_factor=0.7, min_particles=100,
+                             max_iterations=256):
+        """Shrinking-sphere centre of caller-ordered float32 particles (tsp_shrink_sphere_center): from the centre of mass, the
+        mass-weighted mean of the particles inside a sphere whose radius shrinks by shrink_factor per step, until fewer than
+        min_particles are inside.  mass_cut_factor > 1 keeps the particles lighter than that many times the smallest mass;
+        r_start = 0 starts from half the x extent.  Returns (center float64 (3,), dict(n_valid, n_inside, iterations, radius,
+        mass_inside)).  Uses this context's device only; what is resident stays."""
+        n = len(x)
+        x, y, z, mass = _f32(x, n, "x"), _f32(y, n, "y"), _f32(z, n, "z"), _f32(mass, n, "mass")
+        center = np.empty(3, dtype=np.float64)
+        info = CenterInfo()
+        _check(self._lib.tsp_shrink_sphere_center(self._h, n, _ptr(x), _ptr(y), _ptr(z), _ptr(mass), float(np.float32(mass_cut_factor)),
+                                                  float(r_start), float(shrink_factor), int(min_particles), int(max_iterations),
+                                                  center.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), ctypes.byref(info)))
+        return center, {"n_valid": int(info.n_valid), "n_inside": int(info.n_inside), "iterations": int(info.iterations),
+                        "radius": float(info.radius), "mass_inside": float(info.mass_inside)}
 
     # ---- surface (include/topsy_splat.h "Surface rendering") ---------------------------------
     def set_sphere_mips(self, mips, n0=64, n_levels=4):

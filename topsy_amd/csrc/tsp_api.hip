@@ -203,7 +203,7 @@ using namespace tsp;
 extern "C" {
 
 const char *tsp_last_error(void) { return g_err; }
-int tsp_version(void) { return 112; }     // 112: tsp_present_surface, tsp_present_surface_yuv420; 111: tsp_content_neg_inf; 110: tsp_sph_sum; 109: tsp_present_yuv420; 108: tsp_present; 107: surface rendering; 106: tsp_smoothing_lengths; 101: tsp_stats gained ms_mega, n_mega (16 bytes); 102: the per-kernel fragment counts (32 bytes); 103: n_chunk_culled (8 bytes); 104: matrix-core / kernel-I options removed; 105: kernel M's options removed (kernel G draws the mid footprints)
+int tsp_version(void) { return 113; }     // 113: tsp_shrink_sphere_center; 112: tsp_present_surface, tsp_present_surface_yuv420; 111: tsp_content_neg_inf; 110: tsp_sph_sum; 109: tsp_present_yuv420; 108: tsp_present; 107: surface rendering; 106: tsp_smoothing_lengths; 101: tsp_stats gained ms_mega, n_mega (16 bytes); 102: the per-kernel fragment counts (32 bytes); 103: n_chunk_culled (8 bytes); 104: matrix-core / kernel-I options removed; 105: kernel M's options removed (kernel G draws the mid footprints)
 int tsp_stats_size(void) { return (int)sizeof(tsp_stats); }
 
 int tsp_device_count(void) {
@@ -779,6 +779,22 @@ int tsp_sph_sum(tsp_context *ctx, int64_t n, const float *x, const float *y, con
                 "period must be 0 (open box) or finite and > 0, not %g", (double)period);
     TSP_HIP(hipSetDevice(ctx->device));
     return sph_sum(ctx, n, x, y, z, h, a, period == 0.0f ? 0.0f : period, out);
+}
+
+int tsp_shrink_sphere_center(tsp_context *ctx, int64_t n, const float *x, const float *y, const float *z, const float *mass,
+                             float mass_cut_factor, double r_start, double shrink_factor, int64_t min_particles,
+                             int max_iterations, double center_out[3], tsp_center_info *info_out) {
+    TSP_REQUIRE(ctx && x && y && z && mass && center_out, TSP_EINVAL, "NULL argument");
+    TSP_REQUIRE(n >= 1 && n < (1ll << 31), TSP_EINVAL, "n = %lld outside [1, 2^31)", (long long)n);
+    TSP_REQUIRE(shrink_factor > 0.0 && shrink_factor < 1.0, TSP_EINVAL, "shrink_factor = %g outside (0, 1)", shrink_factor);
+    TSP_REQUIRE(min_particles >= 1, TSP_EINVAL, "min_particles = %lld below 1", (long long)min_particles);
+    TSP_REQUIRE(max_iterations >= 0 && max_iterations <= 256, TSP_EINVAL, "max_iterations = %d outside [0, 256]", max_iterations);
+    TSP_REQUIRE(std::isfinite(r_start) && r_start >= 0.0, TSP_EINVAL, "r_start must be 0 (estimated) or finite and > 0, not %g", r_start);
+    TSP_REQUIRE(mass_cut_factor == 0.0f || (std::isfinite(mass_cut_factor) && mass_cut_factor > 1.0f), TSP_EINVAL,
+                "mass_cut_factor must be 0 (no selection) or finite and > 1, not %g", (double)mass_cut_factor);
+    TSP_HIP(hipSetDevice(ctx->device));
+    return shrink_sphere_center(ctx, n, x, y, z, mass, mass_cut_factor == 0.0f ? 0.0f : mass_cut_factor, r_start == 0.0 ? 0.0 : r_start,
+                                shrink_factor, min_particles, max_iterations, center_out, info_out);
 }
 
 int tsp_present(tsp_context *ctx, int width, int height, const tsp_present_base *base, const tsp_present_layer *layers,

@@ -252,6 +252,10 @@ int smoothing_lengths(tsp_context *ctx, int64_t n, const float *x, const float *
                       float *h_out);   // tsp_smooth.hip: per-call DeviceScratch only, no context state
 int sph_sum(tsp_context *ctx, int64_t n, const float *x, const float *y, const float *z, const float *h, const float *a,
             float period, float *out);       // tsp_smooth.hip: the gather-form SPH sum on the same index; per-call DeviceScratch only
+// tsp_center.hip: the shrinking-sphere centre of caller-ordered host arrays; per-call DeviceScratch only, no context state
+int shrink_sphere_center(tsp_context *ctx, int64_t n, const float *x, const float *y, const float *z, const float *mass,
+                         float mass_cut_factor, double r_start, double shrink_factor, int64_t min_particles, int max_iterations,
+                         double center_out[3], tsp_center_info *info_out);
 // tsp_surface.hip: the occlusion pass + resolve (keys in image64, (q, depth) in image), the rho order statistics and the
 // filter + shading; per-call memory is DeviceScratch
 int render_surface(tsp_context *ctx, const Camera &cam, float cut, const int64_t *h_starts, const int64_t *h_lens,

@@ -174,6 +174,45 @@ def check_smoothing_arguments(n_smooth, periodicity_scale):
     return int(n_smooth), period
 
 
+ZOOM_MASS_CUT_FACTOR = 1.01      # center="zoom": the particles with mass < 1.01 * mass.min() (reference loader.py:210-211)
+
+
+def check_center_arguments(select="all", r_start=None, shrink_factor=0.7, min_particles=100):
+    """The arguments of a shrinking-sphere centre, checked on the host (tsp_shrink_sphere_center would refuse them): returns
+    (mass_cut_factor, r_start as float with 0 = estimated, shrink_factor, min_particles).  Raises ValueError."""
+    if select not in ("all", "zoom"):
+        raise ValueError(f"select must be 'all' or 'zoom', not {select!r}")
+    try:
+        r0 = 0.0 if r_start is None else float(r_start)
+        shrink = float(shrink_factor)
+    except (TypeError, ValueError):
+        raise ValueError(f"r_start and shrink_factor must be numbers, not {r_start!r} and {shrink_factor!r}") from None
+    if r_start is not None and not (np.isfinite(r0) and r0 > 0):
+        raise ValueError(f"r_start must be None or a finite number > 0, not {r_start!r}")
+    if not 0.0 < shrink < 1.0:
+        raise ValueError(f"shrink_factor must lie strictly between 0 and 1, not {shrink_factor!r}")
+    if isinstance(min_particles, bool) or not isinstance(min_particles, (int, np.integer)) or min_particles < 1:
+        raise ValueError(f"min_particles must be an integer >= 1, not {min_particles!r}")
+    return (ZOOM_MASS_CUT_FACTOR if select == "zoom" else 0.0), r0, shrink, int(min_particles)
+
+
+def check_center_option(center):
+    """The center= option of ArrayDataLoader / from_arrays: returns "none", "all", "zoom" or a float64 (3,) array.  Raises
+    ValueError."""
+    if isinstance(center, str):
+        if center not in ("none", "all", "zoom"):
+            raise ValueError(f"center must be 'none', 'all', 'zoom' or three coordinates, not {center!r} "
+                             f"('halo-N' needs a halo catalogue, which arrays do not carry)")
+        return center
+    try:
+        c = np.asarray(center, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError(f"center must be 'none', 'all', 'zoom' or three coordinates, not {center!r}") from None
+    if c.shape != (3,) or not np.isfinite(c).all():
+        raise ValueError(f"center must be 'none', 'all', 'zoom' or three finite coordinates, not {center!r}")
+    return c.copy()
+
+
 class ArrayDataLoader(AbstractDataLoader):
     """Particles given as numpy arrays (e.g. pulled from a pynbody snapshot by the caller:
     snap['pos'], snap['smooth'], snap['mass'], ...; reference PynbodyDataInMemory, loader.py:79-154).
@@ -185,14 +224,24 @@ class ArrayDataLoader(AbstractDataLoader):
     'rho' is always a quantity, as it is for every pynbody family (the reference hands any such name to the renderer,
     loader.py:123-127): quantities["rho"] when the caller supplied one, else the gather-form SPH density of the particles,
     computed on the GPU at the first get_named_quantity("rho") -- by the visualizer's context once ParticleBuffers has set it
-    (set_density_context), else by a context of its own -- and cached; set_density() restores it from the caller's cache."""
+    (set_density_context), else by a context of its own -- and cached; set_density() restores it from the caller's cache.
+
+    center: where the view opens (the reference centres the snapshot at load, loader.py:201-217).  "none": the origin;
+    "all": the shrinking-sphere centre of every particle; "zoom": that of the lightest mass species (mass < 1.01 * mass.min());
+    three coordinates: that point.  get_initial_center() computes the centre on the GPU (tsp_shrink_sphere_center) on first use
+    -- on the same context as 'rho', from the host arrays, on the first device when there are several -- and caches it;
+    set_initial_center() restores it from the caller's cache.  The particles are not moved: the camera is.  Out of scope:
+    periodic wrapping of the displacements, "halo-N" (needs a halo catalogue), and DeviceSyntheticLoader (no host arrays)."""
 
     # reference PynbodyDataInMemory.get_rgb_masses (loader.py:115-121): (band, weight) per rgb channel
     RGB_BANDS = (("I", 0.5), ("V", 1.0), ("U", 1.0))
 
     def __init__(self, device=None, pos=None, smooth=None, mass=None, quantities=None, rgb=None,
-                 units="kpc", periodicity_scale=None, with_cells=False, band_magnitudes=None, n_smooth=None):
+                 units="kpc", periodicity_scale=None, with_cells=False, band_magnitudes=None, n_smooth=None,
+                 center="none"):
         super().__init__(device)
+        self._center_option = check_center_option(center)
+        self._center = None              # the initial centre once known (float64 (3,))
         self._pos = np.asarray(pos, dtype=np.float32)
         self.needs_smoothing = smooth is None
         self.n_smooth = config.SMOOTH_NEIGHBOURS if n_smooth is None else n_smooth
@@ -215,6 +264,12 @@ class ArrayDataLoader(AbstractDataLoader):
                 raise ValueError("pos and mass must have the same length")
         elif not (len(self._pos) == len(self._smooth) == len(self._mass)):
             raise ValueError("pos, smooth and mass must have the same length")
+        if isinstance(self._center_option, str) and self._center_option != "none":
+            if self._pos.ndim != 2 or self._pos.shape[1] != 3:
+                raise ValueError(f"center={self._center_option!r} needs pos of shape (n, 3), not {self._pos.shape}")
+            if self._mass.shape != (len(self._pos),) or len(self._pos) == 0:
+                raise ValueError(f"center={self._center_option!r} needs one mass per particle: mass has shape {self._mass.shape}, "
+                                 f"pos {self._pos.shape}")
         if with_cells:
             # cell sort + shuffle inside cells, as PynbodyDataInMemory.__init__ (loader.py:88-97)
             lo, hi = self._pos.min(), self._pos.max()
@@ -295,6 +350,37 @@ class ArrayDataLoader(AbstractDataLoader):
                 if own:
                     ctx.close()
         return self._rho
+
+    def get_initial_center(self):
+        if isinstance(self._center_option, str) and self._center_option == "none":
+            return super().get_initial_center()
+        if self._center is None:
+            if not isinstance(self._center_option, str):
+                self._center = self._center_option
+            else:
+                cut, r0, shrink, min_particles = check_center_arguments(self._center_option)
+                ctx = self._density_context
+                own = ctx is None
+                if own:
+                    from . import _native
+                    ctx = _native.Context(1, 2, self._device if isinstance(self._device, int) else 0)
+                try:
+                    self._center, self.center_info = ctx.shrink_sphere_center(
+                        self._pos[:, 0], self._pos[:, 1], self._pos[:, 2], self._mass, mass_cut_factor=cut, r_start=r0,
+                        shrink_factor=shrink, min_particles=min_particles)
+                finally:
+                    if own:
+                        ctx.close()
+        return self._center
+
+    def set_initial_center(self, center):
+        """The initial centre (e.g. from the caller's cache, next to set_smooth / set_density): it is then not computed."""
+        center = np.asarray(center, dtype=np.float64)
+        if center.shape != (3,) or not np.isfinite(center).all():
+            raise ValueError(f"center must be three finite coordinates, not {center!r}")
+        if isinstance(self._center_option, str) and self._center_option == "none":
+            self._center_option = center.copy()
+        self._center = center.copy()
 
     def get_quantity_label(self, quantity_name):
         return "density" if quantity_name is None else quantity_name

@@ -205,6 +205,10 @@ class MultiGpuContext:
         """The SPH sum over the whole (caller-ordered) snapshot, on the first context like smoothing_lengths."""
         return self.contexts[0].sph_sum(x, y, z, h, a, period)
 
+    def shrink_sphere_center(self, x, y, z, mass, **kwargs):
+        """The shrinking-sphere centre of the whole (caller-ordered) snapshot, on the first context like smoothing_lengths."""
+        return self.contexts[0].shrink_sphere_center(x, y, z, mass, **kwargs)
+
     def generate_synthetic(self, n_total, first=0, count=None, seed=1337, h_cap=0.0, with_quantity=False, with_rgb=False):
         count = n_total - first if count is None else count
         # the generator's index bijection makes every index range a uniform sample: contiguous shards are balanced

@@ -184,6 +184,10 @@ class SurfaceView:
     def position_offset(self, value):
         self._vis.position_offset = value
 
+    def centre_on_pixel(self, row, col):
+        """The visualizer's centre_on_pixel: (row, col) index the shared R x R image; the camera is the visualizer's."""
+        return self._vis.centre_on_pixel(row, col)
+
     @property
     def quantity_name(self):
         return self._vis.quantity_name

@@ -343,6 +343,22 @@ class VisualizerBase:
         self.invalidate(DrawReason.CHANGE)
         return depth
 
+    def centre_on_pixel(self, row, col):
+        """Move position_offset so that the point drawn at pixel (row, col) of get_sph_image() comes to the image centre and,
+        where get_depth_image() is finite at that pixel, its depth to the view plane: the arithmetic of the reference canvas's
+        double click (canvas/__init__.py:105-129) without the glide.  Returns the new offset."""
+        res = self._render_resolution
+        row, col = int(row), int(col)
+        if not (0 <= row < res and 0 <= col < res):
+            raise ValueError(f"pixel ({row}, {col}) outside the {res} x {res} image")
+        # pixel centres in view coordinates: column j at x = ((j + 0.5) * 2 / R - 1) * scale, row i at y = (1 - (i + 0.5) * 2 / R) * scale
+        view = np.array([((col + 0.5) * 2.0 / res - 1.0) * self.scale, (1.0 - (row + 0.5) * 2.0 / res) * self.scale, 0.0])
+        depth = float(self.get_depth_image()[row, col])     # the line-of-sight position at the pixel, before any move
+        if np.isfinite(depth):
+            view[2] = depth
+        self.position_offset = np.asarray(self.position_offset, dtype=np.float64) - np.asarray(self.rotation_matrix).T @ view
+        return self.position_offset
+
     def save(self, filename="output.npy"):
         self._sph.render(DrawReason.EXPORT)
         if filename.endswith(".npy"):
