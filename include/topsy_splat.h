@@ -86,7 +86,9 @@ const char *tsp_last_error(void);
  * 111: new entry point tsp_content_neg_inf (how many content values of the last tsp_content_sort were -inf); nothing else changed.
  * 112: surface frames: tsp_present_surface and tsp_present_surface_yuv420 (the lit surface composed onto a canvas of any size under
  * the layers of tsp_present, and that frame as I420 planes); no struct changed, nothing else changed.
- * 113: new entry point tsp_shrink_sphere_center and the struct tsp_center_info (a snapshot's centre); nothing else changed. */
+ * 113: new entry point tsp_shrink_sphere_center and the struct tsp_center_info (a snapshot's centre); nothing else changed.
+ * 114: new entry point tsp_fof_groups and the struct tsp_fof_info (friends-of-friends groups: a halo catalogue for arrays);
+ * nothing else changed. */
 int tsp_version(void);
 int tsp_stats_size(void);
 
@@ -296,6 +298,32 @@ typedef struct {
 int tsp_shrink_sphere_center(tsp_context *ctx, int64_t n, const float *x, const float *y, const float *z, const float *mass,
                              float mass_cut_factor, double r_start, double shrink_factor, int64_t min_particles,
                              int max_iterations, double center_out[3], tsp_center_info *info_out);
+
+/* Friends-of-friends groups: the halo catalogue that arrays do not carry, which the reference's center = "halo-N" takes from
+ * pynbody (PynbodyDataLoader._perform_centering, src/topsy/loader.py:203-206).  Host arrays in and out, caller's order; uses
+ * ctx's device and stream only: resident particles, image, accumulator and tsp_stats unchanged.
+ *   - Valid particles.  Particle i is valid iff x[i], y[i], z[i] are finite.  An invalid particle gets group_out[i] = -1 and is
+ *     nobody's friend, so it never bridges two groups.
+ *   - Links.  Two valid particles i != j are linked iff d2 <= ll2, where d2 is exactly the float32 expression
+ *     tsp_smoothing_lengths defines (period > 0: the nearest image by dx - period * rint(dx / period)) and
+ *     ll2 = linking_length * linking_length in float32.  A pair at exactly ll2 is linked.  Every step of d2 is odd-symmetric in
+ *     dx, so d2(i, j) and d2(j, i) are the same bits: the relation is symmetric.
+ *   - Groups.  The connected components of that graph; the size of a group is its member count.  The groups with
+ *     size >= min_members are ranked 1, 2, ... by size descending, ties by the smaller smallest member index (caller's order).
+ *     group_out[i] = the rank of i's group, or 0 for a valid particle whose group is too small.
+ *   - info_out (optional): n_valid; n_groups = the number of ranked groups; n_grouped = the particles with rank >= 1;
+ *     largest = the size of group 1, or 0.
+ *   - Determinism.  Everything is an integer and the partition is unique: the same input gives the same output whatever order
+ *     the atomics of the union-find resolve in.
+ * 1 <= n < 2^31, linking_length finite and > 0, period = 0 (open box) or finite and > 0 with linking_length < period / 2,
+ * min_members >= 1, no NULL array; anything else returns TSP_EINVAL and writes nothing.  The cost is proportional to the
+ * candidates tested: a linking length of the order of the box is slow, not wrong.  Device memory is allocated for the call only
+ * (about 48 bytes per particle); a failed allocation returns TSP_ENOMEM and writes nothing. */
+typedef struct {
+    int64_t n_valid, n_groups, n_grouped, largest;
+} tsp_fof_info;
+int tsp_fof_groups(tsp_context *ctx, int64_t n, const float *x, const float *y, const float *z, float linking_length,
+                   float period, int64_t min_members, int32_t *group_out, tsp_fof_info *info_out);
 
 /* Surface rendering: DepthSPHWithOcclusion + ColorAsSurfaceMap (reference src/topsy/sph.py:448-656, shaders/sph.wgsl:94-122,
  * 149-158, shaders/smooth.wgsl, shaders/surface.wgsl, colormap/surface.py).  Float32 throughout, operations in the order written.

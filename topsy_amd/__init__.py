@@ -26,7 +26,7 @@ def test(nparticle=config.TEST_DATA_NUM_PARTICLES_DEFAULT, **kwargs):
 
 
 def from_arrays(pos, smooth, mass, quantities=None, rgb=None, with_cells=False, n_smooth=None, periodicity_scale=None,
-                center="none", **kwargs):
+                center="none", halos=None, **kwargs):
     """Visualizer over caller-supplied numpy arrays (e.g. taken from a pynbody snapshot).
 
     smooth=None computes the smoothing lengths on the GPU from the n_smooth (default config.SMOOTH_NEIGHBOURS) nearest
@@ -38,13 +38,18 @@ def from_arrays(pos, smooth, mass, quantities=None, rgb=None, with_cells=False, 
 
     center: where the view opens -- "none" (the origin), "all" (the shrinking-sphere centre of the particles, found on the GPU:
     shrink_sphere_center), "zoom" (that of the lightest mass species) or three coordinates.  vis.data_loader.get_initial_center()
-    returns it, set_initial_center() restores it from the caller's own cache."""
+    returns it, set_initial_center() restores it from the caller's own cache.
+
+    halos: the halo catalogue -- "fof" (friends-of-friends groups found on the GPU: friends_of_friends, in the periodic box of
+    periodicity_scale if one is given), a dict of its keywords (linking_length, b, min_members), or your own integer (n,) labels
+    (halo N is label N; <= 0: no halo).  With it center="halo-N" opens the view on halo N (1 = the largest) and
+    vis.centre_on_halo(N) jumps there; vis.data_loader.get_halos() returns the catalogue, set_halos() restores it."""
     from . import visualizer, loader
     return visualizer.Visualizer(data_loader_class=loader.ArrayDataLoader,
                                  data_loader_kwargs={"pos": pos, "smooth": smooth, "mass": mass,
                                                      "quantities": quantities, "rgb": rgb, "with_cells": with_cells,
                                                      "n_smooth": n_smooth, "periodicity_scale": periodicity_scale,
-                                                     "center": center},
+                                                     "center": center, "halos": halos},
                                  **kwargs)
 
 
@@ -133,7 +138,8 @@ def shrink_sphere_center(pos, mass, select="all", r_start=None, shrink_factor=0.
     until fewer than min_particles are inside.  select="zoom" uses the lightest mass species only (mass < 1.01 * mass.min(),
     the reference's center="zoom").  Particles with a non-finite coordinate or a mass that is not finite and > 0 take no part.
     Returns (center float64 (3,), dict(n_valid, n_inside, iterations, radius, mass_inside)).
-    Out of scope: periodic wrapping of the displacements, "halo-N" centres (they need a halo catalogue)."""
+    Out of scope: periodic wrapping of the displacements.  The centre of one halo: friends_of_friends(pos).members(N) selects
+    its particles; from_arrays(..., halos="fof", center="halo-N") does both."""
     from . import _native, loader
     cut, r0, shrink, min_particles = loader.check_center_arguments(select, r_start, shrink_factor, min_particles)
     pos = np.asarray(pos, dtype=np.float32)
@@ -155,6 +161,25 @@ def shrink_sphere_center(pos, mass, select="all", r_start=None, shrink_factor=0.
         ctx.close()
 
 
+def friends_of_friends(pos, linking_length=None, b=0.2, min_members=20, periodicity_scale=None, device_id=0):
+    """Friends-of-friends groups of an (n, 3) position array on GPU `device_id` (C: tsp_fof_groups): particles closer than
+    linking_length are friends (nearest image in a periodic box of side periodicity_scale), the groups are the connected
+    components.  linking_length=None: b times the mean separation (V / n_valid) ** (1/3), V = periodicity_scale ** 3 or the
+    volume of the bounding box of the finite positions.  Returns a FofCatalogue: .group (int32 (n,): N >= 1 = the N-th largest
+    group with at least min_members members, 0 = a smaller one, -1 = a non-finite coordinate), .sizes (int64, sizes[N - 1]),
+    len(), .members(N), .linking_length, .info."""
+    from . import _native, loader
+    ll, b, min_members, period = loader.check_fof_arguments(linking_length, b, min_members, periodicity_scale)
+    pos = loader.check_fof_positions(pos)
+    if ll is None:
+        ll = loader.fof_linking_length(pos, b, period)
+    ctx = _native.Context(1, 2, device_id)
+    try:
+        return loader.compute_fof_catalogue(ctx, pos, ll, b, min_members, period)
+    finally:
+        ctx.close()
+
+
 def SurfaceView(visualizer, **colormap_params):
     """Surface rendering of `visualizer`'s scene (the reference's render_mode "surface"): the front-most sphere of every
     particle above a density cut, smoothed and lit.  render(), get_sph_image() ((R, R, 2) filtered (q, depth)),
@@ -164,7 +189,11 @@ def SurfaceView(visualizer, **colormap_params):
 
 
 def __getattr__(name):
-    """topsy_amd.VisualizationRecorder (movie recording and export, topsy_amd/recorder), imported on first use."""
+    """topsy_amd.VisualizationRecorder (movie recording and export, topsy_amd/recorder) and topsy_amd.FofCatalogue
+    (topsy_amd/loader.py), imported on first use."""
+    if name == "FofCatalogue":
+        from .loader import FofCatalogue
+        return FofCatalogue
     if name == "VisualizationRecorder":
         from .recorder import VisualizationRecorder
         return VisualizationRecorder

@@ -17,7 +17,7 @@ PIPE_DEFAULT, PIPE_GENERIC = 0, 1
 SAMPLE_BILINEAR_MIP0, SAMPLE_BILINEAR_MIP = 0x10, 0x20      # diagnostic sampling rules (generic kernel)
 UNIQUE_ID_BYTES = 128
 ABI_VERSION = 112            # the oldest tsp_version() whose structs this binding matches; entry points added since
-                             # (113: tsp_shrink_sphere_center) are required by name in load_library()
+                             # (113: tsp_shrink_sphere_center, 114: tsp_fof_groups) are required by name in load_library()
 PRESENT_SCALAR, PRESENT_BIVARIATE, PRESENT_RGB, PRESENT_RGB_HDR = 0, 1, 2, 3
 LAYER_QUAD, LAYER_LINES = 0, 1
 
@@ -51,6 +51,12 @@ class CenterInfo(ctypes.Structure):
     """struct tsp_center_info."""
     _fields_ = [("n_valid", ctypes.c_int64), ("n_inside", ctypes.c_int64), ("iterations", ctypes.c_int32),
                 ("reserved", ctypes.c_int32), ("radius", ctypes.c_double), ("mass_inside", ctypes.c_double)]
+
+
+class FofInfo(ctypes.Structure):
+    """struct tsp_fof_info."""
+    _fields_ = [("n_valid", ctypes.c_int64), ("n_groups", ctypes.c_int64), ("n_grouped", ctypes.c_int64),
+                ("largest", ctypes.c_int64)]
 
 
 class BackendUnavailable(RuntimeError):
@@ -121,6 +127,8 @@ SIGNATURES = {
     "tsp_shrink_sphere_center": (ctypes.c_int, [_ctx, ctypes.c_int64, _fp, _fp, _fp, _fp, ctypes.c_float, ctypes.c_double,
                                                 ctypes.c_double, ctypes.c_int64, ctypes.c_int, ctypes.POINTER(ctypes.c_double),
                                                 ctypes.POINTER(CenterInfo)]),
+    "tsp_fof_groups": (ctypes.c_int, [_ctx, ctypes.c_int64, _fp, _fp, _fp, ctypes.c_float, ctypes.c_float, ctypes.c_int64,
+                                      ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(FofInfo)]),
     "tsp_set_sphere_mips": (ctypes.c_int, [_ctx, _fp, ctypes.c_int, ctypes.c_int]),
     "tsp_density_order_stats": (ctypes.c_int, [_ctx, _i64p, ctypes.c_int, _fp]),
     "tsp_render_surface": (ctypes.c_int, [_ctx, _fp, ctypes.c_float, ctypes.c_float, _i64p, _i64p, ctypes.c_int, ctypes.c_int,
@@ -414,6 +422,22 @@ class Context:
                                                   center.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), ctypes.byref(info)))
         return center, {"n_valid": int(info.n_valid), "n_inside": int(info.n_inside), "iterations": int(info.iterations),
                         "radius": float(info.radius), "mass_inside": float(info.mass_inside)}
+
+    def fof_groups(self, x, y, z, linking_length, period=0.0, min_members=20):
+        """Friends-of-friends groups of caller-ordered float32 positions (tsp_fof_groups): particles closer than linking_length
+        (nearest image in a periodic box of side `period`; None or 0: open) are friends, the groups are the connected
+        components.  Returns (int32 (n,) labels, dict(n_valid, n_groups, n_grouped, largest)): label N >= 1 is the N-th largest
+        group with at least min_members members, 0 a smaller one, -1 a particle with a non-finite coordinate.  Uses this
+        context's device only; what is resident stays."""
+        n = len(x)
+        x, y, z = _f32(x, n, "x"), _f32(y, n, "y"), _f32(z, n, "z")
+        out = np.empty(n, dtype=np.int32)
+        info = FofInfo()
+        _check(self._lib.tsp_fof_groups(self._h, n, _ptr(x), _ptr(y), _ptr(z), float(np.float32(linking_length)),
+                                        float(np.float32(period or 0.0)), int(min_members),
+                                        out.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), ctypes.byref(info)))
+        return out, {"n_valid": int(info.n_valid), "n_groups": int(info.n_groups), "n_grouped": int(info.n_grouped),
+                     "largest": int(info.largest)}
 
     # ---- surface (include/topsy_splat.h "Surface rendering") ---------------------------------
     def set_sphere_mips(self, mips, n0=64, n_levels=4):

@@ -203,7 +203,7 @@ using namespace tsp;
 extern "C" {
 
 const char *tsp_last_error(void) { return g_err; }
-int tsp_version(void) { return 113; }     // 113: tsp_shrink_sphere_center; 112: tsp_present_surface, tsp_present_surface_yuv420; 111: tsp_content_neg_inf; 110: tsp_sph_sum; 109: tsp_present_yuv420; 108: tsp_present; 107: surface rendering; 106: tsp_smoothing_lengths; 101: tsp_stats gained ms_mega, n_mega (16 bytes); 102: the per-kernel fragment counts (32 bytes); 103: n_chunk_culled (8 bytes); 104: matrix-core / kernel-I options removed; 105: kernel M's options removed (kernel G draws the mid footprints)
+int tsp_version(void) { return 114; }     // 114: tsp_fof_groups; 113: tsp_shrink_sphere_center; 112: tsp_present_surface, tsp_present_surface_yuv420; 111: tsp_content_neg_inf; 110: tsp_sph_sum; 109: tsp_present_yuv420; 108: tsp_present; 107: surface rendering; 106: tsp_smoothing_lengths; 101: tsp_stats gained ms_mega, n_mega (16 bytes); 102: the per-kernel fragment counts (32 bytes); 103: n_chunk_culled (8 bytes); 104: matrix-core / kernel-I options removed; 105: kernel M's options removed (kernel G draws the mid footprints)
 int tsp_stats_size(void) { return (int)sizeof(tsp_stats); }
 
 int tsp_device_count(void) {
@@ -795,6 +795,21 @@ int tsp_shrink_sphere_center(tsp_context *ctx, int64_t n, const float *x, const 
     TSP_HIP(hipSetDevice(ctx->device));
     return shrink_sphere_center(ctx, n, x, y, z, mass, mass_cut_factor == 0.0f ? 0.0f : mass_cut_factor, r_start == 0.0 ? 0.0 : r_start,
                                 shrink_factor, min_particles, max_iterations, center_out, info_out);
+}
+
+int tsp_fof_groups(tsp_context *ctx, int64_t n, const float *x, const float *y, const float *z, float linking_length, float period,
+                   int64_t min_members, int32_t *group_out, tsp_fof_info *info_out) {
+    TSP_REQUIRE(ctx && x && y && z && group_out, TSP_EINVAL, "NULL argument");
+    TSP_REQUIRE(n >= 1 && n < (1ll << 31), TSP_EINVAL, "n = %lld outside [1, 2^31)", (long long)n);
+    TSP_REQUIRE(std::isfinite(linking_length) && linking_length > 0.0f, TSP_EINVAL, "linking_length must be finite and > 0, not %g",
+                (double)linking_length);
+    TSP_REQUIRE(period == 0.0f || (std::isfinite(period) && period > 0.0f), TSP_EINVAL,
+                "period must be 0 (open box) or finite and > 0, not %g", (double)period);
+    TSP_REQUIRE(period == 0.0f || linking_length < 0.5f * period, TSP_EINVAL, "linking_length = %g must be below period / 2 = %g",
+                (double)linking_length, 0.5 * (double)period);
+    TSP_REQUIRE(min_members >= 1, TSP_EINVAL, "min_members = %lld below 1", (long long)min_members);
+    TSP_HIP(hipSetDevice(ctx->device));
+    return fof_groups(ctx, n, x, y, z, linking_length, period == 0.0f ? 0.0f : period, min_members, group_out, info_out);
 }
 
 int tsp_present(tsp_context *ctx, int width, int height, const tsp_present_base *base, const tsp_present_layer *layers,

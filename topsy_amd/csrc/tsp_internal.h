@@ -252,6 +252,9 @@ int smoothing_lengths(tsp_context *ctx, int64_t n, const float *x, const float *
                       float *h_out);   // tsp_smooth.hip: per-call DeviceScratch only, no context state
 int sph_sum(tsp_context *ctx, int64_t n, const float *x, const float *y, const float *z, const float *h, const float *a,
             float period, float *out);       // tsp_smooth.hip: the gather-form SPH sum on the same index; per-call DeviceScratch only
+// tsp_fof.hip: friends-of-friends groups over the index of tsp_morton.h; per-call DeviceScratch only, no context state
+int fof_groups(tsp_context *ctx, int64_t n, const float *x, const float *y, const float *z, float linking_length, float period,
+               int64_t min_members, int32_t *group_out, tsp_fof_info *info_out);
 // tsp_center.hip: the shrinking-sphere centre of caller-ordered host arrays; per-call DeviceScratch only, no context state
 int shrink_sphere_center(tsp_context *ctx, int64_t n, const float *x, const float *y, const float *z, const float *mass,
                          float mass_cut_factor, double r_start, double shrink_factor, int64_t min_particles, int max_iterations,

@@ -3,7 +3,7 @@
 //
 // Contract (include/topsy_splat.h): for every particle i with finite coordinates, h[i] = 0.5 * sqrt(the k-th smallest
 // d2 = (dx*dx + dy*dy) + dz*dz over every particle j with finite coordinates, j = i included), in float32 with the operation
-// order written out in dist2() below; a periodic box first maps each dx to its nearest image, dx - L * rint(dx / L).
+// order written out in dist2() (tsp_morton.h); a periodic box first maps each dx to its nearest image, dx - L * rint(dx / L).
 // A particle with a non-finite coordinate gets NaN and is nobody's neighbour.
 //
 // The search:
@@ -29,71 +29,10 @@
 #include <math.h>
 #include <stdlib.h>
 
-#include "tsp_internal.h"
+#include "tsp_morton.h"
 
 namespace tsp {
 namespace {
-
-constexpr int QBITS = 21;                          // quantisation steps per axis: 2^21 (3 x 21 = 63 key bits)
-constexpr int QMAX = (1 << QBITS) - 1;
-constexpr uint64_t INVALID_KEY = ~0ull;            // a particle with a non-finite coordinate: sorts after every valid key
-constexpr float CULL_SLACK = 1.0f + 1e-5f;         // relative slack of every comparison between a box distance and a d2
-
-struct Grid {
-    float lo[3];       // quantisation origin (0 for a periodic box)
-    float inv[3];      // steps per unit length; 0 on an axis of zero extent (every particle in step 0)
-    float step[3];     // length of one step (0 with inv = 0)
-    float eps;         // absolute margin of the box tests (rounding of the quantisation, the wrap and the cell faces)
-    float period;      // 0: open box
-};
-
-__device__ __forceinline__ bool finite3(float x, float y, float z) {
-    return __builtin_isfinite(x) && __builtin_isfinite(y) && __builtin_isfinite(z);
-}
-
-// the position binned on axis a: wrapped into [0, L) in a periodic box
-__device__ __forceinline__ float grid_coord(float v, float period) {
-    return period > 0.0f ? v - period * floorf(v / period) : v;
-}
-
-// floor((v - lo) * inv), held inside +-2^23 (enough for any box of half-width up to the whole domain; an overflowing
-// v - lo saturates instead of becoming undefined)
-__device__ __forceinline__ int qstep(float v, float lo, float inv) {
-    if (inv == 0.0f) return 0;
-    float t = (v - lo) * inv;
-    t = fminf(fmaxf(t, -8388608.0f), 8388608.0f);
-    return (int)floorf(t);
-}
-__device__ __forceinline__ int qclamp(int u) { return min(max(u, 0), QMAX); }
-
-__device__ __forceinline__ uint64_t spread3(uint64_t x) {     // 21 bits -> every third bit
-    x &= 0x1fffffull;
-    x = (x | x << 32) & 0x1f00000000ffffull;
-    x = (x | x << 16) & 0x1f0000ff0000ffull;
-    x = (x | x << 8) & 0x100f00f00f00f00full;
-    x = (x | x << 4) & 0x10c30c30c30c30c3ull;
-    x = (x | x << 2) & 0x1249249249249249ull;
-    return x;
-}
-__device__ __forceinline__ uint64_t morton3(uint32_t a, uint32_t b, uint32_t c) {
-    return spread3(a) | (spread3(b) << 1) | (spread3(c) << 2);
-}
-
-// The contract's distance: float32, these operations in this order (-ffp-contract=off keeps them unfused).
-__device__ __forceinline__ float min_image(float d, float period) {
-    float t = __fdiv_rn(d, period);
-    t = rintf(t);
-    return d - period * t;
-}
-__device__ __forceinline__ float dist2(float qx, float qy, float qz, float px, float py, float pz, float period) {
-    float dx = px - qx, dy = py - qy, dz = pz - qz;
-    if (period > 0.0f) {
-        dx = min_image(dx, period);
-        dy = min_image(dy, period);
-        dz = min_image(dz, period);
-    }
-    return (dx * dx + dy * dy) + dz * dz;
-}
 
 // The k smallest values so far, ascending, in KP registers (KP = k rounded up to 8, 16, 32 or 64).  The first KP - k entries
 // hold -inf and are never displaced, so list[KP - 1] -- a compile-time index -- is always the k-th smallest value; every index
@@ -187,30 +126,6 @@ __global__ __launch_bounds__(256) void smooth_scatter_kernel(const float *__rest
         h[idx[i]] = i < nv ? h_sorted[i] : __builtin_nanf("");
 }
 
-// first index in [0, nv) whose key is >= key
-__device__ __forceinline__ int64_t key_lower_bound(const uint64_t *__restrict__ keys, int64_t nv, uint64_t key) {
-    int64_t lo = 0, hi = nv;
-    while (lo < hi) {
-        const int64_t mid = (lo + hi) >> 1;
-        if (keys[mid] < key) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
-
-// distance along one axis from q to the step interval [c 2^s, (c + 1) 2^s) of the grid (and its periodic images), less the margin
-__device__ __forceinline__ float axis_gap(const Grid &g, int a, float q, int c, int s) {
-    if (g.inv[a] == 0.0f) return 0.0f;
-    const float lo = g.lo[a] + ldexpf((float)c, s) * g.step[a];
-    const float hi = g.lo[a] + ldexpf((float)(c + 1), s) * g.step[a];
-    float d = fmaxf(fmaxf(lo - q, q - hi), 0.0f);
-    if (g.period > 0.0f) {
-        const float L = g.period;
-        d = fminf(d, fmaxf(fmaxf(lo + L - q, q - hi - L), 0.0f));
-        d = fminf(d, fmaxf(fmaxf(lo - L - q, q - hi + L), 0.0f));
-    }
-    return fmaxf(d - g.eps, 0.0f);
-}
-
 template <int KP>
 __global__ __launch_bounds__(256) void smooth_knn_kernel(const float *__restrict__ sx, const float *__restrict__ sy,
                                                          const float *__restrict__ sz, const uint64_t *__restrict__ keys,
@@ -233,50 +148,18 @@ __global__ __launch_bounds__(256) void smooth_knn_kernel(const float *__restrict
 
         // 3. the level at which the box of half-width R >= sqrt(r0) touches at most two cells per axis
         const float R = sqrtf(r0) * CULL_SLACK + g.eps;
-        const float q[3] = {grid_coord(qx, L), grid_coord(qy, L), grid_coord(qz, L)};
-        int uq[3], ua[3], ub[3];
-        for (int a = 0; a < 3; ++a) {
-            uq[a] = qclamp(qstep(q[a], g.lo[a], g.inv[a]));
-            ua[a] = qstep(q[a] - R, g.lo[a], g.inv[a]);
-            ub[a] = qstep(q[a] + R, g.lo[a], g.inv[a]);
-            if (L == 0.0f) {
-                ua[a] = qclamp(ua[a]);
-                ub[a] = qclamp(ub[a]);
-            }
-            ua[a] = min(ua[a], uq[a]);      // the own cell is inside the range even where the wrap rounds q up to L
-            ub[a] = max(ub[a], uq[a]);
-        }
-        int s = 0;
-        while (s < QBITS && ((ub[0] >> s) - (ua[0] >> s) > 1 || (ub[1] >> s) - (ua[1] >> s) > 1 || (ub[2] >> s) - (ua[2] >> s) > 1))
-            ++s;
-        const int level = QBITS - s;
-        const int ncell = 1 << level;
-        // per axis: the query's own cell, and the other cell the box touches (unwrapped index; equal to own when none)
-        int own[3], other[3];
-        for (int a = 0; a < 3; ++a) {
-            own[a] = uq[a] >> s;
-            const int ca = ua[a] >> s, cb = ub[a] >> s;
-            other[a] = (ncell == 1) ? own[a] : (ca != own[a] ? ca : cb);
-        }
+        const QueryCells qc = query_cells(g, qx, qy, qz, R);
         list_init(list, k);
         for (int combo = 0; combo < 8; ++combo) {
             int c[3];
-            bool skip = false;
-            for (int a = 0; a < 3; ++a) {
-                const bool second = (combo >> a) & 1;
-                if (second && other[a] == own[a]) skip = true;
-                c[a] = second ? other[a] : own[a];
-            }
-            if (skip) continue;
+            if (!combo_cell(qc, combo, c)) continue;
             const float bound = fminf(r0, list[KP - 1]) * CULL_SLACK;
-            const float gx = axis_gap(g, 0, q[0], c[0], s);
-            const float gy = axis_gap(g, 1, q[1], c[1], s);
-            const float gz = axis_gap(g, 2, q[2], c[2], s);
+            const float gx = axis_gap(g, 0, qc.q[0], c[0], qc.s);
+            const float gy = axis_gap(g, 1, qc.q[1], c[1], qc.s);
+            const float gz = axis_gap(g, 2, qc.q[2], c[2], qc.s);
             if ((gx * gx + gy * gy) + gz * gz > bound) continue;
-            const uint64_t prefix = morton3((uint32_t)(c[0] & (ncell - 1)), (uint32_t)(c[1] & (ncell - 1)), (uint32_t)(c[2] & (ncell - 1)));
-            const int shift = 3 * s;
-            const int64_t b = key_lower_bound(keys, nv, prefix << shift);
-            const int64_t e = key_lower_bound(keys, nv, (prefix + 1) << shift);
+            int64_t b, e;
+            cell_run(keys, nv, c, qc.s, b, e);
             for (int64_t j = b; j < e; ++j) list_insert(list, dist2(qx, qy, qz, sx[j], sy[j], sz[j], L));
             evaluated += (unsigned long long)(e - b);
         }
@@ -344,50 +227,10 @@ __global__ __launch_bounds__(256) void sph_sum_kernel(const float *__restrict__ 
         const float R = reach + g.eps;
         reach2 = reach * reach >= 1e-30f ? reach * reach : __builtin_inff();
         const double cull2 = ((double)reach * (double)reach) * (double)CULL_SLACK;
-        const float q[3] = {grid_coord(qx, L), grid_coord(qy, L), grid_coord(qz, L)};
-        int uq[3], ua[3], ub[3];
-        for (int a = 0; a < 3; ++a) {
-            uq[a] = qclamp(qstep(q[a], g.lo[a], g.inv[a]));
-            ua[a] = qstep(q[a] - R, g.lo[a], g.inv[a]);
-            ub[a] = qstep(q[a] + R, g.lo[a], g.inv[a]);
-            if (L == 0.0f) {
-                ua[a] = qclamp(ua[a]);
-                ub[a] = qclamp(ub[a]);
-            }
-            ua[a] = min(ua[a], uq[a]);
-            ub[a] = max(ub[a], uq[a]);
-        }
-        int s = 0;
-        while (s < QBITS && ((ub[0] >> s) - (ua[0] >> s) > 1 || (ub[1] >> s) - (ua[1] >> s) > 1 || (ub[2] >> s) - (ua[2] >> s) > 1))
-            ++s;
-        const int ncell = 1 << (QBITS - s);
-        int own[3], other[3];
-        for (int a = 0; a < 3; ++a) {
-            own[a] = uq[a] >> s;
-            const int ca = ua[a] >> s, cb = ub[a] >> s;
-            other[a] = (ncell == 1) ? own[a] : (ca != own[a] ? ca : cb);
-        }
-        for (int combo = 0; combo < 8; ++combo) {
-            int c[3];
-            bool skip = false;
-            for (int a = 0; a < 3; ++a) {
-                const bool second = (combo >> a) & 1;
-                if (second && other[a] == own[a]) skip = true;
-                c[a] = second ? other[a] : own[a];
-            }
-            if (skip) continue;
-            const double gx = axis_gap(g, 0, q[0], c[0], s);
-            const double gy = axis_gap(g, 1, q[1], c[1], s);
-            const double gz = axis_gap(g, 2, q[2], c[2], s);
-            if ((gx * gx + gy * gy) + gz * gz > cull2) continue;
-            const uint64_t prefix = morton3((uint32_t)(c[0] & (ncell - 1)), (uint32_t)(c[1] & (ncell - 1)), (uint32_t)(c[2] & (ncell - 1)));
-            const int shift = 3 * s;
-            const int64_t b = key_lower_bound(keys, nv, prefix << shift);
-            const int64_t e = key_lower_bound(keys, nv, (prefix + 1) << shift);
+        scanned = for_each_run(g, keys, nv, qx, qy, qz, R, cull2, [&](int combo, int64_t b, int64_t e) {
             run_b[threadIdx.x][combo] = (uint32_t)b;      // (nv < 2^31)
             run_e[threadIdx.x][combo] = (uint32_t)e;
-            scanned += (unsigned long long)(e - b);
-        }
+        });
     }
     __syncthreads();
 
@@ -422,28 +265,9 @@ __global__ __launch_bounds__(256) void sph_sum_kernel(const float *__restrict__ 
     }
 }
 
-#define SMOOTH_ALLOC(who, buf, bytes)                                                                                    \
-    do {                                                                                                                 \
-        const hipError_t e_ = (buf).alloc(bytes);                                                                        \
-        if (e_ != hipSuccess) {                                                                                          \
-            (void)hipGetLastError();                                                                                     \
-            tsp::set_error("%s: cannot allocate %zu bytes of device memory: %s", (who), (size_t)(bytes),                 \
-                           hipGetErrorString(e_));                                                                       \
-            return e_ == hipErrorOutOfMemory ? TSP_ENOMEM : TSP_EHIP;                                                    \
-        }                                                                                                                \
-    } while (0)
+}  // namespace
 
-// Step 1 of both entry points: the raw positions on the device (dx, dy, dz), the grid, the sorted keys (keys2) with the
-// sort's index (vals2: sorted -> caller's order), and the positions of the nv valid particles in Morton order (sx, sy, sz).
-// vals (n x 4 bytes) is free for the caller's per-query result once the sort is done.
-struct MortonIndex {
-    DeviceScratch dx, dy, dz, keys2, vals, vals2, sx, sy, sz, mm;
-    Grid g = {};
-    int64_t nv = 0;
-    unsigned grid = 0;                       // blocks of the grid-stride kernels
-    unsigned long long *d_count = nullptr;   // [0] valid particles, [1] .. [3] the caller's counters (zeroed)
-};
-
+// Step 1 of every entry point over the index (tsp_morton.h).
 // min_valid: the call is refused (TSP_EINVAL) when fewer particles have finite coordinates
 int build_morton_index(tsp_context *ctx, const char *who, int64_t n, const float *x, const float *y, const float *z, float period,
                        int min_valid, MortonIndex &ix) {
@@ -484,6 +308,7 @@ int build_morton_index(tsp_context *ctx, const char *who, int64_t n, const float
         if (hmm[a] > hmm[3 + a]) break;      // no finite particle at all
         maxabs = std::max(maxabs, std::max(fabs((double)lo), fabs((double)hi)));
         const double extent = period > 0.0f ? (double)period : (double)hi - (double)lo;
+        ix.extent[a] = extent;
         g.lo[a] = period > 0.0f ? 0.0f : lo;
         if (extent > 1e-30 && extent < 1e38) {
             g.inv[a] = (float)((double)(1 << QBITS) / extent);
@@ -525,8 +350,6 @@ int build_morton_index(tsp_context *ctx, const char *who, int64_t n, const float
     TSP_HIP(hipGetLastError());
     return TSP_OK;
 }
-
-}  // namespace
 
 int smoothing_lengths(tsp_context *ctx, int64_t n, const float *x, const float *y, const float *z, int k, float period,
                       float *h_out) {

@@ -5,6 +5,7 @@ The abstract surface and the synthetic TestDataLoader mirror reference src/topsy
 fed through `ArrayDataLoader` (positions / smoothing / mass / named quantities as numpy arrays),
 which is what the reference's PynbodyDataInMemory hands to its GPU buffers anyway.
 """
+import re
 from abc import ABC, abstractmethod
 
 import numpy as np
@@ -196,13 +197,144 @@ def check_center_arguments(select="all", r_start=None, shrink_factor=0.7, min_pa
     return (ZOOM_MASS_CUT_FACTOR if select == "zoom" else 0.0), r0, shrink, int(min_particles)
 
 
-def check_center_option(center):
-    """The center= option of ArrayDataLoader / from_arrays: returns "none", "all", "zoom" or a float64 (3,) array.  Raises
-    ValueError."""
+FOF_KEYWORDS = ("linking_length", "b", "min_members")
+
+
+def check_fof_arguments(linking_length=None, b=0.2, min_members=20, periodicity_scale=None):
+    """The arguments of a friends-of-friends search, checked on the host (tsp_fof_groups would refuse them): returns
+    (linking_length as float or None = from b, b, min_members, period as float with 0 = open box).  Raises ValueError."""
+    def number(name, value):
+        if isinstance(value, (bool, str)):
+            raise ValueError(f"{name} must be a finite number > 0, not {value!r}")
+        try:
+            v = float(value)
+        except (TypeError, ValueError):
+            raise ValueError(f"{name} must be a finite number > 0, not {value!r}") from None
+        if not (np.isfinite(v) and v > 0 and np.isfinite(np.float32(v)) and np.float32(v) > 0):
+            raise ValueError(f"{name} must be a finite number > 0, not {value!r}")
+        return v
+    ll = None if linking_length is None else number("linking_length", linking_length)
+    b = number("b", b)
+    if isinstance(min_members, bool) or not isinstance(min_members, (int, np.integer)) or min_members < 1:
+        raise ValueError(f"min_members must be an integer >= 1, not {min_members!r}")
+    period = 0.0
+    if periodicity_scale is not None:
+        try:
+            period = number("periodicity_scale", periodicity_scale)
+        except ValueError:
+            raise ValueError(f"periodicity_scale must be None or a finite number > 0, not {periodicity_scale!r}") from None
+    if ll is not None and period > 0 and not np.float32(ll) < np.float32(0.5) * np.float32(period):
+        raise ValueError(f"linking_length = {linking_length!r} must be below half the periodicity_scale {periodicity_scale!r}")
+    return ll, b, int(min_members), period
+
+
+def fof_linking_length(pos, b, period):
+    """b times the mean separation of the particles with finite coordinates, (V / n_valid) ** (1/3) in float64: V = period ** 3
+    in a periodic box, else the volume of their bounding box.  Raises ValueError where that is no length."""
+    finite = np.isfinite(pos).all(axis=1)
+    n_valid = int(finite.sum())
+    if n_valid == 0:
+        raise ValueError("no particle has finite coordinates: the default linking_length needs at least one")
+    if period > 0:
+        volume = float(period) ** 3
+    else:
+        p = pos[finite].astype(np.float64)
+        extent = p.max(axis=0) - p.min(axis=0)
+        if not (extent > 0).all():
+            raise ValueError(f"the particles span no volume (extent {extent.tolist()}): pass an explicit linking_length")
+        volume = float(np.prod(extent))
+    ll = float(b) * (volume / n_valid) ** (1.0 / 3.0)
+    if not (np.isfinite(np.float32(ll)) and np.float32(ll) > 0):
+        raise ValueError(f"the default linking_length {ll!r} is no float32 length: pass an explicit linking_length")
+    if period > 0 and not np.float32(ll) < np.float32(0.5) * np.float32(period):
+        raise ValueError(f"the default linking_length {ll!r} is not below half the periodicity_scale {period!r}: "
+                         f"pass an explicit linking_length")
+    return ll
+
+
+def check_fof_positions(pos):
+    pos = np.asarray(pos, dtype=np.float32)
+    if pos.ndim != 2 or pos.shape[1] != 3:
+        raise ValueError(f"pos must have shape (n, 3), not {pos.shape}")
+    if len(pos) == 0:
+        raise ValueError("pos must have at least one particle")
+    return pos
+
+
+class FofCatalogue:
+    """A halo catalogue over n particles: .group, the int32 (n,) labels (N >= 1: halo N, the N-th largest; 0 or less: no halo);
+    .sizes, int64, sizes[N - 1] = the members of halo N; len() = the number of haloes; .members(N) = the indices of halo N;
+    .linking_length (None for a caller's own labels); .info, what tsp_fof_groups reported (None likewise)."""
+
+    def __init__(self, group, linking_length=None, info=None):
+        self.group = np.ascontiguousarray(group, dtype=np.int32)
+        self.linking_length = linking_length
+        self.info = info
+        labelled = self.group[self.group > 0]
+        self.sizes = np.bincount(labelled)[1:].astype(np.int64) if len(labelled) else np.zeros(0, dtype=np.int64)
+
+    def __len__(self):
+        return len(self.sizes)
+
+    def members(self, n):
+        if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or n < 1:
+            raise ValueError(f"halo numbers are integers >= 1, not {n!r}")
+        if n > len(self):
+            raise ValueError(f"halo {n} does not exist: the catalogue has {len(self)} halo(es)")
+        return np.flatnonzero(self.group == n)
+
+
+def compute_fof_catalogue(ctx, pos, linking_length, b, min_members, period):
+    """The catalogue of checked arguments (check_fof_arguments, check_fof_positions) on an existing context."""
+    ll = fof_linking_length(pos, b, period) if linking_length is None else linking_length
+    group, info = ctx.fof_groups(pos[:, 0], pos[:, 1], pos[:, 2], ll, period, min_members)
+    return FofCatalogue(group, float(np.float32(ll)), info)
+
+
+def check_halo_labels(labels, n):
+    """A caller's own catalogue: an integer (n,) array, label N >= 1 = halo N, anything <= 0 = no halo.  Raises ValueError."""
+    a = np.asarray(labels)
+    if a.dtype == bool or not np.issubdtype(a.dtype, np.integer):
+        raise ValueError(f"halo labels must be an integer array, not dtype {a.dtype}")
+    if a.shape != (n,):
+        raise ValueError(f"halo labels must have shape ({n},), not {a.shape}")
+    if a.size and (a.max() > np.iinfo(np.int32).max or a.min() < np.iinfo(np.int32).min):
+        raise ValueError("halo labels must fit 32 bits")
+    return a.astype(np.int32)
+
+
+def check_halos_option(halos, n, periodicity_scale):
+    """The halos= option of ArrayDataLoader / from_arrays: returns None, a dict of friends-of-friends keywords (checked) or an
+    int32 (n,) label array.  Raises ValueError."""
+    if halos is None:
+        return None
+    if isinstance(halos, str):
+        if halos != "fof":
+            raise ValueError(f"halos must be None, 'fof', a dict of {FOF_KEYWORDS} or an integer label array, not {halos!r}")
+        halos = {}
+    if isinstance(halos, dict):
+        unknown = sorted(set(halos) - set(FOF_KEYWORDS))
+        if unknown:
+            raise ValueError(f"halos: unknown friends-of-friends keyword(s) {unknown}; known: {FOF_KEYWORDS}")
+        check_fof_arguments(periodicity_scale=periodicity_scale, **halos)
+        return dict(halos)
+    return check_halo_labels(halos, n)
+
+
+_HALO_CENTER = re.compile(r"halo-([1-9][0-9]*)")
+
+
+def check_center_option(center, halos=None):
+    """The center= option of ArrayDataLoader / from_arrays: returns "none", "all", "zoom", "halo-N" (N >= 1; only with a halo
+    catalogue, halos=) or a float64 (3,) array.  Raises ValueError."""
     if isinstance(center, str):
+        if center.startswith("halo-") and halos is not None:
+            if not _HALO_CENTER.fullmatch(center):
+                raise ValueError(f"center={center!r}: the N of 'halo-N' must be an integer >= 1")
+            return center
         if center not in ("none", "all", "zoom"):
             raise ValueError(f"center must be 'none', 'all', 'zoom' or three coordinates, not {center!r} "
-                             f"('halo-N' needs a halo catalogue, which arrays do not carry)")
+                             f"('halo-N' needs a halo catalogue: pass halos='fof' or your own label array)")
         return center
     try:
         c = np.asarray(center, dtype=np.float64)
@@ -230,19 +362,31 @@ class ArrayDataLoader(AbstractDataLoader):
     "all": the shrinking-sphere centre of every particle; "zoom": that of the lightest mass species (mass < 1.01 * mass.min());
     three coordinates: that point.  get_initial_center() computes the centre on the GPU (tsp_shrink_sphere_center) on first use
     -- on the same context as 'rho', from the host arrays, on the first device when there are several -- and caches it;
-    set_initial_center() restores it from the caller's cache.  The particles are not moved: the camera is.  Out of scope:
-    periodic wrapping of the displacements, "halo-N" (needs a halo catalogue), and DeviceSyntheticLoader (no host arrays)."""
+    set_initial_center() restores it from the caller's cache.  The particles are not moved: the camera is.
+
+    halos: the halo catalogue (arrays carry none).  "fof": friends-of-friends groups found on the GPU (tsp_fof_groups) with the
+    defaults of topsy_amd.friends_of_friends, in the periodic box of periodicity_scale when one is given; a dict of its keywords
+    (linking_length, b, min_members); or the caller's own integer (n,) labels (halo N is label N, anything <= 0 is no halo;
+    permuted with the other arrays under with_cells).  get_halos() computes the catalogue on first use, on the same context as
+    'rho', and caches it; set_halos() restores it from the caller's cache.  With a catalogue, center="halo-N" (N >= 1, 1 = the
+    largest halo; the reference's --center halo-N, loader.py:203-206) opens the view on the shrinking-sphere centre of the
+    members of halo N (get_halo_center(N): in a periodic box the members are first unwrapped by nearest image around the
+    lowest-index member, and the centre is in those coordinates).  Out of scope: periodic wrapping of the displacements inside the
+    shrinking sphere itself, and DeviceSyntheticLoader (no host arrays)."""
 
     # reference PynbodyDataInMemory.get_rgb_masses (loader.py:115-121): (band, weight) per rgb channel
     RGB_BANDS = (("I", 0.5), ("V", 1.0), ("U", 1.0))
 
     def __init__(self, device=None, pos=None, smooth=None, mass=None, quantities=None, rgb=None,
                  units="kpc", periodicity_scale=None, with_cells=False, band_magnitudes=None, n_smooth=None,
-                 center="none"):
+                 center="none", halos=None):
         super().__init__(device)
-        self._center_option = check_center_option(center)
-        self._center = None              # the initial centre once known (float64 (3,))
         self._pos = np.asarray(pos, dtype=np.float32)
+        self._halos_option = check_halos_option(halos, len(self._pos), periodicity_scale)
+        self._halos = None               # the catalogue once known
+        self._halo_centers = {}          # N -> centre of halo N (float64 (3,))
+        self._center_option = check_center_option(center, self._halos_option)
+        self._center = None              # the initial centre once known (float64 (3,))
         self.needs_smoothing = smooth is None
         self.n_smooth = config.SMOOTH_NEIGHBOURS if n_smooth is None else n_smooth
         if self.needs_smoothing or n_smooth is not None:
@@ -285,6 +429,8 @@ class ArrayDataLoader(AbstractDataLoader):
                 self._rgb = self._rgb[order]
             if self._mags is not None:
                 self._mags = {k: v[order] for k, v in self._mags.items()}
+            if isinstance(self._halos_option, np.ndarray):
+                self._halos_option = self._halos_option[order]
 
     def __len__(self):
         return len(self._pos)
@@ -351,26 +497,81 @@ class ArrayDataLoader(AbstractDataLoader):
                     ctx.close()
         return self._rho
 
+    def _with_context(self, work):
+        """work(ctx) on the visualizer's context once it was handed over (set_density_context), else on one made for the call."""
+        ctx = self._density_context
+        own = ctx is None
+        if own:
+            from . import _native
+            ctx = _native.Context(1, 2, self._device if isinstance(self._device, int) else 0)
+        try:
+            return work(ctx)
+        finally:
+            if own:
+                ctx.close()
+
+    def get_halos(self):
+        """The halo catalogue (FofCatalogue) of halos=: computed on the GPU on first use unless the labels were supplied."""
+        if self._halos is None:
+            if self._halos_option is None:
+                raise ValueError("no halo catalogue: pass halos='fof', a dict of friends-of-friends keywords or your own labels")
+            if isinstance(self._halos_option, np.ndarray):
+                self._halos = FofCatalogue(self._halos_option)
+            else:
+                ll, b, min_members, period = check_fof_arguments(periodicity_scale=self._period, **self._halos_option)
+                pos = check_fof_positions(self._pos)
+                if ll is None:
+                    ll = fof_linking_length(pos, b, period)      # (raises before a context exists)
+                self._halos = self._with_context(lambda ctx: compute_fof_catalogue(ctx, pos, ll, b, min_members, period))
+        return self._halos
+
+    def set_halos(self, labels):
+        """The halo labels in this loader's particle order (e.g. from the caller's cache, next to set_smooth / set_density):
+        the catalogue is then not computed."""
+        labels = check_halo_labels(labels, len(self))
+        if self._halos_option is None:
+            self._halos_option = labels
+        self._halos = FofCatalogue(labels)
+        self._halo_centers = {}
+
+    def get_halo_center(self, n):
+        """The shrinking-sphere centre (float64 (3,)) of the members of halo n, found on the GPU and cached."""
+        if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or n < 1:
+            raise ValueError(f"halo numbers are integers >= 1, not {n!r}")
+        n = int(n)
+        if n not in self._halo_centers:
+            members = self.get_halos().members(n)
+            if len(members) == 0:
+                raise ValueError(f"halo {n} has no members")
+            if self._pos.ndim != 2 or self._pos.shape[1] != 3 or self._mass.shape != (len(self._pos),):
+                raise ValueError(f"a halo centre needs pos of shape (n, 3) and one mass per particle, not {self._pos.shape} "
+                                 f"and {self._mass.shape}")
+            pos = self._pos[members].astype(np.float64)
+            if self._period:
+                # one image of the halo: every member by nearest image around the lowest-index member
+                d = pos - pos[0]
+                pos = pos[0] + (d - self._period * np.rint(d / self._period))
+            pos = pos.astype(np.float32)
+            mass = self._mass[members]
+            cut, r0, shrink, min_particles = check_center_arguments("all")
+            self._halo_centers[n], self.center_info = self._with_context(lambda ctx: ctx.shrink_sphere_center(
+                pos[:, 0], pos[:, 1], pos[:, 2], mass, mass_cut_factor=cut, r_start=r0, shrink_factor=shrink,
+                min_particles=min_particles))
+        return self._halo_centers[n]
+
     def get_initial_center(self):
         if isinstance(self._center_option, str) and self._center_option == "none":
             return super().get_initial_center()
         if self._center is None:
             if not isinstance(self._center_option, str):
                 self._center = self._center_option
+            elif self._center_option.startswith("halo-"):
+                self._center = self.get_halo_center(int(self._center_option[5:]))
             else:
                 cut, r0, shrink, min_particles = check_center_arguments(self._center_option)
-                ctx = self._density_context
-                own = ctx is None
-                if own:
-                    from . import _native
-                    ctx = _native.Context(1, 2, self._device if isinstance(self._device, int) else 0)
-                try:
-                    self._center, self.center_info = ctx.shrink_sphere_center(
-                        self._pos[:, 0], self._pos[:, 1], self._pos[:, 2], self._mass, mass_cut_factor=cut, r_start=r0,
-                        shrink_factor=shrink, min_particles=min_particles)
-                finally:
-                    if own:
-                        ctx.close()
+                self._center, self.center_info = self._with_context(lambda ctx: ctx.shrink_sphere_center(
+                    self._pos[:, 0], self._pos[:, 1], self._pos[:, 2], self._mass, mass_cut_factor=cut, r_start=r0,
+                    shrink_factor=shrink, min_particles=min_particles))
         return self._center
 
     def set_initial_center(self, center):

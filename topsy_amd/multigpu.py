@@ -209,6 +209,10 @@ class MultiGpuContext:
         """The shrinking-sphere centre of the whole (caller-ordered) snapshot, on the first context like smoothing_lengths."""
         return self.contexts[0].shrink_sphere_center(x, y, z, mass, **kwargs)
 
+    def fof_groups(self, x, y, z, linking_length, period=0.0, min_members=20):
+        """The friends-of-friends groups of the whole (caller-ordered) snapshot, on the first context like smoothing_lengths."""
+        return self.contexts[0].fof_groups(x, y, z, linking_length, period, min_members)
+
     def generate_synthetic(self, n_total, first=0, count=None, seed=1337, h_cap=0.0, with_quantity=False, with_rgb=False):
         count = n_total - first if count is None else count
         # the generator's index bijection makes every index range a uniform sample: contiguous shards are balanced

@@ -188,6 +188,10 @@ class SurfaceView:
         """The visualizer's centre_on_pixel: (row, col) index the shared R x R image; the camera is the visualizer's."""
         return self._vis.centre_on_pixel(row, col)
 
+    def centre_on_halo(self, n):
+        """The visualizer's centre_on_halo: the camera is the visualizer's."""
+        return self._vis.centre_on_halo(n)
+
     @property
     def quantity_name(self):
         return self._vis.quantity_name

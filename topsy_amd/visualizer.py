@@ -359,6 +359,16 @@ class VisualizerBase:
         self.position_offset = np.asarray(self.position_offset, dtype=np.float64) - np.asarray(self.rotation_matrix).T @ view
         return self.position_offset
 
+    def centre_on_halo(self, n):
+        """Move position_offset to minus the centre of halo n (1 = the largest) of the data loader's halo catalogue
+        (halos= of from_arrays / ArrayDataLoader: friends-of-friends groups found on the GPU, or the caller's labels): the
+        shrinking-sphere centre of the halo's members.  The array-snapshot counterpart of centre_on_pixel.  Returns the new
+        offset."""
+        if not hasattr(self.data_loader, "get_halo_center"):
+            raise ValueError(f"{type(self.data_loader).__name__} has no halo catalogue")
+        self.position_offset = -np.asarray(self.data_loader.get_halo_center(n), dtype=np.float64)
+        return self.position_offset
+
     def save(self, filename="output.npy"):
         self._sph.render(DrawReason.EXPORT)
         if filename.endswith(".npy"):
