@@ -137,7 +137,14 @@ int tsp_generate_synthetic(tsp_context *ctx, int64_t n_total, int64_t first, int
  * strata, each Morton-sorted, so that index prefixes remain unbiased samples (progressive
  * rendering) while consecutive indices are screen-coherent.  perm_out (optional, host, n
  * int64) receives new->old indices.  Later tsp_upload_quantity/rgb calls are given in the OLD
- * order and permuted by the library. */
+ * order and permuted by the library.  A second call sorts the particles as they lie then and
+ * reports new->ORIGINAL indices.
+ * The key of particle i is stratum << 48 | Morton code of its position quantised to 16 bits per
+ * axis over the bounding box of the FINITE coordinates (float32: (x - lo) * (65535 / (max - min)),
+ * truncated), stratum = splitmix64(seed ^ i) % n_strata.  The sort is stable: particles with
+ * equal keys (equal positions, among others) keep their index order.  Non-finite coordinates are
+ * outside the box: NaN and -inf quantise to the lowest step of their axis, +inf to the highest;
+ * an axis without any finite value, or with a single one, has one step. */
 int tsp_reorder_spatial(tsp_context *ctx, int n_strata, uint64_t seed, int64_t *perm_out);
 /* First index of every stratum of the last tsp_reorder_spatial call, plus the particle count:
  * n_strata + 1 ascending int64 values.  A contiguous index range is an unbiased spatial sample only
@@ -155,6 +162,14 @@ int tsp_get_strata_offsets(tsp_context *ctx, int64_t *offsets_out, int capacity)
  * n_strata * cells_per_axis^3 + 1 ascending int64 values, entry s * cells^3 + code for stratum s and Morton cell code
  * (bit 3 j of the code = bit j of cx, bit 3 j + 1 = bit j of cy, bit 3 j + 2 = bit j of cz), the last entry = n.
  * The host selects the cells that meet the view sphere and hands tsp_render the (start, len) runs of those cells.
+ * The grid is honest for every snapshot: a particle that is finite on all axes lies inside the box its run's cell is
+ * reported to cover (to float32 rounding, far inside the one-cell-diagonal margin the host adds).  Where float32 gives
+ * out the library goes on in another way instead of reporting cell_width = 0 for particles that differ: an axis whose
+ * extent max - min overflows float32 (sentinel rows at +-3e38) is quantised in float64; its cell_width is finite (about
+ * extent / cells_per_axis) except with cells_per_axis = 1, where 2^16 / inv overflows and cell_width = +inf is
+ * reported -- a cell whose centre or diagonal is not finite must be selected; an
+ * axis so narrow that 65535 / (max - min) overflows (a few denormals) is quantised with FLT_MAX steps per unit.
+ * cell_width = 0 means that every finite coordinate of the axis is box_lo (0 when the axis has none).
  * tsp_get_cell_offsets returns the number of values written (<= capacity), 0 when the particles were never reordered. */
 int tsp_get_cell_layout(tsp_context *ctx, int *n_strata_out, int *cells_per_axis_out, float *box_lo_out /*3*/,
                         float *cell_width_out /*3*/);

@@ -94,8 +94,11 @@ class StratifiedCells:
                     cxyz[:, a] |= ((code >> (3 * j + a)) & 1) << j
             width = np.asarray(lay["cell_width"], dtype=np.float64)
             centres = np.asarray(lay["box_lo"], dtype=np.float64) + (cxyz + 0.5) * width
+            reach = float(np.linalg.norm(width))                           # one cell diagonal, as cells_in_sphere adds
+            # a cell that cannot be placed is never culled: the one cell of an axis wider than float32 (cell_width = inf)
+            unplaced = ~np.isfinite(centres).all(axis=1) | (not np.isfinite(reach))
             self.groups.append({"ncell": ncell, "n_strata": int(lay["n_strata"]), "centres": centres,
-                                "reach": float(np.linalg.norm(width)),      # one cell diagonal, as cells_in_sphere adds
+                                "reach": reach, "unplaced": unplaced,
                                 "offsets": np.asarray(lay["offsets"], dtype=np.int64)})
         self.select_all()
 
@@ -123,7 +126,9 @@ class StratifiedCells:
     def select_sphere(self, centre, radius):
         """Cells whose centre lies within radius + one cell diagonal of `centre` (reference cell_layout.py:26-31)."""
         centre = np.asarray(centre, dtype=np.float64)
-        self._set_selection([np.linalg.norm(g["centres"] - centre, axis=1) < radius + g["reach"] for g in self.groups])
+        with np.errstate(invalid="ignore", over="ignore"):
+            self._set_selection([~(np.linalg.norm(g["centres"] - centre, axis=1) >= radius + g["reach"]) | g["unplaced"]
+                                 for g in self.groups])
 
     def all_selected(self):
         return self._all

@@ -7,6 +7,8 @@
 #include <hipcub/hipcub.hpp>
 
 #include <algorithm>
+#include <cfloat>
+#include <cmath>
 #include <vector>
 
 #include "tsp_internal.h"
@@ -210,13 +212,19 @@ __device__ __forceinline__ uint64_t part1by2(uint64_t x) {   // classic 21-bit s
     return x;
 }
 
-__global__ void morton_key_kernel(const float *x, const float *y, const float *z, int64_t n, float3 lo, float3 inv,
+// One axis of the key: 16-bit step of v in the box.  float32, a subtraction then a multiplication (-ffp-contract=off keeps them
+// apart).  A wide axis (max - min overflows float32: v - lo may overflow too) forms both in float64 and rounds once.  NaN -> step
+// 0; +-inf and everything the rounding puts outside clamp to the edge steps.
+__device__ __forceinline__ float key_step(float v, float lo, float inv, bool wide) {
+    const float f = wide ? (float)(((double)v - (double)lo) * (double)inv) : (v - lo) * inv;
+    return f != f ? 0.f : fminf(fmaxf(f, 0.f), 65535.f);
+}
+
+__global__ void morton_key_kernel(const float *x, const float *y, const float *z, int64_t n, float3 lo, float3 inv, int wide,
                                   int n_strata, uint64_t seed, uint64_t *keys, uint32_t *vals) {
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        float fx = (x[i] - lo.x) * inv.x, fy = (y[i] - lo.y) * inv.y, fz = (z[i] - lo.z) * inv.z;
-        fx = fx != fx ? 0.f : fminf(fmaxf(fx, 0.f), 65535.f);
-        fy = fy != fy ? 0.f : fminf(fmaxf(fy, 0.f), 65535.f);
-        fz = fz != fz ? 0.f : fminf(fmaxf(fz, 0.f), 65535.f);
+        const float fx = key_step(x[i], lo.x, inv.x, wide & 1), fy = key_step(y[i], lo.y, inv.y, wide & 2);
+        const float fz = key_step(z[i], lo.z, inv.z, wide & 4);
         const uint64_t mk = part1by2((uint64_t)fx) | (part1by2((uint64_t)fy) << 1) | (part1by2((uint64_t)fz) << 2);
         const uint64_t stratum = n_strata > 1 ? splitmix64(seed ^ (uint64_t)i) % (uint64_t)n_strata : 0;
         keys[i] = (stratum << 48) | mk;
@@ -354,7 +362,8 @@ int reorder_spatial(tsp_context *ctx, int n_strata, uint64_t seed, int64_t *perm
     p.wm_valid = p.wrgb_valid = false;       // (recomputed in the new order by the next render)
     hipStream_t st = ctx->stream;
     float lo[3], inv[3];
-    {   // bounding box of the positions
+    int wide = 0;              // bit k: axis k is keyed in float64 (its extent overflows float32)
+    {   // bounding box of the finite positions
         DeviceScratch mm;
         TSP_HIP(mm.alloc(6 * sizeof(unsigned)));
         const unsigned init[6] = {0xffffffffu, 0xffffffffu, 0xffffffffu, 0, 0, 0};
@@ -364,9 +373,19 @@ int reorder_spatial(tsp_context *ctx, int n_strata, uint64_t seed, int64_t *perm
         TSP_HIP(hipMemcpyAsync(hmm, mm.p, sizeof(hmm), hipMemcpyDeviceToHost, st));
         TSP_HIP(hipStreamSynchronize(st));
         for (int k = 0; k < 3; ++k) {
-            const float a = unordered_f32(hmm[k]), b = unordered_f32(hmm[3 + k]);
+            const bool none = hmm[k] > hmm[3 + k];          // no finite value on this axis: the box is the point 0
+            const float a = none ? 0.0f : unordered_f32(hmm[k]), b = none ? 0.0f : unordered_f32(hmm[3 + k]);
             lo[k] = a;
-            inv[k] = (b > a) ? 65535.0f / (b - a) : 0.0f;
+            // steps per unit length.  Two snapshots leave float32 here and must still get a finite, honest grid (cells that
+            // hold what the layout says they hold): an extent beyond FLT_MAX (sentinel rows at +-3e38) is formed in float64,
+            // and the quotient of an extent below 65535 / FLT_MAX (a few denormals) is held at FLT_MAX.
+            const float ext = b - a;
+            if (b > a && !std::isfinite(ext)) {
+                wide |= 1 << k;
+                inv[k] = (float)(65535.0 / ((double)b - (double)a));
+            } else {
+                inv[k] = (b > a) ? std::min(65535.0f / ext, FLT_MAX) : 0.0f;
+            }
         }
     }
     DeviceScratch order;       // order[new] = old index (relative to the current order)
@@ -377,7 +396,7 @@ int reorder_spatial(tsp_context *ctx, int n_strata, uint64_t seed, int64_t *perm
         TSP_HIP(vals.alloc((size_t)n * 4));
         TSP_HIP(order.alloc((size_t)n * 4));
         hipLaunchKernelGGL(morton_key_kernel, dim3(4096), dim3(256), 0, st, p.x, p.y, p.z, n,
-                           make_float3(lo[0], lo[1], lo[2]), make_float3(inv[0], inv[1], inv[2]), n_strata, seed,
+                           make_float3(lo[0], lo[1], lo[2]), make_float3(inv[0], inv[1], inv[2]), wide, n_strata, seed,
                            keys.as<uint64_t>(), vals.as<uint32_t>());
         TSP_HIP(hipGetLastError());
         size_t tmp_bytes = 0;
@@ -412,7 +431,8 @@ int reorder_spatial(tsp_context *ctx, int n_strata, uint64_t seed, int64_t *perm
         ctx->cell_bits = k;
         for (int a = 0; a < 3; ++a) {
             ctx->cell_lo[a] = lo[a];
-            // a cell spans 2^(16 - k) quantisation steps of 1 / inv world units each (inv = 0: a degenerate axis, one cell)
+            // a cell spans 2^(16 - k) quantisation steps of 1 / inv world units each (inv = 0: a degenerate axis, one cell);
+            // +inf for the one cell (k = 0) of a wide axis: the host selects a cell whose centre or reach is not finite
             ctx->cell_width[a] = inv[a] > 0.0f ? (float)(1 << (16 - k)) / inv[a] : 0.0f;
         }
         // Lane decorrelation (round 5): kernel S gives one lane per particle and 64 consecutive particles per wave step.  Morton

@@ -140,13 +140,17 @@ int tsp_group_upload_particles(tsp_group *grp, int64_t n, const float *x, const 
 
 int tsp_group_upload_quantity(tsp_group *grp, const float *q) {
     TSP_REQUIRE(grp, TSP_EINVAL, "NULL group");
-    return for_each_context(grp, [&](int g) { return tsp_upload_quantity(grp->ctx[g], q ? q + grp->bounds[g] : nullptr); });
+    return for_each_context(grp, [&](int g) {
+        if (q && grp->bounds[g + 1] == grp->bounds[g]) return (int)TSP_OK;      // an empty shard (more members than particles)
+        return tsp_upload_quantity(grp->ctx[g], q ? q + grp->bounds[g] : nullptr);
+    });
 }
 
 int tsp_group_upload_rgb(tsp_group *grp, const float *r, const float *g_, const float *b) {
     TSP_REQUIRE(grp && r && g_ && b, TSP_EINVAL, "NULL argument");
     return for_each_context(grp, [&](int g) {
         const int64_t a = grp->bounds[g];
+        if (grp->bounds[g + 1] == a) return (int)TSP_OK;
         return tsp_upload_rgb(grp->ctx[g], r + a, g_ + a, b + a);
     });
 }
