@@ -502,13 +502,7 @@ class Context:
         lut_rgba); layers as present takes them.  `timings`, a list, receives [filter ms, composition ms]."""
         p, _lut = self._surface_params(**(params or {}))
         arr, _keep = self._layer_args(layers)
-        W, H = int(width), int(height)
-        out = np.empty((max(H, 0), max(W, 0), 4), dtype=np.uint8)
-        ms = (ctypes.c_double * 2)()
-        _check(self._lib.tsp_present_surface(self._h, W, H, ctypes.byref(p), arr, len(layers), out.ctypes.data_as(_u8p), ms))
-        if timings is not None:
-            timings[:] = [ms[0], ms[1]]
-        return out
+        return self._compose(self._lib.tsp_present_surface, width, height, p, arr, len(layers), 2, timings)
 
     def present_surface_yuv420(self, width, height, params=None, layers=(), timings=None):
         """The frame of present_surface(width, height, params, layers) as I420 planes (tsp_present_surface_yuv420): uint8 arrays
@@ -516,15 +510,7 @@ class Context:
         [filter ms, composition + conversion ms]."""
         p, _lut = self._surface_params(**(params or {}))
         arr, _keep = self._layer_args(layers)
-        W, H = int(width), int(height)
-        n = max(W, 0) * max(H, 0)
-        out = np.empty(n + 2 * (max(W, 0) // 2) * (max(H, 0) // 2), dtype=np.uint8)
-        ms = (ctypes.c_double * 2)()
-        _check(self._lib.tsp_present_surface_yuv420(self._h, W, H, ctypes.byref(p), arr, len(layers), out.ctypes.data_as(_u8p), ms))
-        if timings is not None:
-            timings[:] = [ms[0], ms[1]]
-        c = (W // 2) * (H // 2)
-        return out[:n].reshape(H, W), out[n:n + c].reshape(H // 2, W // 2), out[n + c:].reshape(H // 2, W // 2)
+        return self._compose(self._lib.tsp_present_surface_yuv420, width, height, p, arr, len(layers), 2, timings, yuv420=True)
 
     def content_sort(self, kind, scale=1.0):
         """Sort the finite content values on the device; returns (n_finite, n_nonpositive)."""
@@ -639,29 +625,29 @@ class Context:
         dv), offsets (n, 2), weights (n,)) or "lines" (starts / ends (n, 4), transform (4, 4) row-major, color (4,), width).
         Returns uint8, or float16 for "rgb-hdr".  `timings`, a list, receives the composition kernel's GPU ms."""
         b, arr, keep = self._present_args(base, layers)
-        W, H = int(width), int(height)
-        hdr = b.map == PRESENT_RGB_HDR
-        out = np.empty((max(H, 0), max(W, 0), 4), dtype=np.float16 if hdr else np.uint8)
-        ms = ctypes.c_double(0.0)
-        _check(self._lib.tsp_present(self._h, W, H, ctypes.byref(b), arr, len(layers), out.ctypes.data, ctypes.byref(ms)))
-        if timings is not None:
-            timings[:] = [ms.value]
-        return out
+        return self._compose(self._lib.tsp_present, width, height, b, arr, len(layers), 1, timings,
+                             dtype=np.float16 if b.map == PRESENT_RGB_HDR else np.uint8)
 
     def present_yuv420(self, width, height, base, layers=(), timings=None):
         """The frame of present(width, height, base, layers) as I420 planes (tsp_present_yuv420): uint8 arrays Y (height,
         width), U and V (height / 2, width / 2).  width and height must be even; the "rgb-hdr" map has no 8-bit frame.
         `timings`, a list, receives the GPU ms of the composition and the conversion together."""
         b, arr, keep = self._present_args(base, layers)
+        return self._compose(self._lib.tsp_present_yuv420, width, height, b, arr, len(layers), 1, timings, yuv420=True)
+
+    def _compose(self, entry, width, height, head, layer_array, n_layers, n_ms, timings, yuv420=False, dtype=np.uint8):
+        """One call of a composition entry point (entry: the library function; head: its base or surface struct): the output sized
+        for the (height, width, 4) frame of `dtype`, or (yuv420) for its I420 planes, which come back as the views Y, U, V; the
+        n_ms GPU times the entry point reports go to `timings`."""
         W, H = int(width), int(height)
-        n = max(W, 0) * max(H, 0)
-        out = np.empty(n + 2 * (max(W, 0) // 2) * (max(H, 0) // 2), dtype=np.uint8)
-        ms = ctypes.c_double(0.0)
-        _check(self._lib.tsp_present_yuv420(self._h, W, H, ctypes.byref(b), arr, len(layers), out.ctypes.data_as(_u8p),
-                                            ctypes.byref(ms)))
+        n, c = max(W, 0) * max(H, 0), (max(W, 0) // 2) * (max(H, 0) // 2)
+        out = np.empty(n + 2 * c, dtype=np.uint8) if yuv420 else np.empty((max(H, 0), max(W, 0), 4), dtype=dtype)
+        ms = (ctypes.c_double * n_ms)()
+        _check(entry(self._h, W, H, ctypes.byref(head), layer_array, n_layers, out.ctypes.data_as(entry.argtypes[6]), ms))
         if timings is not None:
-            timings[:] = [ms.value]
-        c = (W // 2) * (H // 2)
+            timings[:] = list(ms)
+        if not yuv420:
+            return out
         return out[:n].reshape(H, W), out[n:n + c].reshape(H // 2, W // 2), out[n + c:].reshape(H // 2, W // 2)
 
     @staticmethod

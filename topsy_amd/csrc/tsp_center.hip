@@ -219,17 +219,6 @@ __global__ __launch_bounds__(256) void center_final_kernel(Partial *__restrict__
     workgroup_sum_store(a, partials + n_partials);
 }
 
-#define CENTER_ALLOC(buf, bytes)                                                                                         \
-    do {                                                                                                                 \
-        const hipError_t e_ = (buf).alloc(bytes);                                                                        \
-        if (e_ != hipSuccess) {                                                                                          \
-            (void)hipGetLastError();                                                                                     \
-            tsp::set_error("tsp_shrink_sphere_center: cannot allocate %zu bytes of device memory: %s", (size_t)(bytes),  \
-                           hipGetErrorString(e_));                                                                       \
-            return e_ == hipErrorOutOfMemory ? TSP_ENOMEM : TSP_EHIP;                                                    \
-        }                                                                                                                \
-    } while (0)
-
 double wall_ms(std::chrono::steady_clock::time_point t0) {
     return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
 }
@@ -251,13 +240,13 @@ int shrink_sphere_center(tsp_context *ctx, int64_t n, const float *x, const floa
     const int grid = (int)std::min<int64_t>((nblocks + 1) / 2, (int64_t)ctx->cu_count * 8);
 
     DeviceScratch dx, dy, dz, dw, dboxes, dpartials, dmin;
-    CENTER_ALLOC(dx, (size_t)npad * sizeof(float));
-    CENTER_ALLOC(dy, (size_t)npad * sizeof(float));
-    CENTER_ALLOC(dz, (size_t)npad * sizeof(float));
-    CENTER_ALLOC(dw, (size_t)npad * sizeof(float));
-    CENTER_ALLOC(dboxes, (size_t)nblocks * 6 * sizeof(float));
-    CENTER_ALLOC(dpartials, (size_t)(grid + 1) * sizeof(Partial));
-    CENTER_ALLOC(dmin, sizeof(unsigned));
+    TSP_SCRATCH_ALLOC("tsp_shrink_sphere_center", dx, (size_t)npad * sizeof(float));
+    TSP_SCRATCH_ALLOC("tsp_shrink_sphere_center", dy, (size_t)npad * sizeof(float));
+    TSP_SCRATCH_ALLOC("tsp_shrink_sphere_center", dz, (size_t)npad * sizeof(float));
+    TSP_SCRATCH_ALLOC("tsp_shrink_sphere_center", dw, (size_t)npad * sizeof(float));
+    TSP_SCRATCH_ALLOC("tsp_shrink_sphere_center", dboxes, (size_t)nblocks * 6 * sizeof(float));
+    TSP_SCRATCH_ALLOC("tsp_shrink_sphere_center", dpartials, (size_t)(grid + 1) * sizeof(Partial));
+    TSP_SCRATCH_ALLOC("tsp_shrink_sphere_center", dmin, sizeof(unsigned));
 
     auto t0 = std::chrono::steady_clock::now();
     const float *host[4] = {x, y, z, mass};

@@ -248,11 +248,11 @@ __global__ __launch_bounds__(H2T, OCC) void splat_huge2_kernel(TileArgs a) {
     const float4 *geom = a.geom;
     const float *wts = a.w;
     unsigned n_rec = (unsigned)a.n_records;
-    if (a.hband_count) {
+    if (a.bin_count) {
         const int band = ty0 / HBAND_H;
-        geom += (size_t)band * a.hband_stride;
-        wts += (size_t)band * a.hband_stride * NW;
-        n_rec = (unsigned)a.hband_count[band];
+        geom += (size_t)band * a.band_stride;
+        wts += (size_t)band * a.band_stride * NW;
+        n_rec = (unsigned)a.bin_count[band];
     }
     const unsigned n_runs = (n_rec + HDEAL - 1) / HDEAL, usplit = (unsigned)a.split, n_last = max(n_rec, 1u) - 1u;
     // record index of this lane in batch run0: ((run0 + lane / HDEAL) * split + sp) * HDEAL + lane % HDEAL = a wave-uniform base + lane_off
@@ -283,13 +283,8 @@ __global__ __launch_bounds__(H2T, OCC) void splat_huge2_kernel(TileArgs a) {
         if (batch_base(run0) + lane_off >= n_rec) g.z = 0.0f;      // (a slot past the end of the list)
         fetch(run0 + 64 / HDEAL, g_next, gw1_next, gw2_next);      // the next 64 records load while these are rasterised
         const float g_half = 0.5f * g.z;
-        bool hit;
-        {
-            const float sdx = fmaxf(fmaxf(sx0 - g.x, g.x - sx1), 0.0f), sdy = fmaxf(fmaxf(sy0 - g.y, g.y - sy1), 0.0f);
-            // g.z = 0 marks an empty slot; the kernel vanishes outside the disc inscribed in the footprint square
-            hit = g.z > 0.0f && sdx < g_half && sdy < g_half && !(a.disc_k2 > 0.0f && sdx * sdx + sdy * sdy >= a.disc_k2 * g.z * g.z);
-        }
-        unsigned long long hits = __ballot(hit);
+        // (g.z = 0 marks an empty slot; the kernel vanishes outside the disc inscribed in the footprint square)
+        unsigned long long hits = __ballot(reaches_strip(g, sx0, sx1, sy0, sy1, a.disc_k2));
         if (hits == 0ull) continue;
         since_fold += __popcll(hits);
         const float g_invP = 1.0f / g.z;
@@ -631,8 +626,7 @@ __global__ __launch_bounds__(256) void huge_band_fill_kernel(const float4 *__res
         b0[k] = 1; b1[k] = 0;
         if (first + k < n) {
             g[k] = geom[first + k];
-            // (margin: one pixel plus two ulps of the coordinate, so that it still covers the rounding of g.y -+ half beyond 2^23 px)
-            const float half = 0.5f * g[k].z, mg = 1.0f + 2.4e-7f * (__builtin_fabsf(g[k].y) + half), lo = g[k].y - half - mg, hi = g[k].y + half + mg;
+            const float half = 0.5f * g[k].z, mg = bin_margin(g[k].y, half), lo = g[k].y - half - mg, hi = g[k].y + half + mg;
             // (non-finite or off-image squares: no band; kernel S emits only records that cover a pixel)
             // (a negative width: a record with a weight that is not finite, drawn by huge_nonfinite_kernel)
             if (g[k].z > 0.0f && hi >= 0.0f && lo < (float)R && lo == lo && hi == hi) {
@@ -662,10 +656,10 @@ __global__ __launch_bounds__(256) void huge_band_fill_kernel(const float4 *__res
     }
 }
 
-// bins the huge list when that pays and fits the memory budget; sets ta.hband_* (or leaves them null)
+// bins the huge list when that pays and fits the memory budget; sets ta.{geom, w, bin_count, band_stride} (or leaves the bins null)
 template <int NW>
 static int bin_huge_records(tsp_context *ctx, TileArgs &ta, const float4 *huge_geom, const float *huge_w, long long n_huge) {
-    ta.hband_count = nullptr; ta.hband_stride = 0; ta.hband_base = nullptr;
+    ta.bin_count = nullptr; ta.band_stride = 0; ta.bin_base = nullptr;
     Workspace &ws = ctx->ws;
     const int n_bands = (ctx->R + HBAND_H - 1) / HBAND_H;
     const size_t rec_bytes = sizeof(float4) + NW * sizeof(float);
@@ -688,7 +682,7 @@ static int bin_huge_records(tsp_context *ctx, TileArgs &ta, const float4 *huge_g
                        (float4 *)ws.hband_geom, (float *)ws.hband_w, (long long)ws.hband_stride, ws.hband_count, (const long long *)nullptr);
     TSP_HIP(hipGetLastError());
     ta.geom = (const float4 *)ws.hband_geom; ta.w = (const float *)ws.hband_w;
-    ta.hband_count = ws.hband_count; ta.hband_stride = ws.hband_stride;
+    ta.bin_count = ws.hband_count; ta.band_stride = ws.hband_stride;
     return TSP_OK;
 }
 

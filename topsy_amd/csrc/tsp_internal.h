@@ -73,13 +73,15 @@ struct Workspace {     // per-context scratch of the three-class pipeline (grown
     void *hband_geom = nullptr, *hband_w = nullptr; // the huge records once more, binned by 64-row image band (n_bands regions of hband_stride records)
     int *hband_count = nullptr;                     // records per band
     int64_t hband_stride = 0; int hband_bands = 0;
-    void *mband_geom = nullptr, *mband_w = nullptr; // the mid records binned by tile for kernel G (exact-size bins)
-    int *mband_count = nullptr;                     // records per tile | fill cursors
-    long long *mband_base = nullptr;                // first record of each tile's bin
+    // the strip bins of the mid records (bin_mid_records, tsp_mid.hip): one set, refilled for each launch of kernel N (16-column strips)
+    // and of kernel G (64-column strips); a "tile" in these names is one strip of the kernel being launched
+    void *mband_geom = nullptr, *mband_w = nullptr; // the mid records copied into exact-size bins, one per strip
+    int *mband_count = nullptr;                     // records per strip | fill cursors
+    long long *mband_base = nullptr;                // first record of each strip's bin
     int64_t mband_capacity = 0;                     // records the bins can hold
     int mtile_capacity = 0;                         // strips the per-strip arrays can hold
     int64_t mitem_capacity = 0;                     // work items the item table can hold
-    int *mitem_tile = nullptr, *mitem_base = nullptr; // kernel G work items: item -> tile, tile -> first item
+    int *mitem_tile = nullptr, *mitem_base = nullptr; // work items of kernels N and G: item -> strip, strip -> first item
     int64_t chunk_capacity = 0;         // chunks alive_list can hold
     float4 *block_bounds = nullptr;     // chunk culling: bounds of every BOUNDS_BLOCK particles (valid while bounds_valid)
     int64_t bounds_capacity = 0;        // blocks
@@ -194,6 +196,17 @@ struct DeviceScratch {
     void *release() { void *q = p; p = nullptr; return q; }
     void reset(void *q) { if (p) (void)hipFree(p); p = q; }
 };
+// buf.alloc(bytes) for a DeviceScratch of the entry point `who`; a failure sets the error text and returns from the caller
+#define TSP_SCRATCH_ALLOC(who, buf, bytes)                                                                               \
+    do {                                                                                                                 \
+        const hipError_t e_ = (buf).alloc(bytes);                                                                        \
+        if (e_ != hipSuccess) {                                                                                          \
+            (void)hipGetLastError();                                                                                     \
+            tsp::set_error("%s: cannot allocate %zu bytes of device memory: %s", (who), (size_t)(bytes),                 \
+                           hipGetErrorString(e_));                                                                       \
+            return e_ == hipErrorOutOfMemory ? TSP_ENOMEM : TSP_EHIP;                                                    \
+        }                                                                                                                \
+    } while (0)
 
 // Every device buffer that can be (re)allocated after tsp_create and the uploads -- the render workspace, the colormap and
 // post-pass staging -- goes through alloc_group().  A group is the buffers that are only ever used together, with the capacity

@@ -93,10 +93,10 @@ __global__ __launch_bounds__(H2T, OCC) void splat_mid_gather_kernel(TileArgs a) 
     __syncthreads();                                       // the only workgroup barrier
     if (idle_wave) return;
 
-    const size_t first = (size_t)a.hband_base[strip] + (size_t)chunk * a.item_records;
+    const size_t first = (size_t)a.bin_base[strip] + (size_t)chunk * a.item_records;
     const float4 *geom = a.geom + first;
     const float *wts = a.w + first * NW;
-    const unsigned n_rec = (unsigned)min(a.item_records, a.hband_count[strip] - chunk * a.item_records);
+    const unsigned n_rec = (unsigned)min(a.item_records, a.bin_count[strip] - chunk * a.item_records);
     auto fetch = [&](unsigned b0, float4 &g, float &gw1, float &gw2) {      // records b0 + lane of the item (one per lane)
         const unsigned rc = min(b0 + lane, n_rec - 1u);       // (unconditional loads, as in kernel H2; an item holds >= 1 record)
         g = geom[rc];
@@ -115,12 +115,7 @@ __global__ __launch_bounds__(H2T, OCC) void splat_mid_gather_kernel(TileArgs a) 
         if (run0 + lane >= n_rec) g.z = 0.0f;                 // (a slot past the end of the item)
         fetch(run0 + 64, g_next, gw1_next, gw2_next);
         const float g_half = 0.5f * g.z;
-        bool hit;
-        {
-            const float sdx = fmaxf(fmaxf(sx0 - g.x, g.x - sx1), 0.0f), sdy = fmaxf(fmaxf(sy0 - g.y, g.y - sy1), 0.0f);
-            hit = g.z > 0.0f && sdx < g_half && sdy < g_half && !(a.disc_k2 > 0.0f && sdx * sdx + sdy * sdy >= a.disc_k2 * g.z * g.z);
-        }
-        unsigned long long hits = __ballot(hit);
+        unsigned long long hits = __ballot(reaches_strip(g, sx0, sx1, sy0, sy1, a.disc_k2));
         if (hits == 0ull) continue;
         since_fold += __popcll(hits);
         const float g_invP = 1.0f / g.z;
@@ -303,11 +298,11 @@ __global__ __launch_bounds__(H2T, OCC) void splat_narrow_gather_kernel(TileArgs 
     __syncthreads();                                       // the only workgroup barrier
     if (idle_wave) return;
 
-    const size_t first = (size_t)a.hband_base[strip] + (size_t)chunk * a.item_records;
+    const size_t first = (size_t)a.bin_base[strip] + (size_t)chunk * a.item_records;
     constexpr int NWN = 2 * NW;           // weight floats per record of kernel N's bins: (w0, w1) / (w0, w1, w2, -): one 8- / 16-byte element; the geometry carries 1 / P
     const float4 *geom = a.geom + first;
     const float *wts = a.w + first * NWN;
-    const unsigned n_rec = (unsigned)min(a.item_records, a.hband_count[strip] - chunk * a.item_records);
+    const unsigned n_rec = (unsigned)min(a.item_records, a.bin_count[strip] - chunk * a.item_records);
     // record r0 + slot of the item (one per slot).  Unconditional loads (a slot past the end re-reads the last record and is
     // emptied where it is used): under a branch the compiler waits for this prefetch right after issuing it
     auto fetch = [&](unsigned r0, float4 &g, float &gw0, float &gw1, float &gw2) {
@@ -467,8 +462,7 @@ struct BinArgs {
 __device__ __forceinline__ TileSpan tile_span(const float4 g, const BinArgs &b) {
     TileSpan s; s.x0 = s.y0 = 1; s.x1 = s.y1 = 0;
     if (!(g.z >= b.pmin && g.z < b.pmax)) return s;
-    // (margin: one pixel plus two ulps of the coordinate -- it covers the rounding of g -+ half at any magnitude)
-    const float half = 0.5f * g.z, mx = 1.0f + 2.4e-7f * (__builtin_fabsf(g.x) + half), my = 1.0f + 2.4e-7f * (__builtin_fabsf(g.y) + half);
+    const float half = 0.5f * g.z, mx = bin_margin(g.x, half), my = bin_margin(g.y, half);
     const float xl = g.x - half - mx, xh = g.x + half + mx, yl = g.y - half - my, yh = g.y + half + my;
     // (non-finite or off-image squares: no tile; kernel S emits only records that cover a pixel)
     if (xh >= 0.0f && xl < (float)b.R && yh >= 0.0f && yl < (float)b.R && xl == xl && xh == xh && yl == yl && yh == yh) {
@@ -479,13 +473,10 @@ __device__ __forceinline__ TileSpan tile_span(const float4 g, const BinArgs &b) 
     }
     return s;
 }
-// the test kernels G and H2 make per (record, strip) pair: the footprint square and the disc inscribed in it reach the strip
+// exact bins: the test kernels G and H2 make per (record, strip) pair (reaches_strip, tsp_pipeline.h)
 __device__ __forceinline__ bool strip_hit(const float4 g, int tx, int ty, const BinArgs &b) {
     if (!b.exact) return true;
-    const float sx0 = (float)(tx * b.tw), sx1 = (float)(tx * b.tw + b.tw), sy0 = (float)(ty * b.th), sy1 = (float)(ty * b.th + b.th);
-    const float half = 0.5f * g.z;
-    const float sdx = fmaxf(fmaxf(sx0 - g.x, g.x - sx1), 0.0f), sdy = fmaxf(fmaxf(sy0 - g.y, g.y - sy1), 0.0f);
-    return g.z > 0.0f && sdx < half && sdy < half && !(b.disc_k2 > 0.0f && sdx * sdx + sdy * sdy >= b.disc_k2 * g.z * g.z);
+    return reaches_strip(g, (float)(tx * b.tw), (float)(tx * b.tw + b.tw), (float)(ty * b.th), (float)(ty * b.th + b.th), b.disc_k2);
 }
 // pass 1: records per tile (counted in LDS first when the image has few enough tiles: one global atomic per workgroup and tile)
 __global__ __launch_bounds__(256) void tile_count_kernel(const float4 *__restrict__ geom, long long n, BinArgs b, int *__restrict__ tile_count) {
@@ -621,7 +612,7 @@ __global__ __launch_bounds__(256) void tile_fill_kernel(const float4 *__restrict
     }
 }
 
-// bins the mid list by strip and builds the work items; sets ta.{geom, w, hband_count (records per strip), hband_base, item_*}
+// bins the mid list by strip and builds the work items; sets ta.{geom, w, bin_count, bin_base, item_*, tiles_x}
 template <int NW>
 static int bin_mid_records(tsp_context *ctx, TileArgs &ta, const float4 *mid_geom, const float *mid_w, long long n_mid, int tw, int th, float pmin,
                            float pmax, bool exact, int *n_items_out, hipStream_t st) {
@@ -681,44 +672,49 @@ static int bin_mid_records(tsp_context *ctx, TileArgs &ta, const float4 *mid_geo
                        &ctx->counters->mid_odd_weights);
     TSP_HIP(hipGetLastError());
     ta.geom = (const float4 *)ws.mband_geom; ta.w = (const float *)ws.mband_w;
-    ta.hband_count = ws.mband_count; ta.hband_stride = 0; ta.hband_base = ws.mband_base;
+    ta.bin_count = ws.mband_count; ta.band_stride = 0; ta.bin_base = ws.mband_base;
     ta.item_tile = ws.mitem_tile; ta.item_base = ws.mitem_base; ta.n_tiles = n_tiles; ta.item_records = item_records;
     ta.tiles_x = tiles_x;
     *n_items_out = total_items;
     return TSP_OK;
 }
 
-template <int MODE, int NACC, int HR, int OCC>
-static int launch_mid_gather_kernel(tsp_context *ctx, TileArgs ta, const float4 *mid_geom, const float *mid_w, long long n_mid, float pmin, hipStream_t st) {
+// what the launches of kernels G and N differ in: the kernel, the width of its strips, its LDS, and whether its bins hold only the
+// records that pass the per-pair test (kernel N draws every record of a bin unasked; kernel G tests each pair itself)
+struct KernelG {
+    static constexpr int STRIP_W = 64;
+    static constexpr bool EXACT_BINS = false;
+    static size_t lds_bytes(bool quad, int /*HR*/) { return (size_t)(quad ? MIPQ_TOTAL : MIP_TOTAL) * sizeof(float) + (H2T / 64) * 64 * sizeof(int); }
+    template <int MODE, int NACC, int HR, int OCC, bool QUAD, bool CNT> static constexpr auto kernel() { return splat_mid_gather_kernel<MODE, NACC, HR, OCC, QUAD, CNT>; }
+};
+struct KernelN {
+    static constexpr int STRIP_W = NSW;
+    static constexpr bool EXACT_BINS = true;
+    static size_t lds_bytes(bool quad, int HR) { return (size_t)(quad ? NQ_LINES * 32 : MIP_TOTAL + 64) * sizeof(float) + (H2T / 64) * 4 * HR * sizeof(int); }
+    template <int MODE, int NACC, int HR, int OCC, bool QUAD, bool CNT> static constexpr auto kernel() { return splat_narrow_gather_kernel<MODE, NACC, HR, OCC, QUAD, CNT>; }
+};
+
+// kernel K for the records with pmin <= P < pmax, from bins of its own
+template <class K, int MODE, int NACC, int HR, int OCC>
+static int launch_strip_kernel(tsp_context *ctx, TileArgs ta, const float4 *mid_geom, const float *mid_w, long long n_mid, float pmin, float pmax, hipStream_t st) {
     const bool quad = ctx->lut_mirror_symmetric && !ctx->debug_gather_full_lut;
-    const size_t smem = (size_t)(quad ? MIPQ_TOTAL : MIP_TOTAL) * sizeof(float) + (H2T / 64) * 64 * sizeof(int);
     int rc, n_items = 0;
     ta.n_records = n_mid;
-    if ((rc = bin_mid_records<(MODE == TSP_MODE_RGB) ? 2 : 1>(ctx, ta, mid_geom, mid_w, n_mid, 64, HR, pmin, __builtin_inff(), false, &n_items, st))) return rc;
+    if ((rc = bin_mid_records<(MODE == TSP_MODE_RGB) ? 2 : 1>(ctx, ta, mid_geom, mid_w, n_mid, K::STRIP_W, HR, pmin, pmax, K::EXACT_BINS, &n_items, st))) return rc;
     if (n_items == 0) return TSP_OK;
     const dim3 grid((n_items + H2T / 64 - 1) / (H2T / 64));
     with_bool(quad, [&](auto Q) { with_bool(ta.count_frag != 0, [&](auto CNT) {
-        hipLaunchKernelGGL((splat_mid_gather_kernel<MODE, NACC, HR, OCC, decltype(Q)::value, decltype(CNT)::value>), grid, dim3(H2T), smem, st, ta);
+        hipLaunchKernelGGL((K::template kernel<MODE, NACC, HR, OCC, decltype(Q)::value, decltype(CNT)::value>()), grid, dim3(H2T), K::lds_bytes(quad, HR), st, ta);
     }); });
     TSP_HIP(hipGetLastError());
     return TSP_OK;
 }
-
-// kernel N for the records below `pmax` px (its own bins: 16-column strips, only the records that reach a strip)
-template <int MODE, int NACC, int HR, int OCC>
-static int launch_narrow_gather_kernel(tsp_context *ctx, TileArgs ta, const float4 *mid_geom, const float *mid_w, long long n_mid, float pmax, hipStream_t st) {
-    const bool quad = ctx->lut_mirror_symmetric && !ctx->debug_gather_full_lut;
-    const size_t smem = (size_t)(quad ? NQ_LINES * 32 : MIP_TOTAL + 64) * sizeof(float) + (H2T / 64) * 4 * HR * sizeof(int);
-    int rc, n_items = 0;
-    ta.n_records = n_mid;
-    if ((rc = bin_mid_records<(MODE == TSP_MODE_RGB) ? 2 : 1>(ctx, ta, mid_geom, mid_w, n_mid, NSW, HR, 0.0f, pmax, true, &n_items, st))) return rc;
-    if (n_items == 0) return TSP_OK;
-    const dim3 grid((n_items + H2T / 64 - 1) / (H2T / 64));
-    with_bool(quad, [&](auto Q) { with_bool(ta.count_frag != 0, [&](auto CNT) {
-        hipLaunchKernelGGL((splat_narrow_gather_kernel<MODE, NACC, HR, OCC, decltype(Q)::value, decltype(CNT)::value>), grid, dim3(H2T), smem, st, ta);
-    }); });
-    TSP_HIP(hipGetLastError());
-    return TSP_OK;
+// accumulator sets, strip height and waves per SIMD by mode: the same for both kernels
+template <class K, int MODE>
+static int launch_strip_kernel_mode(tsp_context *ctx, TileArgs ta, bool second_channel, const float4 *mid_geom, const float *mid_w, long long n_mid, float pmin, float pmax, hipStream_t st) {
+    if (MODE == TSP_MODE_RGB) return launch_strip_kernel<K, MODE, 3, 16, TSP_G_OCC3>(ctx, ta, mid_geom, mid_w, n_mid, pmin, pmax, st);
+    if (second_channel) return launch_strip_kernel<K, MODE, 2, 16, TSP_G_OCC2>(ctx, ta, mid_geom, mid_w, n_mid, pmin, pmax, st);
+    return launch_strip_kernel<K, MODE, 1, TSP_G_HR1, TSP_G_OCC1>(ctx, ta, mid_geom, mid_w, n_mid, pmin, pmax, st);
 }
 
 template <int MODE>
@@ -727,17 +723,11 @@ static int launch_mid_gather_mode(tsp_context *ctx, TileArgs ta, bool second_cha
     // the mid list is drawn in two passes over it: footprints below mid_narrow_px by kernel N (four records per wave step on
     // 16-column strips), the rest by kernel G (one record per wave step on 64-column strips); 0 = everything by kernel G
     const float split = ctx->mid_narrow_px;
-    int rc;
     if (split > 0.0f) {
-        if (MODE == TSP_MODE_RGB) rc = launch_narrow_gather_kernel<MODE, 3, 16, TSP_G_OCC3>(ctx, ta, mid_geom, mid_w, n_mid, split, st);
-        else if (second_channel) rc = launch_narrow_gather_kernel<MODE, 2, 16, TSP_G_OCC2>(ctx, ta, mid_geom, mid_w, n_mid, split, st);
-        else rc = launch_narrow_gather_kernel<MODE, 1, TSP_G_HR1, TSP_G_OCC1>(ctx, ta, mid_geom, mid_w, n_mid, split, st);
-        if (rc) return rc;
+        if (int rc = launch_strip_kernel_mode<KernelN, MODE>(ctx, ta, second_channel, mid_geom, mid_w, n_mid, 0.0f, split, st)) return rc;
         if (split >= P_BILINEAR) return TSP_OK;        // (every mid footprint is below 64 px: nothing is left for kernel G)
     }
-    if (MODE == TSP_MODE_RGB) return launch_mid_gather_kernel<MODE, 3, 16, TSP_G_OCC3>(ctx, ta, mid_geom, mid_w, n_mid, split, st);
-    if (second_channel) return launch_mid_gather_kernel<MODE, 2, 16, TSP_G_OCC2>(ctx, ta, mid_geom, mid_w, n_mid, split, st);
-    return launch_mid_gather_kernel<MODE, 1, TSP_G_HR1, TSP_G_OCC1>(ctx, ta, mid_geom, mid_w, n_mid, split, st);
+    return launch_strip_kernel_mode<KernelG, MODE>(ctx, ta, second_channel, mid_geom, mid_w, n_mid, split, __builtin_inff(), st);
 }
 
 int launch_mid_gather(tsp_context *ctx, TileArgs ta, int mode, bool second_channel, const float4 *mid_geom, const float *mid_w,

@@ -186,17 +186,6 @@ static __device__ __forceinline__ unsigned long long for_each_run(const Grid &g,
     return scanned;
 }
 
-#define SMOOTH_ALLOC(who, buf, bytes)                                                                                    \
-    do {                                                                                                                 \
-        const hipError_t e_ = (buf).alloc(bytes);                                                                        \
-        if (e_ != hipSuccess) {                                                                                          \
-            (void)hipGetLastError();                                                                                     \
-            tsp::set_error("%s: cannot allocate %zu bytes of device memory: %s", (who), (size_t)(bytes),                 \
-                           hipGetErrorString(e_));                                                                       \
-            return e_ == hipErrorOutOfMemory ? TSP_ENOMEM : TSP_EHIP;                                                    \
-        }                                                                                                                \
-    } while (0)
-
 // Step 1 of every entry point over the index: the raw positions on the device (dx, dy, dz), the grid, the sorted keys
 // (keys2) with the sort's index (vals2: sorted -> caller's order), and the positions of the nv valid particles in Morton order
 // (sx, sy, sz).  vals (n x 4 bytes) is free for the caller's per-query result once the sort is done.

@@ -71,6 +71,18 @@ __device__ __forceinline__ void fmac_plain(float &acc, float x, float y) {     /
     asm volatile("v_fmac_f32_e32 %0, %1, %2" : "+v"(acc) : "v"(x), "v"(y));
 }
 
+// The test of a (record, strip) pair: the footprint square of g = (pcx, pcy, P, .) and the disc inscribed in it (disc_k2 > 0) reach the
+// strip [sx0, sx1] x [sy0, sy1]; P <= 0 marks an empty slot.  Kernels G and H2 make it per pair, the strip bins of kernel N once per
+// copy (tsp_mid.hip strip_hit): kernel N draws every record of a bin unasked, so there is one copy of the test.
+__device__ __forceinline__ bool reaches_strip(const float4 g, float sx0, float sx1, float sy0, float sy1, float disc_k2) {
+    const float half = 0.5f * g.z;
+    const float sdx = fmaxf(fmaxf(sx0 - g.x, g.x - sx1), 0.0f), sdy = fmaxf(fmaxf(sy0 - g.y, g.y - sy1), 0.0f);
+    return g.z > 0.0f && sdx < half && sdy < half && !(disc_k2 > 0.0f && sdx * sdx + sdy * sdy >= disc_k2 * g.z * g.z);
+}
+// Margin of the binning passes around a footprint's extent c -+ half: one pixel plus two ulps of the coordinate, so that it still
+// covers the rounding of c -+ half at any magnitude (float rounding can only add a bin, never drop one)
+__device__ __forceinline__ float bin_margin(float c, float half) { return 1.0f + 2.4e-7f * (__builtin_fabsf(c) + half); }
+
 constexpr int H2T = 256;             // threads per workgroup of kernels H2, N and G: 4 waves (H2: 2 x 2 strips sharing one pair table)
 
 __device__ __forceinline__ void latomic_add(double *addr, float v) {
@@ -95,12 +107,13 @@ struct TileArgs {
     int tiles_x, split;
     int count_frag;
     float disc_k2;     // (0.5235)^2 when the LUT is zero outside the inscribed disc (exact corner culling), else 0
-    // kernel H2: the huge records binned by image band (huge_band_fill_kernel): band b (rows [b, b + 1) * HBAND_H) holds
-    // hband_count[b] records at geom + b * hband_stride (w likewise); nullptr = one list for every tile (geom, n_records)
-    // (kernels N and G: exact-size bins, band b starts at record hband_base[b])
-    const int *hband_count; long long hband_stride; const long long *hband_base;
-    // kernels N and G: the mid records binned by tile (hband_count[t] records from record hband_base[t] on); workgroup i draws work item i =
-    // GCHUNK consecutive records of tile item_tile[i]'s bin (that tile's items start at item_base[tile]; item_base[n_tiles] = their number)
+    // The records in bins; a bin is an image band for kernel H2 and a strip for kernels N and G.
+    // kernel H2 (huge_band_fill_kernel): band b (rows [b, b + 1) * HBAND_H) holds bin_count[b] records at geom + b * band_stride (w
+    // likewise), bin_base unused; bin_count = nullptr: one list for every tile (geom, n_records)
+    // kernels N and G (bin_mid_records): exact-size bins, strip t holds bin_count[t] records from record bin_base[t] on, band_stride unused
+    const int *bin_count; long long band_stride; const long long *bin_base;
+    // kernels N and G: wave i draws work item i = item_records consecutive records of strip item_tile[i]'s bin (that strip's items start
+    // at item_base[strip]; item_base[n_tiles] = their number)
     int n_tiles; const int *item_tile; const int *item_base; int item_records;      // item_records: records per work item (a power of two)
 };
 

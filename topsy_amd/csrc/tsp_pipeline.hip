@@ -932,7 +932,7 @@ static int run_pipeline(tsp_context *ctx, const Camera &cam, const int64_t *h_st
     TileArgs ta;
     ta.cam = cam; ta.mips = ctx->mips; ta.img = ctx->image64; ta.cnt = ctx->counters; ta.tiles_x = 0; ta.split = 1;
     ta.count_frag = ctx->count_fragments ? 1 : 0;
-    ta.hband_count = nullptr; ta.hband_stride = 0; ta.hband_base = nullptr; ta.n_tiles = 0; ta.item_tile = nullptr; ta.item_base = nullptr;
+    ta.bin_count = nullptr; ta.band_stride = 0; ta.bin_base = nullptr; ta.n_tiles = 0; ta.item_tile = nullptr; ta.item_base = nullptr;
     // corner culling is exact for the value channels; the rgb counter channel (which also counts zero-valued
     // fragments) is not touched by kernel H2 at all: add_rect_counts() sums the footprint rectangles instead
     ta.disc_k2 = (ctx->lut_zero_outside_disc && !ctx->count_fragments) ? 0.5235f * 0.5235f : 0.0f;

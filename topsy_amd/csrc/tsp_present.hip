@@ -394,17 +394,6 @@ int check_layer(const tsp_present_layer &L, int index, int64_t &n_prims, int64_t
     return TSP_OK;
 }
 
-#define PRESENT_ALLOC(buf, bytes)                                                                                       \
-    do {                                                                                                                \
-        const hipError_t e_ = (buf).alloc(bytes);                                                                       \
-        if (e_ != hipSuccess) {                                                                                         \
-            (void)hipGetLastError();                                                                                    \
-            tsp::set_error("tsp_present: cannot allocate %zu bytes of device memory: %s", (size_t)(bytes),              \
-                           hipGetErrorString(e_));                                                                      \
-            return e_ == hipErrorOutOfMemory ? TSP_ENOMEM : TSP_EHIP;                                                   \
-        }                                                                                                               \
-    } while (0)
-
 // One frame: exactly one of `base` (the four maps of tsp_present) and `surf` (the lit surface) is given.  ms_out: base: the
 // composition (+ conversion); surf: [filter, composition (+ conversion)].
 int compose(tsp_context *ctx, int W, int H, const tsp_present_base *base, const tsp_surface_params *surf,
@@ -458,12 +447,12 @@ int compose(tsp_context *ctx, int W, int H, const tsp_present_base *base, const 
     const size_t frame_bytes = (size_t)W * H * (hdr ? 8 : 4);
     const size_t out_bytes = yuv420 ? (size_t)W * H + 2 * ((size_t)(W / 2) * (H / 2)) : frame_bytes;
     DeviceScratch d_tex, d_prims, d_lut, d_frame, d_yuv, d_filtered;
-    PRESENT_ALLOC(d_frame, frame_bytes);
-    if (yuv420) PRESENT_ALLOC(d_yuv, out_bytes);
-    PRESENT_ALLOC(d_prims, prims.size() * sizeof(PresentPrim));
-    PRESENT_ALLOC(d_tex, (size_t)n_texels * sizeof(float4));
-    if (h_lut) PRESENT_ALLOC(d_lut, (size_t)n_lut * sizeof(float4));
-    if (surf) PRESENT_ALLOC(d_filtered, (size_t)ctx->R * ctx->R * sizeof(float2));
+    TSP_SCRATCH_ALLOC("tsp_present", d_frame, frame_bytes);
+    if (yuv420) TSP_SCRATCH_ALLOC("tsp_present", d_yuv, out_bytes);
+    TSP_SCRATCH_ALLOC("tsp_present", d_prims, prims.size() * sizeof(PresentPrim));
+    TSP_SCRATCH_ALLOC("tsp_present", d_tex, (size_t)n_texels * sizeof(float4));
+    if (h_lut) TSP_SCRATCH_ALLOC("tsp_present", d_lut, (size_t)n_lut * sizeof(float4));
+    if (surf) TSP_SCRATCH_ALLOC("tsp_present", d_filtered, (size_t)ctx->R * ctx->R * sizeof(float2));
 
     for (int l = 0; l < n_layers; ++l)
         if (tex_at[l] >= 0)

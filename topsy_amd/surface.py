@@ -4,25 +4,22 @@ filter and the lit shading (colormap.surface.ColorAsSurfaceMap), what the refere
 It shares the visualizer's context, particles, quantity and camera, and renders into the same device target: a later read of
 the visualizer re-renders its own frame, and the other way round.
 
-It has the frame interface of VisualizerBase -- get_presentation_image / get_presentation_image_yuv420 (the lit surface on a
-canvas of any size under the colorbar, scale bar, crosshairs and status line, composed on the GPU by tsp_present_surface), the
-show_* switches, display_status, the view-state properties and the frame listeners -- so that what is written against a
-visualizer's frames, topsy_amd.VisualizationRecorder included, works on a view."""
+It has the frame interface of VisualizerBase -- frames.FrameInterface (the lit surface on a canvas of any size under the
+colorbar, scale bar, crosshairs and status line, composed on the GPU by tsp_present_surface) and the view-state properties --
+so that what is written against a visualizer's frames, topsy_amd.VisualizationRecorder included, works on a view."""
 import copy
 
 import numpy as np
 
-from . import overlays, sph
+from . import sph
 from .colormap.surface import ColorAsSurfaceMap
 from .drawreason import DrawReason
+from .frames import FrameInterface
 
 
-class SurfaceView:
-    show_status = True     # layers of get_presentation_image, the visualizer's defaults
-    show_colorbar = True
-    show_scalebar = True
-    crosshairs_visible = False
+class SurfaceView(FrameInterface):
     canvas_format = "rgba8unorm"
+    _render_mode = "surface"
 
     def __init__(self, visualizer, **colormap_params):
         if getattr(visualizer.particle_buffers.context, "n_gpus", 1) != 1:
@@ -35,10 +32,7 @@ class SurfaceView:
         params = {"vmin": None, "vmax": None, "weighted_average": visualizer.quantity_name is not None}
         self._colormap = ColorAsSurfaceMap(None, self._sph.get_output_texture(), "rgba8unorm", params | colormap_params)
         self._quantity = visualizer.quantity_name
-        self._colorbar = overlays.ColorbarOverlay()
-        self._scalebar = overlays.ScalebarOverlay(visualizer.data_loader.get_position_units())
-        self._status = overlays.StatusLine()
-        self._frame_listeners = []
+        self._init_frames(visualizer.data_loader.get_position_units())
         self._sync_camera()
 
     def _sync_camera(self):
@@ -88,78 +82,23 @@ class SurfaceView:
     def colormap_autorange(self):
         self._colormap.autorange_vmin_vmax(self.get_raw_image())
 
-    # -- composed frames (reference visualizer.py:367-384,480-491 in render_mode "surface") ----------
-    def get_presentation_image(self, resolution=(640, 480)):
-        """The full frame, (H, W, 4) uint8 for resolution = (W, H): the lit surface on the canvas with the colorbar of the
-        material, scale bar, crosshairs and status line on top, composed on the GPU in one call (tsp_present_surface)."""
-        width, height, ctx, params, layers = self._prepare_presentation(resolution)
-        out = ctx.present_surface(width, height, params, layers)
-        self._frame_produced()
-        return out
-
-    def get_presentation_image_yuv420(self, resolution=(1920, 1080)):
-        """The frame get_presentation_image(resolution) composes, as I420 planes for a movie encoder: uint8 Y (H, W), U and V
-        (H/2, W/2), converted on the GPU (tsp_present_surface_yuv420).  W and H must be even."""
-        width, height = (int(v) for v in resolution)
-        if width % 2 or height % 2:
-            raise ValueError(f"4:2:0 frames need an even width and height, not {width} x {height}")
-        width, height, ctx, params, layers = self._prepare_presentation(resolution)
-        out = ctx.present_surface_yuv420(width, height, params, layers)
-        self._frame_produced()
-        return out
-
-    def _prepare_presentation(self, resolution):
-        """The EXPORT occlusion render, the material range, the surface parameters and the layers of a (W, H) frame."""
-        width, height = (int(v) for v in resolution)
-        if not (1 <= width <= 16384 and 1 <= height <= 16384):
-            raise ValueError(f"resolution {resolution} outside 1 .. 16384 pixels per side")
+    # -- the composed frame's base and colorbar (frames.FrameInterface; reference visualizer.py:367-384,480-491 in render_mode "surface")
+    def _presentation_base(self, width, height):
         self.render(DrawReason.EXPORT)
         if self._colormap.get_parameter("vmin") is None or self._colormap.get_parameter("vmax") is None:
             self.colormap_autorange()
-        params = self._colormap.surface_parameters()
-        layers = self._presentation_layers(width, height)
-        self._last_presentation = (params, layers)      # what the frame was composed from (tests restate it)
-        return width, height, self._sph._context, params, layers
+        return self._colormap.surface_parameters()
 
-    def _presentation_layers(self, width, height):
-        """The layers in the reference's order (visualizer.py:367-384): colorbar, scale bar, crosshairs, status line.  A surface
-        map has a colorbar only when it colours by a quantity (visualizer.py:327-328)."""
-        layers = []
-        p = self._colormap.get_parameters()
-        if self.show_colorbar and p["weighted_average"]:
-            layers.append(self._colorbar.layer(p["vmin"], p["vmax"], p["colormap_name"], self._get_colorbar_label(), width, height))
-        if self.show_scalebar:
-            layers += self._scalebar.layers(self.scale, width, height)
-        if self.crosshairs_visible:
-            layers.append(overlays.crosshairs_layer())
-        if self.show_status:
-            self._status.update(self._sph)
-            layers.append(self._status.layer(width, height))
-        # a canvas a few pixels high gives the colorbar figure no pixels at all: such a layer has nothing to draw
-        return [L for L in layers if L["kind"] != "quad" or min(L["texture"].shape[:2]) > 0]
+    def _compose_frame(self, width, height, params, layers, yuv420):
+        ctx = self._sph._context
+        return (ctx.present_surface_yuv420 if yuv420 else ctx.present_surface)(width, height, params, layers)
 
-    def _get_colorbar_label(self):
-        """The quantity's label, marked as a log10 when the material map is logarithmic (reference visualizer.py:341-346)."""
-        prefix = r"$\log_{10}$ " if self._colormap.get_parameter("log") else ""
-        return prefix + self._vis.data_loader.get_quantity_label(self.quantity_name)
-
-    def display_status(self, text, timeout=0.5):
-        """Show `text` in the status line of the next frames for `timeout` seconds."""
-        self._status.display(text, timeout)
-
-    # -- frame listeners ----------------------------------------------------------------------------
-    def add_frame_listener(self, callback):
-        """Call callback(view) after every frame of get_presentation_image and get_presentation_image_yuv420."""
-        self._frame_listeners.append(callback)
-
-    def remove_frame_listener(self, callback):
-        self._frame_listeners.remove(callback)
-
-    def _frame_produced(self):
-        for callback in list(self._frame_listeners):
-            callback(self)
+    def _has_colorbar(self):
+        return self._colormap.get_parameter("weighted_average")      # only when it colours by a quantity (visualizer.py:327-328)
 
     # -- view state: the visualizer's ------------------------------------------------------------------
+    data_loader = property(lambda self: self._vis.data_loader)
+
     @property
     def rotation_matrix(self):
         return self._vis.rotation_matrix

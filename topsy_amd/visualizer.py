@@ -5,11 +5,8 @@ Windowing and view synchronisation are out of scope; what 
 the orchestrator -- rotate / scale / position_offset / quantity_name / render_mode / invalidate / draw /
 colormap_autorange / get_sph_image / get_sph_presentation_image / get_depth_image / save -- is here with
 the reference's semantics, so those layers can sit on top unchanged.
-get_presentation_image composes the full frame of any size on the GPU (tsp_present): the colormapped
-image with the colorbar, scale bar, crosshairs, simulation cube and status line of topsy_amd/overlays.py;
-get_presentation_image_yuv420 returns that frame as the I420 planes a movie encoder reads
-(tsp_present_yuv420).  add_frame_listener lets the movie recorder (topsy_amd/recorder) sample the view
-state at every frame the visualizer produces.
+The composed frames (get_presentation_image, get_presentation_image_yuv420), their layer switches and the
+frame listeners come from topsy_amd/frames.py, shared with SurfaceView.
 """
 import logging
 
@@ -17,6 +14,7 @@ import numpy as np
 
 from . import colormap, config, loader, overlays, particle_buffers, periodic_sph, sph
 from .drawreason import DrawReason
+from .frames import FrameInterface
 
 logger = logging.getLogger(__name__)
 
@@ -26,12 +24,8 @@ _UNSUPPORTED_MODES = {
 }
 
 
-class VisualizerBase:
+class VisualizerBase(FrameInterface):
     device = None      # kept for signature compatibility; the GPU is owned by particle_buffers.context
-    show_status = True     # layers of get_presentation_image, the reference's defaults (visualizer.py:34,53-60)
-    show_colorbar = True
-    show_scalebar = True
-    crosshairs_visible = False
 
     def __init__(self, data_loader_class=loader.TestDataLoader, data_loader_args=(), data_loader_kwargs={},
                  *, render_resolution=config.DEFAULT_RESOLUTION, periodic_tiling=False,
@@ -61,10 +55,7 @@ class VisualizerBase:
         if periodic_tiling and not self.periodicity_scale:
             raise ValueError("periodic_tiling needs a data loader with a finite periodicity scale")
         self._pending_draw = None
-        self._colorbar = overlays.ColorbarOverlay()
-        self._scalebar = overlays.ScalebarOverlay(self.data_loader.get_position_units())
-        self._status = overlays.StatusLine()
-        self._frame_listeners = []
+        self._init_frames(self.data_loader.get_position_units())
         self._initialize_sph_and_colormap(colormap_name)
 
     # -- mode plumbing (reference visualizer.py:96-120, 170-186, 203-231) ----------------------
@@ -247,19 +238,6 @@ class VisualizerBase:
             self._frame_produced()
         return out
 
-    # -- frame listeners (what the reference's view synchronizer tells the recorder) --------------
-    def add_frame_listener(self, callback):
-        """Call callback(visualizer) after every frame: draw for any reason but REFINE and PRESENTATION_CHANGE,
-        get_sph_presentation_image, get_presentation_image and get_presentation_image_yuv420."""
-        self._frame_listeners.append(callback)
-
-    def remove_frame_listener(self, callback):
-        self._frame_listeners.remove(callback)
-
-    def _frame_produced(self):
-        for callback in list(self._frame_listeners):
-            callback(self)
-
     # -- exports (reference visualizer.py:452-570) ---------------------------------------------
     def get_sph_image(self):
         """Logical content of the SPH image (no colormap): density, weighted mean, or rgb."""
@@ -274,68 +252,23 @@ class VisualizerBase:
         self._frame_produced()
         return out
 
-    def get_presentation_image(self, resolution=(640, 480)):
-        """The full frame, (H, W, 4) uint8 (float16 for rgb-hdr) for resolution = (W, H): the image colormapped onto the canvas
-        with the colorbar, scale bar, crosshairs, simulation cube and status line on top (reference visualizer.py:480-491,
-        367-384), composed on the GPU in one pass (tsp_present)."""
-        width, height, ctx, base, layers = self._prepare_presentation(resolution)
-        out = ctx.present(width, height, base, layers)
-        self._frame_produced()
-        return out
-
-    def get_presentation_image_yuv420(self, resolution=(1920, 1080)):
-        """The frame get_presentation_image(resolution) composes, as I420 planes for a movie encoder: uint8 Y (H, W), U and V
-        (H/2, W/2), BT.709 limited range, converted on the GPU (tsp_present_yuv420, include/topsy_splat.h).  W and H must be
-        even; the rgb-hdr canvas has no 8-bit frame (ValueError)."""
-        width, height = (int(v) for v in resolution)
-        if width % 2 or height % 2:
-            raise ValueError(f"4:2:0 frames need an even width and height, not {width} x {height}")
-        if self.canvas_format != "rgba8unorm":
-            raise ValueError(f"4:2:0 frames are 8-bit: the {self._render_mode} canvas ({self.canvas_format}) has none")
-        width, height, ctx, base, layers = self._prepare_presentation(resolution)
-        out = ctx.present_yuv420(width, height, base, layers)
-        self._frame_produced()
-        return out
-
-    def _prepare_presentation(self, resolution):
-        """The EXPORT render, the colormap scaling, the base and the layers of a (W, H) frame."""
-        width, height = (int(v) for v in resolution)
-        if not (1 <= width <= 16384 and 1 <= height <= 16384):
-            raise ValueError(f"resolution {resolution} outside 1 .. 16384 pixels per side")
+    # -- the composed frame's base, colorbar and extra layer (frames.FrameInterface) -----------------
+    def _presentation_base(self, width, height):
         self.render_sph(DrawReason.EXPORT)
         self._colormap.set_scaling(width, height, self._sph.last_render_mass_scale)
+        return self._colormap.present_base(self._sph._context)
+
+    def _compose_frame(self, width, height, base, layers, yuv420):
         ctx = self._sph._context
-        base = self._colormap.present_base(ctx)
-        layers = self._presentation_layers(width, height)
-        self._last_presentation = (base, layers)      # what the frame was composed from (tests restate it)
-        return width, height, ctx, base, layers
+        return (ctx.present_yuv420 if yuv420 else ctx.present)(width, height, base, layers)
 
-    def _presentation_layers(self, width, height):
-        """The layers in the reference's order (visualizer.py:367-384): colorbar, scale bar, crosshairs, cube, status line."""
-        layers = []
-        if self.show_colorbar and self._colormap.colormap_kind() != "rgb":        # no colorbar for rgb maps (:327-335)
-            p = self._colormap.get_parameters()
-            layers.append(self._colorbar.layer(p["vmin"], p["vmax"], p["colormap_name"], self._get_colorbar_label(), width, height))
-        if self.show_scalebar:
-            layers += self._scalebar.layers(self.scale, width, height)
-        if self.crosshairs_visible:
-            layers.append(overlays.crosshairs_layer())
-        if self._periodic_tiling:
-            layers.append(overlays.simcube_layer(self.data_loader.get_periodicity_scale(), self._sph._transform[0], width, height))
-        if self.show_status:
-            self._status.update(self._sph)
-            layers.append(self._status.layer(width, height))
-        # a canvas a few pixels high gives the colorbar figure no pixels at all: such a layer has nothing to draw
-        return [L for L in layers if L["kind"] != "quad" or min(L["texture"].shape[:2]) > 0]
+    def _has_colorbar(self):
+        return self._colormap.colormap_kind() != "rgb"        # no colorbar for rgb maps (reference visualizer.py:327-335)
 
-    def _get_colorbar_label(self):
-        """The quantity's label, marked as a log10 when the map is logarithmic (reference visualizer.py:341-346)."""
-        prefix = r"$\log_{10}$ " if self._colormap.get_parameter("log") else ""
-        return prefix + self.data_loader.get_quantity_label(self.quantity_name)
-
-    def display_status(self, text, timeout=0.5):
-        """Show `text` in the status line of the next frames for `timeout` seconds (reference visualizer.py:426-428)."""
-        self._status.display(text, timeout)
+    def _extra_layers(self, width, height):
+        if not self._periodic_tiling:
+            return []
+        return [overlays.simcube_layer(self.data_loader.get_periodicity_scale(), self._sph._transform[0], width, height)]
 
     def get_depth_image(self):
         depth = self._sph.get_depth_image()
