@@ -88,7 +88,9 @@ const char *tsp_last_error(void);
  * the layers of tsp_present, and that frame as I420 planes); no struct changed, nothing else changed.
  * 113: new entry point tsp_shrink_sphere_center and the struct tsp_center_info (a snapshot's centre); nothing else changed.
  * 114: new entry point tsp_fof_groups and the struct tsp_fof_info (friends-of-friends groups: a halo catalogue for arrays);
- * nothing else changed. */
+ * nothing else changed.
+ * 115: new entry point tsp_sphere_moments and the struct tsp_moments (the moments of the particles inside a sphere: what a
+ * face-on or side-on orientation is taken from); nothing else changed. */
 int tsp_version(void);
 int tsp_stats_size(void);
 
@@ -339,6 +341,48 @@ typedef struct {
 } tsp_fof_info;
 int tsp_fof_groups(tsp_context *ctx, int64_t n, const float *x, const float *y, const float *z, float linking_length,
                    float period, int64_t min_members, int32_t *group_out, tsp_fof_info *info_out);
+
+/* The moments of the particles inside a sphere: what pynbody.analysis.angmom.faceon / sideon take a disc's orientation from (the
+ * mean velocity of a small sphere, then the angular momentum of a larger one about it), and the second-moment tensor for
+ * snapshots without velocities.  Host arrays in, caller's order; uses ctx's device and stream only: resident particles, image,
+ * accumulator and tsp_stats unchanged.  Float64 throughout unless said otherwise (no fused multiply-adds):
+ *   - Velocities.  vx, vy, vz are all given or all NULL.
+ *   - Valid particles.  Particle i is valid iff x[i], y[i], z[i], mass[i] (and vx[i], vy[i], vz[i] when given) are finite and
+ *     mass[i] > 0.  m = (double)mass[i].
+ *   - Membership.  dx = (double)x[i] - center[0] (dy, dz alike), d2 = (dx * dx + dy * dy) + dz * dz, d = (dx, dy, dz).  A valid
+ *     particle is inside the r sphere iff d2 < r * r (strict), inside the r_vel sphere iff d2 < r_vel * r_vel.
+ *   - Pass A, only with velocities: n_inside_vel, mass_vel = sum m and sum m v over the r_vel sphere, v = the (double)
+ *     velocities; v_cen = sum m v / mass_vel.  Without velocities n_inside_vel = 0, mass_vel = 0, v_cen = 0.
+ *   - Pass B, over the r sphere: n_inside; mass = sum m; com = sum m d / mass (the offset of the centre of mass from center);
+ *     S = sum m d_i d_j in the order xx, xy, xz, yy, yz, zz, each term (m * d_i) * d_j.  With velocities, u = v - v_cen:
+ *       L_x = sum m * (dy * u_z - dz * u_y), L_y = sum m * (dz * u_x - dx * u_z), L_z = sum m * (dx * u_y - dy * u_x);
+ *       A = sum (m * sqrt(d2)) * sqrt((u_x * u_x + u_y * u_y) + u_z * u_z): the scale of L's rounding, and |L| / A the degree of
+ *       ordered rotation.  Without velocities L = 0 and A = 0.
+ *     The displacements are formed in float64 before anything is multiplied, so the rounding error is proportional to r and not
+ *     to |center|.
+ *   - n_valid counts the valid particles, inside or not.
+ *   - The order of every sum is free but fixed (no floating-point atomics; per-wave and per-workgroup partial sums are combined in
+ *     a fixed order, the grid is a function of n and the device): the same call on the same input and device returns the same
+ *     bits.  Counts are integers.
+ * 1 <= n < 2^31; no NULL among x, y, z, mass, center, out; center finite; r finite and > 0; with velocities r_vel finite and
+ * 0 < r_vel <= r, without r_vel = 0; at least one valid particle; anything else returns TSP_EINVAL and writes nothing.  So does an
+ * r sphere or, with velocities, an r_vel sphere without a valid particle inside: tsp_last_error names the sphere.  Not provided:
+ * periodic wrapping of the displacements.  Device memory is allocated for the call only (about 16 bytes per particle, 28 with
+ * velocities); a failed allocation returns TSP_ENOMEM and writes nothing.  The cost is one pass per sphere over those bytes, less
+ * the blocks of 1024 consecutive particles whose bounding box lies outside the sphere: those are not read (identical results; pays
+ * with a spatial order of the arrays, and makes the r_vel pass almost free there). */
+typedef struct {
+    int64_t n_valid, n_inside, n_inside_vel;   /* valid particles; inside r; inside r_vel (0 without velocities) */
+    double  mass, mass_vel;                    /* sum m inside r / inside r_vel */
+    double  com[3];                            /* sum m d / mass        (offset of the centre of mass from center) */
+    double  v_cen[3];                          /* sum m v / mass_vel over the r_vel sphere; zeros without velocities */
+    double  L[3];                              /* sum m d x (v - v_cen) over the r sphere; zeros without velocities */
+    double  S[6];                              /* sum m d_i d_j over the r sphere: xx, xy, xz, yy, yz, zz */
+    double  A;                                 /* sum m |d| |v - v_cen| over the r sphere (the scale of L's rounding) */
+} tsp_moments;
+int tsp_sphere_moments(tsp_context *ctx, int64_t n, const float *x, const float *y, const float *z, const float *mass,
+                       const float *vx, const float *vy, const float *vz,      /* all three or none (NULL) */
+                       const double center[3], double r, double r_vel, tsp_moments *out);
 
 /* Surface rendering: DepthSPHWithOcclusion + ColorAsSurfaceMap (reference src/topsy/sph.py:448-656, shaders/sph.wgsl:94-122,
  * 149-158, shaders/smooth.wgsl, shaders/surface.wgsl, colormap/surface.py).  Float32 throughout, operations in the order written.

@@ -26,7 +26,7 @@ def test(nparticle=config.TEST_DATA_NUM_PARTICLES_DEFAULT, **kwargs):
 
 
 def from_arrays(pos, smooth, mass, quantities=None, rgb=None, with_cells=False, n_smooth=None, periodicity_scale=None,
-                center="none", halos=None, **kwargs):
+                center="none", halos=None, vel=None, orient="none", orient_radius=None, orient_method=None, **kwargs):
     """Visualizer over caller-supplied numpy arrays (e.g. taken from a pynbody snapshot).
 
     smooth=None computes the smoothing lengths on the GPU from the n_smooth (default config.SMOOTH_NEIGHBOURS) nearest
@@ -43,13 +43,22 @@ def from_arrays(pos, smooth, mass, quantities=None, rgb=None, with_cells=False, 
     halos: the halo catalogue -- "fof" (friends-of-friends groups found on the GPU: friends_of_friends, in the periodic box of
     periodicity_scale if one is given), a dict of its keywords (linking_length, b, min_members), or your own integer (n,) labels
     (halo N is label N; <= 0: no halo).  With it center="halo-N" opens the view on halo N (1 = the largest) and
-    vis.centre_on_halo(N) jumps there; vis.data_loader.get_halos() returns the catalogue, set_halos() restores it."""
+    vis.centre_on_halo(N) jumps there; vis.data_loader.get_halos() returns the catalogue, set_halos() restores it.
+
+    vel, orient: the angle the view opens at -- orient="faceon" or "sideon" turns the view (no particle moves) so that the disc
+    inside the sphere of radius orient_radius (required: a length in the units of pos) around the initial centre, whatever center=
+    produced, is seen face-on or edge-on, as pynbody.analysis.angmom.faceon / sideon do.  vel, the (n, 3) velocities, gives the
+    axis as the angular momentum about the mean velocity of the inner fifth of the sphere (orient_method="angmom", the default
+    with vel); without it the axis is the minor axis of the particles' second-moment tensor ("shape").  The moments are found on
+    the GPU (sphere_moments); vis.data_loader.get_initial_rotation() returns the matrix, set_initial_rotation() restores it,
+    and vis.orient("faceon" | "sideon", radius) re-orients on whatever the view is centred on."""
     from . import visualizer, loader
     return visualizer.Visualizer(data_loader_class=loader.ArrayDataLoader,
                                  data_loader_kwargs={"pos": pos, "smooth": smooth, "mass": mass,
                                                      "quantities": quantities, "rgb": rgb, "with_cells": with_cells,
                                                      "n_smooth": n_smooth, "periodicity_scale": periodicity_scale,
-                                                     "center": center, "halos": halos},
+                                                     "center": center, "halos": halos, "vel": vel, "orient": orient,
+                                                     "orient_radius": orient_radius, "orient_method": orient_method},
                                  **kwargs)
 
 
@@ -159,6 +168,36 @@ def shrink_sphere_center(pos, mass, select="all", r_start=None, shrink_factor=0.
                                         shrink_factor=shrink, min_particles=min_particles)
     finally:
         ctx.close()
+
+
+def sphere_moments(pos, mass, vel=None, center=(0, 0, 0), radius=None, vel_radius=None, device_id=0):
+    """Moments of the particles of an (n, 3) position array inside the sphere of `radius` (required) around `center`, on GPU
+    `device_id` (C: tsp_sphere_moments), as a dict: n_valid, n_inside, mass, com (the offset of the centre of mass from center),
+    S (sum m d_i d_j: xx, xy, xz, yy, yz, zz) and, with vel (n, 3), n_inside_vel, mass_vel and v_cen (the mean velocity inside
+    vel_radius; None: radius / 5, the ratio of pynbody's 1 kpc to 5 kpc), L (sum m d x (v - v_cen)) and A (sum m |d| |v - v_cen|).
+    Float64 sums of displacements formed in float64.  Particles with a non-finite coordinate or velocity or a mass that is not
+    finite and > 0 take no part.  Out of scope: periodic wrapping of the displacements."""
+    from . import _native, loader
+    pos, mass, vel = loader.check_moments_arrays(pos, mass, vel)
+    c, r, r_vel = loader.check_moments_arguments(center, radius, vel_radius, vel is not None)
+    ctx = _native.Context(1, 2, device_id)
+    try:
+        return loader.compute_moments(ctx, pos, mass, vel, c, r, r_vel)
+    finally:
+        ctx.close()
+
+
+def orientation(pos, mass, vel=None, center=(0, 0, 0), radius=None, vel_radius=None, orient="faceon", method=None, up=(0, 1, 0),
+                device_id=0):
+    """The rotation that shows the disc inside the sphere of `radius` around `center` face-on (orient="faceon": its axis toward
+    the viewer) or edge-on ("sideon": its axis up the screen), as (matrix float64 (3, 3), the moments of sphere_moments).  The axis:
+    method="angmom", the angular momentum L (the default with vel), or "shape", the minor axis of the second-moment tensor about
+    the centre of mass (the default without).  The matrix is pynbody's calc_faceon_matrix: rows up x a, a x (up x a), a.
+    ValueError where the sphere has no net rotation / no unique minor axis."""
+    from . import loader
+    method = loader.check_orient_arguments(orient, method, vel is not None)
+    moments = sphere_moments(pos, mass, vel, center, radius, vel_radius, device_id)
+    return loader.orientation_matrix(moments, orient, method, up), moments
 
 
 def friends_of_friends(pos, linking_length=None, b=0.2, min_members=20, periodicity_scale=None, device_id=0):

@@ -17,7 +17,8 @@ PIPE_DEFAULT, PIPE_GENERIC = 0, 1
 SAMPLE_BILINEAR_MIP0, SAMPLE_BILINEAR_MIP = 0x10, 0x20      # diagnostic sampling rules (generic kernel)
 UNIQUE_ID_BYTES = 128
 ABI_VERSION = 112            # the oldest tsp_version() whose structs this binding matches; entry points added since
-                             # (113: tsp_shrink_sphere_center, 114: tsp_fof_groups) are required by name in load_library()
+                             # (113: tsp_shrink_sphere_center, 114: tsp_fof_groups, 115: tsp_sphere_moments) are required by
+                             # name in load_library()
 PRESENT_SCALAR, PRESENT_BIVARIATE, PRESENT_RGB, PRESENT_RGB_HDR = 0, 1, 2, 3
 LAYER_QUAD, LAYER_LINES = 0, 1
 
@@ -57,6 +58,21 @@ class FofInfo(ctypes.Structure):
     """struct tsp_fof_info."""
     _fields_ = [("n_valid", ctypes.c_int64), ("n_groups", ctypes.c_int64), ("n_grouped", ctypes.c_int64),
                 ("largest", ctypes.c_int64)]
+
+
+class Moments(ctypes.Structure):
+    """struct tsp_moments."""
+    _fields_ = [("n_valid", ctypes.c_int64), ("n_inside", ctypes.c_int64), ("n_inside_vel", ctypes.c_int64),
+                ("mass", ctypes.c_double), ("mass_vel", ctypes.c_double), ("com", ctypes.c_double * 3),
+                ("v_cen", ctypes.c_double * 3), ("L", ctypes.c_double * 3), ("S", ctypes.c_double * 6), ("A", ctypes.c_double)]
+
+    def as_dict(self):
+        """Counts as int, sums as float, vectors as float64 arrays."""
+        out = {}
+        for name, kind in self._fields_:
+            v = getattr(self, name)
+            out[name] = int(v) if kind is ctypes.c_int64 else float(v) if kind is ctypes.c_double else np.array(v, dtype=np.float64)
+        return out
 
 
 class BackendUnavailable(RuntimeError):
@@ -129,6 +145,8 @@ SIGNATURES = {
                                                 ctypes.POINTER(CenterInfo)]),
     "tsp_fof_groups": (ctypes.c_int, [_ctx, ctypes.c_int64, _fp, _fp, _fp, ctypes.c_float, ctypes.c_float, ctypes.c_int64,
                                       ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(FofInfo)]),
+    "tsp_sphere_moments": (ctypes.c_int, [_ctx, ctypes.c_int64, _fp, _fp, _fp, _fp, _fp, _fp, _fp, ctypes.POINTER(ctypes.c_double),
+                                          ctypes.c_double, ctypes.c_double, ctypes.POINTER(Moments)]),
     "tsp_set_sphere_mips": (ctypes.c_int, [_ctx, _fp, ctypes.c_int, ctypes.c_int]),
     "tsp_density_order_stats": (ctypes.c_int, [_ctx, _i64p, ctypes.c_int, _fp]),
     "tsp_render_surface": (ctypes.c_int, [_ctx, _fp, ctypes.c_float, ctypes.c_float, _i64p, _i64p, ctypes.c_int, ctypes.c_int,
@@ -438,6 +456,28 @@ class Context:
                                         out.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), ctypes.byref(info)))
         return out, {"n_valid": int(info.n_valid), "n_groups": int(info.n_groups), "n_grouped": int(info.n_grouped),
                      "largest": int(info.largest)}
+
+    def sphere_moments(self, x, y, z, mass, vel=None, center=(0.0, 0.0, 0.0), r=1.0, r_vel=0.0):
+        """Moments of the caller-ordered float32 particles inside the sphere of radius r around center (tsp_sphere_moments):
+        mass, com (the offset of the centre of mass from center), the second moments S (xx, xy, xz, yy, yz, zz) and, with
+        vel = (vx, vy, vz), the mean velocity v_cen of the sphere of radius r_vel, the angular momentum L about it and its
+        scale A.  Returns a dict of the fields of struct tsp_moments (counts int, sums float, vectors float64 arrays).  Uses this
+        context's device only; what is resident stays."""
+        n = len(x)
+        x, y, z, mass = _f32(x, n, "x"), _f32(y, n, "y"), _f32(z, n, "z"), _f32(mass, n, "mass")
+        if vel is not None:
+            if len(vel) != 3:
+                raise ValueError("vel must be the three arrays (vx, vy, vz)")
+            vel = [_f32(v, n, name) for v, name in zip(vel, ("vx", "vy", "vz"))]
+        vx, vy, vz = vel if vel is not None else (None, None, None)
+        center = np.ascontiguousarray(center, dtype=np.float64)
+        if center.shape != (3,):
+            raise ValueError(f"center must be three coordinates, not shape {center.shape}")
+        out = Moments()
+        _check(self._lib.tsp_sphere_moments(self._h, n, _ptr(x), _ptr(y), _ptr(z), _ptr(mass), _ptr(vx), _ptr(vy), _ptr(vz),
+                                            center.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), float(r), float(r_vel),
+                                            ctypes.byref(out)))
+        return out.as_dict()
 
     # ---- surface (include/topsy_splat.h "Surface rendering") ---------------------------------
     def set_sphere_mips(self, mips, n0=64, n_levels=4):

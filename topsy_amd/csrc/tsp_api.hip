@@ -203,7 +203,7 @@ using namespace tsp;
 extern "C" {
 
 const char *tsp_last_error(void) { return g_err; }
-int tsp_version(void) { return 114; }     // 114: tsp_fof_groups; 113: tsp_shrink_sphere_center; 112: tsp_present_surface, tsp_present_surface_yuv420; 111: tsp_content_neg_inf; 110: tsp_sph_sum; 109: tsp_present_yuv420; 108: tsp_present; 107: surface rendering; 106: tsp_smoothing_lengths; 101: tsp_stats gained ms_mega, n_mega (16 bytes); 102: the per-kernel fragment counts (32 bytes); 103: n_chunk_culled (8 bytes); 104: matrix-core / kernel-I options removed; 105: kernel M's options removed (kernel G draws the mid footprints)
+int tsp_version(void) { return 115; }     // 115: tsp_sphere_moments; 114: tsp_fof_groups; 113: tsp_shrink_sphere_center; 112: tsp_present_surface, tsp_present_surface_yuv420; 111: tsp_content_neg_inf; 110: tsp_sph_sum; 109: tsp_present_yuv420; 108: tsp_present; 107: surface rendering; 106: tsp_smoothing_lengths; 101: tsp_stats gained ms_mega, n_mega (16 bytes); 102: the per-kernel fragment counts (32 bytes); 103: n_chunk_culled (8 bytes); 104: matrix-core / kernel-I options removed; 105: kernel M's options removed (kernel G draws the mid footprints)
 int tsp_stats_size(void) { return (int)sizeof(tsp_stats); }
 
 int tsp_device_count(void) {
@@ -810,6 +810,24 @@ int tsp_fof_groups(tsp_context *ctx, int64_t n, const float *x, const float *y, 
     TSP_REQUIRE(min_members >= 1, TSP_EINVAL, "min_members = %lld below 1", (long long)min_members);
     TSP_HIP(hipSetDevice(ctx->device));
     return fof_groups(ctx, n, x, y, z, linking_length, period == 0.0f ? 0.0f : period, min_members, group_out, info_out);
+}
+
+int tsp_sphere_moments(tsp_context *ctx, int64_t n, const float *x, const float *y, const float *z, const float *mass,
+                       const float *vx, const float *vy, const float *vz, const double center[3], double r, double r_vel,
+                       tsp_moments *out) {
+    TSP_REQUIRE(ctx && x && y && z && mass && center && out, TSP_EINVAL, "NULL argument");
+    TSP_REQUIRE((vx && vy && vz) || (!vx && !vy && !vz), TSP_EINVAL, "vx, vy and vz must be given together or not at all");
+    TSP_REQUIRE(n >= 1 && n < (1ll << 31), TSP_EINVAL, "n = %lld outside [1, 2^31)", (long long)n);
+    TSP_REQUIRE(std::isfinite(center[0]) && std::isfinite(center[1]) && std::isfinite(center[2]), TSP_EINVAL,
+                "center = (%g, %g, %g) is not finite", center[0], center[1], center[2]);
+    TSP_REQUIRE(std::isfinite(r) && r > 0.0, TSP_EINVAL, "r must be finite and > 0, not %g", r);
+    if (vx)
+        TSP_REQUIRE(std::isfinite(r_vel) && r_vel > 0.0 && r_vel <= r, TSP_EINVAL,
+                    "with velocities r_vel must be finite with 0 < r_vel <= r = %g, not %g", r, r_vel);
+    else
+        TSP_REQUIRE(r_vel == 0.0, TSP_EINVAL, "without velocities r_vel must be 0, not %g", r_vel);
+    TSP_HIP(hipSetDevice(ctx->device));
+    return sphere_moments(ctx, n, x, y, z, mass, vx, vy, vz, center, r, r_vel == 0.0 ? 0.0 : r_vel, out);
 }
 
 int tsp_present(tsp_context *ctx, int width, int height, const tsp_present_base *base, const tsp_present_layer *layers,

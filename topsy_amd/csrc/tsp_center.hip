@@ -31,12 +31,12 @@
 #include <chrono>
 #include <vector>
 
+#include "tsp_blocks.h"
 #include "tsp_internal.h"
 
 namespace tsp {
 namespace {
 
-constexpr int CBLK = 1024;      // particles per block: one float4 per lane of a 256-lane workgroup
 constexpr unsigned INF_BITS = 0x7f800000u;
 
 struct Partial {                // 64 bytes: what a workgroup (and the whole pass) sums
@@ -91,10 +91,6 @@ __device__ __forceinline__ void workgroup_sum_store(Partial a, Partial *out) {
     }
 }
 
-__device__ __forceinline__ bool valid_before_cut(float x, float y, float z, float m) {
-    return __builtin_isfinite(x) && __builtin_isfinite(y) && __builtin_isfinite(z) && __builtin_isfinite(m) && m > 0.0f;
-}
-
 // 0. the smallest positive finite mass of a particle with finite coordinates (positive floats order as their bits)
 __global__ __launch_bounds__(256) void center_min_mass_kernel(const float *__restrict__ x, const float *__restrict__ y,
                                                               const float *__restrict__ z, const float *__restrict__ m, int64_t n,
@@ -102,7 +98,7 @@ __global__ __launch_bounds__(256) void center_min_mass_kernel(const float *__res
     unsigned lo = INF_BITS;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
         const float mi = m[i];
-        if (valid_before_cut(x[i], y[i], z[i], mi)) lo = min(lo, __float_as_uint(mi));
+        if (finite_position_and_mass(x[i], y[i], z[i], mi)) lo = min(lo, __float_as_uint(mi));
     }
     for (int off = 32; off; off >>= 1) lo = min(lo, (unsigned)__shfl_xor((int)lo, off));
     if ((threadIdx.x & 63) == 0 && lo != INF_BITS) atomicMin(min_bits, lo);
@@ -114,7 +110,6 @@ __global__ __launch_bounds__(256) void center_prepare_kernel(const float4 *__res
                                                              const float4 *__restrict__ z4, float4 *__restrict__ w4,
                                                              int64_t nblocks, double mass_limit, float *__restrict__ boxes,
                                                              Partial *__restrict__ partials) {
-    __shared__ float wave_box[4][6];
     Partial a = partial_zero();
     for (int64_t b = blockIdx.x; b < nblocks; b += gridDim.x) {
         const int64_t i4 = b * (CBLK / 4) + threadIdx.x;
@@ -122,10 +117,11 @@ __global__ __launch_bounds__(256) void center_prepare_kernel(const float4 *__res
         float4 W = w4[i4];
         const float px[4] = {X.x, X.y, X.z, X.w}, py[4] = {Y.x, Y.y, Y.z, Y.w}, pz[4] = {Z.x, Z.y, Z.z, Z.w};
         float pw[4] = {W.x, W.y, W.z, W.w};
-        float box[6] = {__builtin_inff(), __builtin_inff(), __builtin_inff(), -__builtin_inff(), -__builtin_inff(), -__builtin_inff()};
+        float box[6];
+        box_empty(box);
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
-            const bool ok = valid_before_cut(px[k], py[k], pz[k], pw[k]) && (double)pw[k] < mass_limit;
+            const bool ok = finite_position_and_mass(px[k], py[k], pz[k], pw[k]) && (double)pw[k] < mass_limit;
             if (ok) {
                 const double m = (double)pw[k];
                 a.sm += m;
@@ -135,42 +131,16 @@ __global__ __launch_bounds__(256) void center_prepare_kernel(const float4 *__res
                 ++a.count;
                 a.lo = fmin(a.lo, (double)px[k]);
                 a.hi = fmax(a.hi, (double)px[k]);
-                box[0] = fminf(box[0], px[k]);
-                box[1] = fminf(box[1], py[k]);
-                box[2] = fminf(box[2], pz[k]);
-                box[3] = fmaxf(box[3], px[k]);
-                box[4] = fmaxf(box[4], py[k]);
-                box[5] = fmaxf(box[5], pz[k]);
+                box_include(box, px[k], py[k], pz[k]);
             } else {
                 pw[k] = 0.0f;
             }
         }
         w4[i4] = make_float4(pw[0], pw[1], pw[2], pw[3]);
-        for (int off = 32; off; off >>= 1) {
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                box[c] = fminf(box[c], __shfl_xor(box[c], off));
-                box[3 + c] = fmaxf(box[3 + c], __shfl_xor(box[3 + c], off));
-            }
-        }
-        if ((threadIdx.x & 63) == 0)
-            for (int c = 0; c < 6; ++c) wave_box[threadIdx.x >> 6][c] = box[c];
-        __syncthreads();
-        if (threadIdx.x < 6) {
-            const int c = threadIdx.x;
-            float v = wave_box[0][c];
-            for (int w = 1; w < 4; ++w) v = c < 3 ? fminf(v, wave_box[w][c]) : fmaxf(v, wave_box[w][c]);
-            boxes[6 * b + c] = v;
-        }
-        __syncthreads();
+        workgroup_box_store(box, boxes + 6 * b);
         if (threadIdx.x == 0) ++a.blocks;
     }
     workgroup_sum_store(a, partials + blockIdx.x);
-}
-
-// the distance along one axis from c to the interval [lo, hi], with the subtraction d2 uses
-__device__ __forceinline__ double axis_distance(float lo, float hi, double c) {
-    return fmax(fmax((double)lo - c, c - (double)hi), 0.0);
 }
 
 __device__ __forceinline__ void center_accumulate(Partial &a, float x, float y, float z, float w, double cx, double cy, double cz,
@@ -196,11 +166,7 @@ __global__ __launch_bounds__(256) void center_pass_kernel(const float4 *__restri
                                                           double cz, double r2, Partial *__restrict__ partials) {
     Partial a = partial_zero();
     for (int64_t b = blockIdx.x; b < nblocks; b += gridDim.x) {
-        const float *box = boxes + 6 * b;
-        const double gx = axis_distance(box[0], box[3], cx);
-        const double gy = axis_distance(box[1], box[4], cy);
-        const double gz = axis_distance(box[2], box[5], cz);
-        if ((gx * gx + gy * gy) + gz * gz >= r2) continue;      // (uniform over the workgroup; an empty block's box is at +inf)
+        if (box_outside_sphere(boxes + 6 * b, cx, cy, cz, r2)) continue;      // (uniform over the workgroup)
         const int64_t i4 = b * (CBLK / 4) + threadIdx.x;
         const float4 X = x4[i4], Y = y4[i4], Z = z4[i4], W = w4[i4];
         center_accumulate(a, X.x, Y.x, Z.x, W.x, cx, cy, cz, r2);
@@ -217,10 +183,6 @@ __global__ __launch_bounds__(256) void center_final_kernel(Partial *__restrict__
     Partial a = partial_zero();
     for (int i = threadIdx.x; i < n_partials; i += 256) partial_add(a, partials[i]);
     workgroup_sum_store(a, partials + n_partials);
-}
-
-double wall_ms(std::chrono::steady_clock::time_point t0) {
-    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
 }
 
 }  // namespace

@@ -272,6 +272,10 @@ int fof_groups(tsp_context *ctx, int64_t n, const float *x, const float *y, cons
 int shrink_sphere_center(tsp_context *ctx, int64_t n, const float *x, const float *y, const float *z, const float *mass,
                          float mass_cut_factor, double r_start, double shrink_factor, int64_t min_particles, int max_iterations,
                          double center_out[3], tsp_center_info *info_out);
+// tsp_orient.hip: the moments of the particles inside a sphere (mass, centre of mass, angular momentum, second moments) of
+// caller-ordered host arrays; per-call DeviceScratch only, no context state
+int sphere_moments(tsp_context *ctx, int64_t n, const float *x, const float *y, const float *z, const float *mass, const float *vx,
+                   const float *vy, const float *vz, const double center[3], double r, double r_vel, tsp_moments *out);
 // tsp_surface.hip: the occlusion pass + resolve (keys in image64, (q, depth) in image), the rho order statistics and the
 // filter + shading; per-call memory is DeviceScratch
 int render_surface(tsp_context *ctx, const Camera &cam, float cut, const int64_t *h_starts, const int64_t *h_lens,

@@ -60,6 +60,9 @@ class AbstractDataLoader(ABC):
     def get_initial_center(self):
         return np.zeros(3, dtype=np.float32)
 
+    def get_initial_rotation(self):
+        return np.eye(3)
+
     def get_initial_view_width(self):
         period = self.get_periodicity_scale()
         return period / 2 if period is not None else config.DEFAULT_SCALE
@@ -345,6 +348,142 @@ def check_center_option(center, halos=None):
     return c.copy()
 
 
+ORIENTATIONS = ("faceon", "sideon")
+ORIENT_METHODS = ("angmom", "shape")
+VEL_RADIUS_FRACTION = 0.2        # vel_radius=None: radius / 5, the ratio of pynbody's defaults (1 kpc inside 5 kpc)
+_SIDEON_FROM_FACEON = np.array([[1.0, 0.0, 0.0], [0.0, 0.0, 1.0], [0.0, -1.0, 0.0]])
+
+
+def _positive_length(name, value):
+    if isinstance(value, (bool, str)):
+        raise ValueError(f"{name} must be a finite number > 0, not {value!r}")
+    try:
+        v = float(value)
+    except (TypeError, ValueError):
+        raise ValueError(f"{name} must be a finite number > 0, not {value!r}") from None
+    if not (np.isfinite(v) and v > 0):
+        raise ValueError(f"{name} must be a finite number > 0, not {value!r}")
+    return v
+
+
+def check_moments_arguments(center, radius, vel_radius, has_vel):
+    """The sphere of tsp_sphere_moments, checked on the host (the library would refuse it): returns (center float64 (3,), r,
+    r_vel); vel_radius=None is radius / 5 with velocities and 0 without.  Raises ValueError."""
+    try:
+        c = np.asarray(center, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError(f"center must be three finite coordinates, not {center!r}") from None
+    if c.shape != (3,) or not np.isfinite(c).all():
+        raise ValueError(f"center must be three finite coordinates, not {center!r}")
+    if radius is None:
+        raise ValueError("radius is required: the radius of the sphere whose particles are summed, a finite number > 0")
+    r = _positive_length("radius", radius)
+    if not has_vel:
+        if vel_radius is not None:
+            raise ValueError(f"vel_radius = {vel_radius!r} needs velocities (vel=)")
+        return c.copy(), r, 0.0
+    r_vel = VEL_RADIUS_FRACTION * r if vel_radius is None else _positive_length("vel_radius", vel_radius)
+    if not r_vel <= r:
+        raise ValueError(f"vel_radius = {vel_radius!r} must not exceed radius = {radius!r}")
+    return c.copy(), r, r_vel
+
+
+def check_moments_arrays(pos, mass, vel):
+    """float32 pos (n, 3), mass (n,) and vel (n, 3) or None, with at least one valid particle.  Raises ValueError."""
+    pos = np.asarray(pos, dtype=np.float32)
+    if pos.ndim != 2 or pos.shape[1] != 3:
+        raise ValueError(f"pos must have shape (n, 3), not {pos.shape}")
+    mass = np.asarray(mass, dtype=np.float32)
+    if mass.shape != (len(pos),):
+        raise ValueError(f"pos and mass must have the same length: mass has shape {mass.shape}, not ({len(pos)},)")
+    if vel is not None:
+        vel = np.asarray(vel, dtype=np.float32)
+        if vel.shape != pos.shape:
+            raise ValueError(f"vel must have the shape of pos, {pos.shape}, not {vel.shape}")
+    if len(pos) == 0:
+        raise ValueError("pos must have at least one particle")
+    with np.errstate(invalid="ignore"):
+        valid = np.isfinite(pos).all(axis=1) & np.isfinite(mass) & (mass > 0)
+        if vel is not None:
+            valid &= np.isfinite(vel).all(axis=1)
+    if not valid.any():
+        raise ValueError("no particle has finite coordinates" + (" and velocities" if vel is not None else "") +
+                         " and a finite mass > 0")
+    return pos, mass, vel
+
+
+def check_orient_arguments(orient, method, has_vel):
+    """orient "faceon" | "sideon"; method None | "angmom" | "shape" -> the method (None: "angmom" with velocities, else
+    "shape").  Raises ValueError."""
+    if orient not in ORIENTATIONS:
+        raise ValueError(f"orient must be one of {ORIENTATIONS}, not {orient!r}")
+    if method is None:
+        return "angmom" if has_vel else "shape"
+    if method not in ORIENT_METHODS:
+        raise ValueError(f"method must be None or one of {ORIENT_METHODS}, not {method!r}")
+    if method == "angmom" and not has_vel:
+        raise ValueError("method='angmom' needs velocities (vel=); without them use method='shape'")
+    return method
+
+
+def compute_moments(ctx, pos, mass, vel, center, r, r_vel):
+    """tsp_sphere_moments of checked arguments (check_moments_arrays, check_moments_arguments) on an existing context."""
+    return ctx.sphere_moments(pos[:, 0], pos[:, 1], pos[:, 2], mass, vel=None if vel is None else (vel[:, 0], vel[:, 1], vel[:, 2]),
+                              center=center, r=r, r_vel=r_vel)
+
+
+def orientation_axis(moments, method):
+    """The unit axis a disc is seen along: method "angmom": L / |L|; "shape": the minor axis of the second-moment tensor about
+    the centre of mass, its largest-magnitude component positive.  Raises ValueError where there is no such axis."""
+    if method == "angmom":
+        L = np.asarray(moments["L"], dtype=np.float64)
+        norm = float(np.sqrt((L * L).sum()))
+        if not norm > 1e-12 * float(moments["A"]):
+            raise ValueError(f"no net rotation inside the sphere: |L| = {norm!r} against sum m |d| |v| = {moments['A']!r} "
+                             f"(no velocities, or none that is ordered); method='shape' orients by the particles' distribution")
+        return L / norm
+    if method != "shape":
+        raise ValueError(f"method must be one of {ORIENT_METHODS}, not {method!r}")
+    xx, xy, xz, yy, yz, zz = (float(v) for v in moments["S"])
+    com = np.asarray(moments["com"], dtype=np.float64)
+    tensor = np.array([[xx, xy, xz], [xy, yy, yz], [xz, yz, zz]]) - float(moments["mass"]) * np.outer(com, com)
+    w, v = np.linalg.eigh(tensor)
+    if not abs(w[1] - w[0]) > 1e-6 * abs(w[1]):
+        raise ValueError(f"no unique minor axis inside the sphere: the second-moment tensor has eigenvalues {w.tolist()}")
+    a = v[:, 0]
+    return -a if a[np.argmax(np.abs(a))] < 0 else a
+
+
+def orientation_matrix(moments, orient, method, up=(0, 1, 0)):
+    """The (3, 3) float64 rotation that shows the axis of orientation_axis(moments, method) face-on (orient="faceon": the rows
+    are p1 = up x a normalised, p2 = a x p1 and a, so that R @ a = +z, toward the viewer -- pynbody's calc_faceon_matrix) or
+    side-on ("sideon": the axis up the screen, the disc along x).  |up x a| < 1e-6: (1, 0, 0) takes the place of up."""
+    if orient not in ORIENTATIONS:
+        raise ValueError(f"orient must be one of {ORIENTATIONS}, not {orient!r}")
+    a = orientation_axis(moments, method)
+    for up in (up, (1.0, 0.0, 0.0), (0.0, 1.0, 0.0)):       # (the last: a caller's up and the axis both along x)
+        p1 = np.cross(np.asarray(up, dtype=np.float64), a)
+        if np.sqrt((p1 * p1).sum()) >= 1e-6:
+            break
+    p1 = p1 / np.sqrt((p1 * p1).sum())
+    p2 = np.cross(a, p1)
+    faceon = np.stack([p1, p2, a])
+    return _SIDEON_FROM_FACEON @ faceon if orient == "sideon" else faceon
+
+
+def check_rotation_matrix(matrix):
+    """A (3, 3) float64 matrix whose rows are orthonormal to 1e-6.  Raises ValueError."""
+    try:
+        m = np.asarray(matrix, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError(f"a rotation must be a (3, 3) matrix, not {matrix!r}") from None
+    if m.shape != (3, 3) or not np.isfinite(m).all():
+        raise ValueError(f"a rotation must be a finite (3, 3) matrix, not shape {m.shape}")
+    if np.abs(m @ m.T - np.eye(3)).max() > 1e-6:
+        raise ValueError(f"the matrix is not orthonormal to 1e-6: R R^T - I reaches {np.abs(m @ m.T - np.eye(3)).max():.3g}")
+    return m.copy()
+
+
 class ArrayDataLoader(AbstractDataLoader):
     """Particles given as numpy arrays (e.g. pulled from a pynbody snapshot by the caller:
     snap['pos'], snap['smooth'], snap['mass'], ...; reference PynbodyDataInMemory, loader.py:79-154).
@@ -372,16 +511,41 @@ class ArrayDataLoader(AbstractDataLoader):
     largest halo; the reference's --center halo-N, loader.py:203-206) opens the view on the shrinking-sphere centre of the
     members of halo N (get_halo_center(N): in a periodic box the members are first unwrapped by nearest image around the
     lowest-index member, and the centre is in those coordinates).  Out of scope: periodic wrapping of the displacements inside the
-    shrinking sphere itself, and DeviceSyntheticLoader (no host arrays)."""
+    shrinking sphere itself, and DeviceSyntheticLoader (no host arrays).
+
+    vel, orient: the angle the view opens at.  vel is the (n, 3) velocities (kept on the host, permuted with the other arrays under
+    with_cells; not resident).  orient="faceon" / "sideon" turns the view so that the disc inside the sphere of radius
+    orient_radius around the initial centre (whatever center= produced) is seen face-on / edge-on: along the angular momentum about
+    the mean velocity of the inner fifth of that sphere (orient_method "angmom", the default with vel; pynbody.analysis.angmom),
+    or along the minor axis of the particles' second-moment tensor ("shape", the default without).  orient_radius is required:
+    no single length suits every snapshot.  get_initial_rotation() computes the matrix on the GPU (tsp_sphere_moments) on first
+    use, on the same context as 'rho', and caches it (orient_moments holds the moments); set_initial_rotation() restores it from
+    the caller's cache.  orientation() gives the matrix for any sphere.  Out of scope: periodic wrapping of the displacements."""
 
     # reference PynbodyDataInMemory.get_rgb_masses (loader.py:115-121): (band, weight) per rgb channel
     RGB_BANDS = (("I", 0.5), ("V", 1.0), ("U", 1.0))
 
     def __init__(self, device=None, pos=None, smooth=None, mass=None, quantities=None, rgb=None,
                  units="kpc", periodicity_scale=None, with_cells=False, band_magnitudes=None, n_smooth=None,
-                 center="none", halos=None):
+                 center="none", halos=None, vel=None, orient="none", orient_radius=None, orient_method=None):
         super().__init__(device)
         self._pos = np.asarray(pos, dtype=np.float32)
+        self._vel = None if vel is None else np.asarray(vel, dtype=np.float32)
+        if self._vel is not None and (self._pos.ndim != 2 or self._vel.shape != self._pos.shape or self._pos.shape[1] != 3):
+            raise ValueError(f"vel must have shape (n, 3) like pos, not {self._vel.shape} (pos: {self._pos.shape})")
+        self._orient_option = orient
+        self._orient_radius = self._orient_method = None
+        self._rotation = None            # the initial rotation once known (float64 (3, 3))
+        self.orient_moments = None       # what tsp_sphere_moments reported for it
+        if orient != "none":
+            self._orient_method = check_orient_arguments(orient, orient_method, self._vel is not None)
+            if orient_radius is None:
+                raise ValueError(f"orient={orient!r} needs orient_radius, the radius (in the units of pos) of the sphere around "
+                                 f"the centre whose particles define the disc: no single length suits every snapshot "
+                                 f"(pynbody's own default is a fixed 5 kpc)")
+            self._orient_radius = _positive_length("orient_radius", orient_radius)
+        elif orient_method is not None and orient_method not in ORIENT_METHODS:
+            raise ValueError(f"orient_method must be None or one of {ORIENT_METHODS}, not {orient_method!r}")
         self._halos_option = check_halos_option(halos, len(self._pos), periodicity_scale)
         self._halos = None               # the catalogue once known
         self._halo_centers = {}          # N -> centre of halo N (float64 (3,))
@@ -431,6 +595,8 @@ class ArrayDataLoader(AbstractDataLoader):
                 self._mags = {k: v[order] for k, v in self._mags.items()}
             if isinstance(self._halos_option, np.ndarray):
                 self._halos_option = self._halos_option[order]
+            if self._vel is not None:
+                self._vel = self._vel[order]
 
     def __len__(self):
         return len(self._pos)
@@ -582,6 +748,32 @@ class ArrayDataLoader(AbstractDataLoader):
         if isinstance(self._center_option, str) and self._center_option == "none":
             self._center_option = center.copy()
         self._center = center.copy()
+
+    def get_velocities(self):
+        """The (n, 3) float32 velocities in this loader's particle order, or None."""
+        return self._vel
+
+    def orientation(self, orient, radius, center=None, method=None, vel_radius=None, up=(0, 1, 0)):
+        """(matrix float64 (3, 3), moments dict): the rotation that shows the particles inside the sphere of `radius` around
+        `center` (None: the initial centre) face-on or side-on, from their moments found on the GPU (tsp_sphere_moments)."""
+        method = check_orient_arguments(orient, method, self._vel is not None)
+        center = self.get_initial_center() if center is None else center
+        c, r, r_vel = check_moments_arguments(center, radius, vel_radius, self._vel is not None)
+        pos, mass, vel = check_moments_arrays(self._pos, self._mass, self._vel)
+        moments = self._with_context(lambda ctx: compute_moments(ctx, pos, mass, vel, c, r, r_vel))
+        return orientation_matrix(moments, orient, method, up), moments
+
+    def get_initial_rotation(self):
+        if self._rotation is None:
+            if self._orient_option == "none":
+                return super().get_initial_rotation()
+            self._rotation, self.orient_moments = self.orientation(self._orient_option, self._orient_radius,
+                                                                   method=self._orient_method)
+        return self._rotation
+
+    def set_initial_rotation(self, matrix):
+        """The initial rotation (e.g. from the caller's cache, next to set_initial_center): it is then not computed."""
+        self._rotation = check_rotation_matrix(matrix)
 
     def get_quantity_label(self, quantity_name):
         return "density" if quantity_name is None else quantity_name

@@ -213,6 +213,10 @@ class MultiGpuContext:
         """The friends-of-friends groups of the whole (caller-ordered) snapshot, on the first context like smoothing_lengths."""
         return self.contexts[0].fof_groups(x, y, z, linking_length, period, min_members)
 
+    def sphere_moments(self, x, y, z, mass, **kwargs):
+        """The moments inside a sphere of the whole (caller-ordered) snapshot, on the first context like smoothing_lengths."""
+        return self.contexts[0].sphere_moments(x, y, z, mass, **kwargs)
+
     def generate_synthetic(self, n_total, first=0, count=None, seed=1337, h_cap=0.0, with_quantity=False, with_rgb=False):
         count = n_total - first if count is None else count
         # the generator's index bijection makes every index range a uniform sample: contiguous shards are balanced

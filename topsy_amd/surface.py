@@ -127,6 +127,10 @@ class SurfaceView(FrameInterface):
         """The visualizer's centre_on_pixel: (row, col) index the shared R x R image; the camera is the visualizer's."""
         return self._vis.centre_on_pixel(row, col)
 
+    def orient(self, orient, radius, center=None, method=None):
+        """The visualizer's orient: the camera is the visualizer's."""
+        return self._vis.orient(orient, radius, center=center, method=method)
+
     def centre_on_halo(self, n):
         """The visualizer's centre_on_halo: the camera is the visualizer's."""
         return self._vis.centre_on_halo(n)

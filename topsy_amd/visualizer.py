@@ -144,9 +144,9 @@ class VisualizerBase(FrameInterface):
         self.rotation_matrix = self._x_rotation_matrix(x_angle) @ self._y_rotation_matrix(y_angle) @ self.rotation_matrix
 
     def reset_view(self, rotation_matrix=None, position_offset=None, scale=None):
-        self._sph.rotation_matrix = np.eye(3) if rotation_matrix is None else rotation_matrix
         self._sph.scale = self.data_loader.get_initial_view_width() if scale is None else scale
         self._sph.position_offset = -self.data_loader.get_initial_center() if position_offset is None else position_offset
+        self._sph.rotation_matrix = self.data_loader.get_initial_rotation() if rotation_matrix is None else rotation_matrix
 
     @property
     def colormap(self):
@@ -301,6 +301,22 @@ class VisualizerBase(FrameInterface):
             raise ValueError(f"{type(self.data_loader).__name__} has no halo catalogue")
         self.position_offset = -np.asarray(self.data_loader.get_halo_center(n), dtype=np.float64)
         return self.position_offset
+
+    def orient(self, orient, radius, center=None, method=None):
+        """Turn the view so that the disc inside the sphere of `radius` around `center` is seen face-on (orient="faceon") or
+        edge-on ("sideon", its axis up the screen): pynbody.analysis.angmom.faceon / sideon for an array snapshot, without moving
+        a particle.  center=None is -position_offset, what the view is centred on (after centre_on_pixel or centre_on_halo: what
+        was just centred).  method: "angmom" (the angular momentum about the mean velocity of the inner fifth of the sphere; the
+        default with from_arrays(vel=...)) or "shape" (the minor axis of the second-moment tensor; the default without).  The
+        moments are found on the GPU from the loader's host arrays (tsp_sphere_moments).  Returns the new rotation_matrix."""
+        if not isinstance(self.data_loader, loader.ArrayDataLoader):
+            raise ValueError(f"{type(self.data_loader).__name__} keeps no host arrays to orient by: orient() needs from_arrays / "
+                             f"ArrayDataLoader")
+        if center is None:
+            center = -np.asarray(self.position_offset, dtype=np.float64)
+        matrix, self.orient_moments = self.data_loader.orientation(orient, radius, center=center, method=method)
+        self.rotation_matrix = matrix
+        return matrix
 
     def save(self, filename="output.npy"):
         self._sph.render(DrawReason.EXPORT)
