@@ -90,7 +90,9 @@ const char *tsp_last_error(void);
  * 114: new entry point tsp_fof_groups and the struct tsp_fof_info (friends-of-friends groups: a halo catalogue for arrays);
  * nothing else changed.
  * 115: new entry point tsp_sphere_moments and the struct tsp_moments (the moments of the particles inside a sphere: what a
- * face-on or side-on orientation is taken from); nothing else changed. */
+ * face-on or side-on orientation is taken from); nothing else changed.
+ * 116: new entry point tsp_radial_profile and the structs tsp_profile_spec / tsp_profile_info (binned shell and annulus sums: radial
+ * profiles, the virial radius); nothing else changed. */
 int tsp_version(void);
 int tsp_stats_size(void);
 
@@ -383,6 +385,69 @@ typedef struct {
 int tsp_sphere_moments(tsp_context *ctx, int64_t n, const float *x, const float *y, const float *z, const float *mass,
                        const float *vx, const float *vy, const float *vz,      /* all three or none (NULL) */
                        const double center[3], double r, double r_vel, tsp_moments *out);
+
+/* Radial profiles: per radial bin the count and eleven sums of the particles in it, in spherical shells or in the cylindrical
+ * annuli of a disc -- what pynbody.analysis.profile.Profile (density, rotation curve, dispersions, specific angular momentum) and
+ * pynbody.analysis.halo.virial_radius are built from.  Host arrays in, caller's order; uses ctx's device and stream only: resident
+ * particles, image, accumulator and tsp_stats unchanged.  Float64 throughout (no fused multiply-adds), every expression in the
+ * order written here:
+ *   - Velocities.  vx, vy, vz are all given or all NULL.
+ *   - Valid particles.  As tsp_sphere_moments: particle i is valid iff x[i], y[i], z[i], mass[i] (and vx[i], vy[i], vz[i] when
+ *     given) are finite and mass[i] > 0.  m = (double)mass[i].  n_valid counts them, binned or not.
+ *   - Displacements.  dx = (double)x[i] - center[0] (dy, dz alike), d = (dx, dy, dz), formed in float64 before anything is
+ *     multiplied.  With F = frame (row-major, F[3 * r + c]):
+ *       x' = (F[0] * dx + F[1] * dy) + F[2] * dz, y' = (F[3] * dx + F[4] * dy) + F[5] * dz, z' = (F[6] * dx + F[7] * dy) + F[8] * dz.
+ *     With velocities u = ((double)vx[i] - v_cen[0], ...) and u' = F u formed in the same way (ux', uy', uz').
+ *   - Bin coordinate.  R2 = x' * x' + y' * y'.  Geometry 0 (shells): s2 = (dx * dx + dy * dy) + dz * dz, from the unrotated d, so
+ *     that membership does not depend on the frame.  Geometry 1 (annuli about the frame's third axis): s2 = R2, and the particle
+ *     takes part only if fabs(z') <= half_height.
+ *   - Bin.  E2[k] = edges[k] * edges[k], k = 0 .. n_bins.  A valid particle (geometry 1: that takes part) is in bin k iff
+ *     E2[k] <= s2 < E2[k + 1]; with s2 < E2[0] it is counted in n_inner and its m in mass_inner; with s2 >= E2[n_bins] it is
+ *     counted nowhere.  count_out[k] = the members of bin k; n_binned = their total.
+ *   - Sums.  sums_out[k * 11 + j] over the members of bin k, each starting at +0.0, with s = sqrt(s2):
+ *       j = 0: sum m;  j = 1: sum m * s;
+ *       j = 2, 3, 4: sum m * c_0, m * c_1, m * c_2;  j = 5, 6, 7: sum (m * c_0) * c_0, (m * c_1) * c_1, (m * c_2) * c_2;
+ *       j = 8, 9, 10: sum m * (dy * uz - dz * uy), m * (dz * ux - dx * uz), m * (dx * uy - dy * ux): the angular momentum about
+ *       center and v_cen in the caller's frame, formed as L of tsp_sphere_moments.
+ *     Without velocities j = 2 .. 10 are +0.0.
+ *   - Components c.  R = sqrt(R2);  eRx = x' / R and eRy = y' / R if R > 0, else eRx = 1 and eRy = 0 (so e_R = (eRx, eRy, 0) and
+ *     e_phi = (-eRy, eRx, 0), on the axis (1, 0, 0) and (0, 1, 0)).
+ *       c_1 = eRx * uy' - eRy * ux'                                             (u_phi, both geometries)
+ *       Geometry 1, the cylindrical triad (u_R, u_phi, u_z):  c_0 = eRx * ux' + eRy * uy',  c_2 = uz'.
+ *       Geometry 0, the spherical triad (u_r, u_phi, u_theta):  D = sqrt(R2 + z' * z');  erx = x' / D, ery = y' / D, erz = z' / D if
+ *       D > 0, else (0, 0, 1);  c_0 = (erx * ux' + ery * uy') + erz * uz';  with e_theta = e_phi x e_r,
+ *       c_2 = ((eRx * erz) * ux' + (eRy * erz) * uy') - (eRx * erx + eRy * ery) * uz'.
+ *   - Determinism.  No floating-point atomics; the order of every sum is free but fixed (per-wave sums are added to a workgroup's
+ *     table in wave order, the workgroups' tables in index order; the grid is a function of n, n_bins and the device): the same
+ *     call on the same input and device returns the same bits.  Counts are integers.
+ * 1 <= n < 2^31; no NULL among x, y, z, mass, spec, spec->edges, count_out, sums_out (info_out is optional); geometry 0 or 1;
+ * 1 <= n_bins <= 512; the n_bins + 1 edges finite, edges[0] >= 0, strictly ascending; center finite; with velocities v_cen finite;
+ * the rows of frame orthonormal to 1e-6 (|row_i . row_j - delta_ij| <= 1e-6); geometry 1: half_height > 0 or +inf; at least one
+ * valid particle; anything else returns TSP_EINVAL and writes nothing.  A profile without a member is no error: zeros.  Not
+ * provided: periodic wrapping of the displacements.  Device memory is allocated for the call only (about 16 bytes per particle, 28
+ * with velocities, and at most 53 KB per workgroup of partial tables, 27 MB in all); a failed allocation returns TSP_ENOMEM and
+ * writes nothing.  The cost is one pass over those bytes, less the blocks of 1024 consecutive particles whose bounding box lies at
+ * a squared distance (formed as in tsp_sphere_moments) >= E2[n_bins] (geometry 0) or, with a finite half_height,
+ * >= (E2[n_bins] + half_height * half_height) * (1 + 1e-5) (geometry 1: the sphere around the cylinder, widened by what the
+ * frame's tolerance and rounding allow) from center: those are not read (identical results).  The pass is fast where a wave's 64
+ * consecutive particles fall into a few bins (a spatial order of the arrays) and slow, not wrong, where they fall into many. */
+typedef struct {
+    int32_t geometry;        /* 0: spherical shells, 1: cylindrical annuli about the frame's third axis */
+    int32_t n_bins;          /* 1 .. 512 */
+    const double *edges;     /* n_bins + 1 radii, finite, edges[0] >= 0, strictly ascending */
+    double center[3];
+    double v_cen[3];         /* subtracted from the velocities; ignored without velocities */
+    double frame[9];         /* row-major rotation: d' = frame * d, u' = frame * u (what topsy_amd.orientation returns) */
+    double half_height;      /* geometry 1: members have |z'| <= half_height; > 0 or +inf.  geometry 0: ignored */
+} tsp_profile_spec;
+typedef struct {
+    int64_t n_valid, n_inner, n_binned;        /* valid particles; those inside edges[0]; those in a bin */
+    double  mass_inner;                        /* sum m inside edges[0] */
+} tsp_profile_info;
+int tsp_radial_profile(tsp_context *ctx, int64_t n, const float *x, const float *y, const float *z, const float *mass,
+                       const float *vx, const float *vy, const float *vz,      /* all three or none (NULL) */
+                       const tsp_profile_spec *spec, int64_t *count_out /* n_bins */, double *sums_out /* n_bins * 11 */,
+                       tsp_profile_info *info_out);
 
 /* Surface rendering: DepthSPHWithOcclusion + ColorAsSurfaceMap (reference src/topsy/sph.py:448-656, shaders/sph.wgsl:94-122,
  * 149-158, shaders/smooth.wgsl, shaders/surface.wgsl, colormap/surface.py).  Float32 throughout, operations in the order written.

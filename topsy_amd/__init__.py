@@ -51,7 +51,11 @@ def from_arrays(pos, smooth, mass, quantities=None, rgb=None, with_cells=False, 
     axis as the angular momentum about the mean velocity of the inner fifth of the sphere (orient_method="angmom", the default
     with vel); without it the axis is the minor axis of the particles' second-moment tensor ("shape").  The moments are found on
     the GPU (sphere_moments); vis.data_loader.get_initial_rotation() returns the matrix, set_initial_rotation() restores it,
-    and vis.orient("faceon" | "sideon", radius) re-orients on whatever the view is centred on."""
+    and vis.orient("faceon" | "sideon", radius) re-orients on whatever the view is centred on.
+
+    vis.profile(r_max, ...) is the radial profile (radial_profile) of what the view shows -- about the view's centre, in the
+    view's frame: after orient("faceon"), geometry="disc" gives the rotation curve -- and vis.scale_to_virial(rho_threshold,
+    r_max) sets the view's scale to the virial radius (virial_radius) of what it is centred on."""
     from . import visualizer, loader
     return visualizer.Visualizer(data_loader_class=loader.ArrayDataLoader,
                                  data_loader_kwargs={"pos": pos, "smooth": smooth, "mass": mass,
@@ -200,6 +204,49 @@ def orientation(pos, mass, vel=None, center=(0, 0, 0), radius=None, vel_radius=N
     return loader.orientation_matrix(moments, orient, method, up), moments
 
 
+def radial_profile(pos, mass, vel=None, center=(0, 0, 0), r_max=None, r_min=0.0, n_bins=100, bins="lin", geometry="sphere",
+                   frame=None, half_height=None, v_cen=None, G=None, device_id=0):
+    """The radial profile of the particles of an (n, 3) position array about `center`, on GPU `device_id` (C: tsp_radial_profile),
+    as a Profile (topsy_amd/loader.py): pynbody.analysis.profile.Profile for arrays.  geometry="sphere": spherical shells, with
+    the velocity components (v_r, v_phi, v_theta); "disc": cylindrical annuli about the third axis of `frame` (None: the identity;
+    the matrix of topsy_amd.orientation(..., orient="faceon") puts the disc's axis there), members within |z'| <= half_height
+    (None: any height), with (v_R, v_phi, v_z): v_phi is the rotation curve.  The bins: bins="lin" or "log" (needs r_min > 0)
+    makes n_bins (1 to 512) bins between r_min and r_max (required), or bins = your own ascending edges.  With vel (n, 3) the
+    velocities are taken about v_cen (None: the mean velocity of the inner fifth of the sphere of the outermost edge, as
+    sphere_moments and orientation take it).  G: the gravitational constant in the caller's units, for Profile.v_circ.  Float64
+    sums of displacements formed in float64; the same call returns the same bits.  Particles with a non-finite coordinate or
+    velocity or a mass that is not finite and > 0 take no part.  Out of scope: periodic wrapping of the displacements."""
+    from . import _native, loader
+    pos, mass, vel = loader.check_moments_arrays(pos, mass, vel)
+    edges = loader.profile_edges(bins, n_bins, r_min, r_max)
+    kwargs, G = loader.check_profile_arguments(center, edges, geometry, frame, half_height, v_cen, G, vel is not None)
+    ctx = _native.Context(1, 2, device_id)
+    try:
+        return loader.compute_profile(ctx, pos, mass, vel, kwargs, G)
+    finally:
+        ctx.close()
+
+
+def virial_radius(pos, mass, center, rho_threshold, r_max, refinements=3, device_id=0):
+    """The radius about `center` inside which the mean density is rho_threshold (pynbody.analysis.halo.virial_radius for arrays;
+    rho_threshold is e.g. 200 times the critical density in the caller's units), on GPU `device_id` (C: tsp_radial_profile).
+    The rule: with M(<r) the mass of the valid particles at a distance below r, the mean enclosed density is
+    rho(r) = 3 M(<r) / (4 pi r^3).  Level 0 evaluates it at the 257 edges of 256 logarithmic bins on [r_max / 1024, r_max] and takes
+    the first bin, going outward, at whose inner edge rho >= rho_threshold and at whose outer edge rho < rho_threshold: where
+    the density first falls below the threshold on the way out from where it was above.  That bin is re-binned `refinements`
+    times into 256 linear bins (the mass below the bracket comes with each call), each time keeping the bin that ends at the
+    first edge with rho < rho_threshold.  The result is the linear interpolation of rho across the last bracket to
+    rho_threshold.  Raises ValueError if level 0 finds no such bin (the threshold is never crossed downward inside r_max)."""
+    from . import _native, loader
+    pos, mass, _ = loader.check_moments_arrays(pos, mass, None)
+    c, rho_threshold, r_max, refinements = loader.check_virial_arguments(center, rho_threshold, r_max, refinements)
+    ctx = _native.Context(1, 2, device_id)
+    try:
+        return loader.compute_virial_radius(ctx, pos, mass, c, rho_threshold, r_max, refinements)[0]
+    finally:
+        ctx.close()
+
+
 def friends_of_friends(pos, linking_length=None, b=0.2, min_members=20, periodicity_scale=None, device_id=0):
     """Friends-of-friends groups of an (n, 3) position array on GPU `device_id` (C: tsp_fof_groups): particles closer than
     linking_length are friends (nearest image in a periodic box of side periodicity_scale), the groups are the connected
@@ -228,11 +275,14 @@ def SurfaceView(visualizer, **colormap_params):
 
 
 def __getattr__(name):
-    """topsy_amd.VisualizationRecorder (movie recording and export, topsy_amd/recorder) and topsy_amd.FofCatalogue
-    (topsy_amd/loader.py), imported on first use."""
+    """topsy_amd.VisualizationRecorder (movie recording and export, topsy_amd/recorder), topsy_amd.FofCatalogue and
+    topsy_amd.Profile (topsy_amd/loader.py), imported on first use."""
     if name == "FofCatalogue":
         from .loader import FofCatalogue
         return FofCatalogue
+    if name == "Profile":
+        from .loader import Profile
+        return Profile
     if name == "VisualizationRecorder":
         from .recorder import VisualizationRecorder
         return VisualizationRecorder

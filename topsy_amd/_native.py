@@ -17,8 +17,8 @@ PIPE_DEFAULT, PIPE_GENERIC = 0, 1
 SAMPLE_BILINEAR_MIP0, SAMPLE_BILINEAR_MIP = 0x10, 0x20      # diagnostic sampling rules (generic kernel)
 UNIQUE_ID_BYTES = 128
 ABI_VERSION = 112            # the oldest tsp_version() whose structs this binding matches; entry points added since
-                             # (113: tsp_shrink_sphere_center, 114: tsp_fof_groups, 115: tsp_sphere_moments) are required by
-                             # name in load_library()
+                             # (113: tsp_shrink_sphere_center, 114: tsp_fof_groups, 115: tsp_sphere_moments,
+                             # 116: tsp_radial_profile) are required by name in load_library()
 PRESENT_SCALAR, PRESENT_BIVARIATE, PRESENT_RGB, PRESENT_RGB_HDR = 0, 1, 2, 3
 LAYER_QUAD, LAYER_LINES = 0, 1
 
@@ -73,6 +73,22 @@ class Moments(ctypes.Structure):
             v = getattr(self, name)
             out[name] = int(v) if kind is ctypes.c_int64 else float(v) if kind is ctypes.c_double else np.array(v, dtype=np.float64)
         return out
+
+
+class ProfileSpec(ctypes.Structure):
+    """struct tsp_profile_spec."""
+    _fields_ = [("geometry", ctypes.c_int32), ("n_bins", ctypes.c_int32), ("edges", ctypes.POINTER(ctypes.c_double)),
+                ("center", ctypes.c_double * 3), ("v_cen", ctypes.c_double * 3), ("frame", ctypes.c_double * 9),
+                ("half_height", ctypes.c_double)]
+
+
+class ProfileInfo(ctypes.Structure):
+    """struct tsp_profile_info."""
+    _fields_ = [("n_valid", ctypes.c_int64), ("n_inner", ctypes.c_int64), ("n_binned", ctypes.c_int64),
+                ("mass_inner", ctypes.c_double)]
+
+
+PROFILE_SUMS = 11            # doubles per bin of tsp_radial_profile's sums_out: mass, ms, mc (3), mc2 (3), mj (3)
 
 
 class BackendUnavailable(RuntimeError):
@@ -147,6 +163,8 @@ SIGNATURES = {
                                       ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(FofInfo)]),
     "tsp_sphere_moments": (ctypes.c_int, [_ctx, ctypes.c_int64, _fp, _fp, _fp, _fp, _fp, _fp, _fp, ctypes.POINTER(ctypes.c_double),
                                           ctypes.c_double, ctypes.c_double, ctypes.POINTER(Moments)]),
+    "tsp_radial_profile": (ctypes.c_int, [_ctx, ctypes.c_int64, _fp, _fp, _fp, _fp, _fp, _fp, _fp, ctypes.POINTER(ProfileSpec), _i64p,
+                                          ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ProfileInfo)]),
     "tsp_set_sphere_mips": (ctypes.c_int, [_ctx, _fp, ctypes.c_int, ctypes.c_int]),
     "tsp_density_order_stats": (ctypes.c_int, [_ctx, _i64p, ctypes.c_int, _fp]),
     "tsp_render_surface": (ctypes.c_int, [_ctx, _fp, ctypes.c_float, ctypes.c_float, _i64p, _i64p, ctypes.c_int, ctypes.c_int,
@@ -478,6 +496,42 @@ class Context:
                                             center.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), float(r), float(r_vel),
                                             ctypes.byref(out)))
         return out.as_dict()
+
+    def radial_profile(self, x, y, z, mass, vel=None, edges=(0.0, 1.0), geometry=0, center=(0.0, 0.0, 0.0), v_cen=(0.0, 0.0, 0.0),
+                       frame=None, half_height=np.inf):
+        """Binned sums of the caller-ordered float32 particles (tsp_radial_profile) in the spherical shells (geometry 0) or the
+        cylindrical annuli about the third axis of `frame` with |z'| <= half_height (geometry 1) between the ascending radii
+        `edges` around center; with vel = (vx, vy, vz) the velocity sums are taken about v_cen.  frame=None is the identity.
+        Returns a dict: count int64 (n_bins,), sums float64 (n_bins, 11) (mass, ms, mc (3), mc2 (3), mj (3): the header's order),
+        n_valid, n_inner, n_binned, mass_inner.  Uses this context's device only; what is resident stays."""
+        n = len(x)
+        x, y, z, mass = _f32(x, n, "x"), _f32(y, n, "y"), _f32(z, n, "z"), _f32(mass, n, "mass")
+        if vel is not None:
+            if len(vel) != 3:
+                raise ValueError("vel must be the three arrays (vx, vy, vz)")
+            vel = [_f32(v, n, name) for v, name in zip(vel, ("vx", "vy", "vz"))]
+        vx, vy, vz = vel if vel is not None else (None, None, None)
+        edges = np.ascontiguousarray(edges, dtype=np.float64)
+        if edges.ndim != 1 or len(edges) < 2:
+            raise ValueError(f"edges must be at least two radii, not shape {edges.shape}")
+        spec = ProfileSpec()
+        spec.geometry, spec.n_bins = int(geometry), len(edges) - 1
+        spec.edges = edges.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
+        for name, value, shape in (("center", center, (3,)), ("v_cen", v_cen, (3,)),
+                                   ("frame", np.eye(3) if frame is None else frame, (3, 3))):
+            value = np.ascontiguousarray(value, dtype=np.float64)
+            if value.shape != shape:
+                raise ValueError(f"{name} must have shape {shape}, not {value.shape}")
+            getattr(spec, name)[:] = value.ravel().tolist()
+        spec.half_height = float(half_height)
+        count = np.zeros(spec.n_bins, dtype=np.int64)
+        sums = np.zeros((spec.n_bins, PROFILE_SUMS), dtype=np.float64)
+        info = ProfileInfo()
+        _check(self._lib.tsp_radial_profile(self._h, n, _ptr(x), _ptr(y), _ptr(z), _ptr(mass), _ptr(vx), _ptr(vy), _ptr(vz),
+                                            ctypes.byref(spec), count.ctypes.data_as(_i64p),
+                                            sums.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), ctypes.byref(info)))
+        return {"count": count, "sums": sums, "n_valid": int(info.n_valid), "n_inner": int(info.n_inner),
+                "n_binned": int(info.n_binned), "mass_inner": float(info.mass_inner)}
 
     # ---- surface (include/topsy_splat.h "Surface rendering") ---------------------------------
     def set_sphere_mips(self, mips, n0=64, n_levels=4):

@@ -203,7 +203,7 @@ using namespace tsp;
 extern "C" {
 
 const char *tsp_last_error(void) { return g_err; }
-int tsp_version(void) { return 115; }     // 115: tsp_sphere_moments; 114: tsp_fof_groups; 113: tsp_shrink_sphere_center; 112: tsp_present_surface, tsp_present_surface_yuv420; 111: tsp_content_neg_inf; 110: tsp_sph_sum; 109: tsp_present_yuv420; 108: tsp_present; 107: surface rendering; 106: tsp_smoothing_lengths; 101: tsp_stats gained ms_mega, n_mega (16 bytes); 102: the per-kernel fragment counts (32 bytes); 103: n_chunk_culled (8 bytes); 104: matrix-core / kernel-I options removed; 105: kernel M's options removed (kernel G draws the mid footprints)
+int tsp_version(void) { return 116; }     // 116: tsp_radial_profile; 115: tsp_sphere_moments; 114: tsp_fof_groups; 113: tsp_shrink_sphere_center; 112: tsp_present_surface, tsp_present_surface_yuv420; 111: tsp_content_neg_inf; 110: tsp_sph_sum; 109: tsp_present_yuv420; 108: tsp_present; 107: surface rendering; 106: tsp_smoothing_lengths; 101: tsp_stats gained ms_mega, n_mega (16 bytes); 102: the per-kernel fragment counts (32 bytes); 103: n_chunk_culled (8 bytes); 104: matrix-core / kernel-I options removed; 105: kernel M's options removed (kernel G draws the mid footprints)
 int tsp_stats_size(void) { return (int)sizeof(tsp_stats); }
 
 int tsp_device_count(void) {
@@ -828,6 +828,39 @@ int tsp_sphere_moments(tsp_context *ctx, int64_t n, const float *x, const float 
         TSP_REQUIRE(r_vel == 0.0, TSP_EINVAL, "without velocities r_vel must be 0, not %g", r_vel);
     TSP_HIP(hipSetDevice(ctx->device));
     return sphere_moments(ctx, n, x, y, z, mass, vx, vy, vz, center, r, r_vel == 0.0 ? 0.0 : r_vel, out);
+}
+
+int tsp_radial_profile(tsp_context *ctx, int64_t n, const float *x, const float *y, const float *z, const float *mass,
+                       const float *vx, const float *vy, const float *vz, const tsp_profile_spec *spec, int64_t *count_out,
+                       double *sums_out, tsp_profile_info *info_out) {
+    TSP_REQUIRE(ctx && x && y && z && mass && spec && count_out && sums_out, TSP_EINVAL, "NULL argument");
+    TSP_REQUIRE((vx && vy && vz) || (!vx && !vy && !vz), TSP_EINVAL, "vx, vy and vz must be given together or not at all");
+    TSP_REQUIRE(n >= 1 && n < (1ll << 31), TSP_EINVAL, "n = %lld outside [1, 2^31)", (long long)n);
+    TSP_REQUIRE(spec->geometry == 0 || spec->geometry == 1, TSP_EINVAL, "geometry = %d is neither 0 (shells) nor 1 (annuli)",
+                (int)spec->geometry);
+    TSP_REQUIRE(spec->n_bins >= 1 && spec->n_bins <= 512, TSP_EINVAL, "n_bins = %d outside [1, 512]", (int)spec->n_bins);
+    TSP_REQUIRE(spec->edges, TSP_EINVAL, "NULL edges");
+    TSP_REQUIRE(std::isfinite(spec->edges[0]) && spec->edges[0] >= 0.0, TSP_EINVAL, "edges[0] must be finite and >= 0, not %g",
+                spec->edges[0]);
+    for (int k = 1; k <= spec->n_bins; ++k)
+        TSP_REQUIRE(std::isfinite(spec->edges[k]) && spec->edges[k] > spec->edges[k - 1], TSP_EINVAL,
+                    "edges must be finite and strictly ascending: edges[%d] = %g after %g", k, spec->edges[k], spec->edges[k - 1]);
+    TSP_REQUIRE(std::isfinite(spec->center[0]) && std::isfinite(spec->center[1]) && std::isfinite(spec->center[2]), TSP_EINVAL,
+                "center = (%g, %g, %g) is not finite", spec->center[0], spec->center[1], spec->center[2]);
+    if (vx)
+        TSP_REQUIRE(std::isfinite(spec->v_cen[0]) && std::isfinite(spec->v_cen[1]) && std::isfinite(spec->v_cen[2]), TSP_EINVAL,
+                    "v_cen = (%g, %g, %g) is not finite", spec->v_cen[0], spec->v_cen[1], spec->v_cen[2]);
+    for (int i = 0; i < 3; ++i)
+        for (int j = i; j < 3; ++j) {
+            const double *a = spec->frame + 3 * i, *b = spec->frame + 3 * j;
+            const double dot = a[0] * b[0] + a[1] * b[1] + a[2] * b[2];
+            TSP_REQUIRE(std::fabs(dot - (i == j ? 1.0 : 0.0)) <= 1e-6, TSP_EINVAL,
+                        "frame is not a rotation: rows %d and %d have the product %g", i, j, dot);      // (NaN fails too)
+        }
+    if (spec->geometry == 1)
+        TSP_REQUIRE(spec->half_height > 0.0, TSP_EINVAL, "half_height must be > 0 or +inf, not %g", spec->half_height);
+    TSP_HIP(hipSetDevice(ctx->device));
+    return radial_profile(ctx, n, x, y, z, mass, vx, vy, vz, spec, count_out, sums_out, info_out);
 }
 
 int tsp_present(tsp_context *ctx, int width, int height, const tsp_present_base *base, const tsp_present_layer *layers,

@@ -276,6 +276,11 @@ int shrink_sphere_center(tsp_context *ctx, int64_t n, const float *x, const floa
 // caller-ordered host arrays; per-call DeviceScratch only, no context state
 int sphere_moments(tsp_context *ctx, int64_t n, const float *x, const float *y, const float *z, const float *mass, const float *vx,
                    const float *vy, const float *vz, const double center[3], double r, double r_vel, tsp_moments *out);
+// tsp_profile.hip: binned shell / annulus sums of caller-ordered host arrays (radial profiles); per-call DeviceScratch only, no
+// context state
+int radial_profile(tsp_context *ctx, int64_t n, const float *x, const float *y, const float *z, const float *mass, const float *vx,
+                   const float *vy, const float *vz, const tsp_profile_spec *spec, int64_t *count_out, double *sums_out,
+                   tsp_profile_info *info_out);
 // tsp_surface.hip: the occlusion pass + resolve (keys in image64, (q, depth) in image), the rho order statistics and the
 // filter + shading; per-call memory is DeviceScratch
 int render_surface(tsp_context *ctx, const Camera &cam, float cut, const int64_t *h_starts, const int64_t *h_lens,

@@ -484,6 +484,208 @@ def check_rotation_matrix(matrix):
     return m.copy()
 
 
+PROFILE_GEOMETRIES = ("sphere", "disc")
+PROFILE_MAX_BINS = 512           # tsp_radial_profile's limit
+VIRIAL_BINS = 256                # bins per level of virial_radius
+VIRIAL_LOG_SPAN = 1024.0         # level 0 of virial_radius spans [r_max / 1024, r_max]
+
+
+def profile_edges(bins="lin", n_bins=100, r_min=0.0, r_max=None):
+    """The bin edges of a profile, float64 (n_bins + 1,): bins="lin": r_min + (r_max - r_min) * k / n_bins; "log" (needs
+    r_min > 0): r_min * (r_max / r_min) ** (k / n_bins); both with the end points exact; or the caller's own ascending radii
+    (then n_bins, r_min and r_max are not used).  Raises ValueError."""
+    if not isinstance(bins, str):
+        try:
+            edges = np.array(bins, dtype=np.float64)
+        except (TypeError, ValueError):
+            raise ValueError(f"bins must be 'lin', 'log' or an ascending array of radii, not {bins!r}") from None
+        if edges.ndim != 1 or not 2 <= len(edges) <= PROFILE_MAX_BINS + 1:
+            raise ValueError(f"explicit bin edges must be 2 to {PROFILE_MAX_BINS + 1} radii, not shape {edges.shape}")
+        if not np.isfinite(edges).all() or edges[0] < 0 or not (np.diff(edges) > 0).all():
+            raise ValueError("explicit bin edges must be finite, >= 0 and strictly ascending")
+        return edges
+    if bins not in ("lin", "log"):
+        raise ValueError(f"bins must be 'lin', 'log' or an ascending array of radii, not {bins!r}")
+    if isinstance(n_bins, bool) or not isinstance(n_bins, (int, np.integer)) or not 1 <= n_bins <= PROFILE_MAX_BINS:
+        raise ValueError(f"n_bins must be an integer from 1 to {PROFILE_MAX_BINS}, not {n_bins!r}")
+    if r_max is None:
+        raise ValueError("r_max is required: the outer radius of the profile, a finite number > 0")
+    r_max = _positive_length("r_max", r_max)
+    if isinstance(r_min, (bool, str)):
+        raise ValueError(f"r_min must be a finite number >= 0 below r_max, not {r_min!r}")
+    try:
+        r_min = float(r_min)
+    except (TypeError, ValueError):
+        raise ValueError(f"r_min must be a finite number >= 0 below r_max, not {r_min!r}") from None
+    if not (np.isfinite(r_min) and 0 <= r_min < r_max):
+        raise ValueError(f"r_min must be a finite number >= 0 below r_max = {r_max!r}, not {r_min!r}")
+    k = np.arange(n_bins + 1, dtype=np.float64) / n_bins
+    if bins == "log":
+        if not r_min > 0:
+            raise ValueError("bins='log' needs r_min > 0")
+        edges = r_min * (r_max / r_min) ** k
+    else:
+        edges = r_min + (r_max - r_min) * k
+    edges[0], edges[-1] = r_min, r_max
+    if not (np.diff(edges) > 0).all():
+        raise ValueError(f"{n_bins} {bins} bins between {r_min!r} and {r_max!r} are not distinct in float64")
+    return edges
+
+
+def check_profile_arguments(center, edges, geometry, frame, half_height, v_cen, G, has_vel):
+    """The arguments of a profile besides its edges, checked on the host (the library would refuse them): returns the keyword
+    arguments of Context.radial_profile without vel (v_cen None where it is to be taken from the inner fifth) and G.  Raises
+    ValueError."""
+    try:
+        c = np.asarray(center, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError(f"center must be three finite coordinates, not {center!r}") from None
+    if c.shape != (3,) or not np.isfinite(c).all():
+        raise ValueError(f"center must be three finite coordinates, not {center!r}")
+    if geometry not in PROFILE_GEOMETRIES:
+        raise ValueError(f"geometry must be one of {PROFILE_GEOMETRIES}, not {geometry!r}")
+    frame = np.eye(3) if frame is None else check_rotation_matrix(frame)
+    if half_height is None:
+        hh = np.inf
+    else:
+        if geometry != "disc":
+            raise ValueError(f"half_height = {half_height!r} needs geometry='disc'")
+        if isinstance(half_height, (bool, str)):
+            raise ValueError(f"half_height must be None or a number > 0, not {half_height!r}")
+        try:
+            hh = float(half_height)
+        except (TypeError, ValueError):
+            raise ValueError(f"half_height must be None or a number > 0, not {half_height!r}") from None
+        if not hh > 0:
+            raise ValueError(f"half_height must be None or a number > 0, not {half_height!r}")
+    if v_cen is not None:
+        if not has_vel:
+            raise ValueError(f"v_cen = {v_cen!r} needs velocities (vel=)")
+        try:
+            v_cen = np.asarray(v_cen, dtype=np.float64)
+        except (TypeError, ValueError):
+            raise ValueError(f"v_cen must be None or three finite components, not {v_cen!r}") from None
+        if v_cen.shape != (3,) or not np.isfinite(v_cen).all():
+            raise ValueError(f"v_cen must be None or three finite components, not {v_cen!r}")
+    if G is not None:
+        G = _positive_length("G", G)
+    return dict(edges=edges, geometry=PROFILE_GEOMETRIES.index(geometry), center=c.copy(), v_cen=v_cen, frame=frame,
+                half_height=hh), G
+
+
+class Profile:
+    """A radial profile built from the raw sums of tsp_radial_profile by NumPy alone.  geometry "sphere": spherical shells;
+    "disc": cylindrical annuli.  Per bin (arrays of n_bins): .edges (n_bins + 1), .rbins (the midpoints, as pynbody), .n (the
+    members), .mass, .mass_enc (the mass inside each bin's outer edge: info["mass_inner"] plus the cumulative sum), .r_mean
+    (sum m s / mass), .density (sphere: mass over the shell's volume; disc: the surface density, mass over the annulus' area)
+    and, with velocities, the mass-weighted mean of each velocity component and its dispersion sqrt(max(<c^2> - <c>^2, 0)) --
+    sphere: .v_r, .v_phi, .v_theta, .sigma_r, .sigma_phi, .sigma_theta; disc: .v_R, .v_phi, .v_z, .sigma_R, .sigma_phi, .sigma_z
+    -- and .j (n_bins, 3), the specific angular momentum sum m d x u / mass in the caller's frame; without velocities these are
+    None.  .v_circ = sqrt(G * mass_enc / edges[1:]) when G was given, else None.  Empty bins have zero mass and NaN means.
+    .info: n_valid, n_inner, n_binned, mass_inner.  .sums and .count are the raw arrays."""
+
+    COMPONENTS = {"sphere": ("r", "phi", "theta"), "disc": ("R", "phi", "z")}
+
+    def __init__(self, edges, count, sums, info, geometry="sphere", G=None, with_velocities=True):
+        if geometry not in PROFILE_GEOMETRIES:
+            raise ValueError(f"geometry must be one of {PROFILE_GEOMETRIES}, not {geometry!r}")
+        self.geometry = geometry
+        self.edges = np.asarray(edges, dtype=np.float64)
+        self.count = self.n = np.asarray(count, dtype=np.int64)
+        self.sums = np.asarray(sums, dtype=np.float64)
+        n_bins = len(self.edges) - 1
+        if self.edges.ndim != 1 or n_bins < 1 or self.n.shape != (n_bins,) or self.sums.shape != (n_bins, 11):
+            raise ValueError(f"a profile of {n_bins} bins needs count ({n_bins},) and sums ({n_bins}, 11), not {self.n.shape} and "
+                             f"{self.sums.shape}")
+        self.info = dict(info)
+        lo, hi = self.edges[:-1], self.edges[1:]
+        self.rbins = 0.5 * (lo + hi)
+        self.mass = self.sums[:, 0].copy()
+        self.mass_enc = float(self.info.get("mass_inner", 0.0)) + np.cumsum(self.mass)
+        extent = 4.0 / 3.0 * np.pi * (hi ** 3 - lo ** 3) if geometry == "sphere" else np.pi * (hi ** 2 - lo ** 2)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            self.density = self.mass / extent
+            self.r_mean = self.sums[:, 1] / self.mass
+            self.j = None
+            for k, name in enumerate(self.COMPONENTS[geometry]):
+                mean = sigma = None
+                if with_velocities:
+                    mean = self.sums[:, 2 + k] / self.mass
+                    sigma = np.sqrt(np.maximum(self.sums[:, 5 + k] / self.mass - mean * mean, 0.0))
+                setattr(self, "v_" + name, mean)
+                setattr(self, "sigma_" + name, sigma)
+            if with_velocities:
+                self.j = self.sums[:, 8:11] / self.mass[:, None]
+            self.v_circ = None if G is None else np.sqrt(float(G) * self.mass_enc / hi)
+
+    def __len__(self):
+        return len(self.rbins)
+
+
+def compute_profile(ctx, pos, mass, vel, kwargs, G=None):
+    """The Profile of checked arguments (check_moments_arrays, profile_edges, check_profile_arguments) on an existing context.
+    v_cen None with velocities: the mean velocity of the inner fifth of the sphere of the outermost edge (sphere_moments'
+    default, what orientation uses)."""
+    kwargs = dict(kwargs)
+    columns = None if vel is None else (vel[:, 0], vel[:, 1], vel[:, 2])
+    if vel is None:
+        kwargs["v_cen"] = np.zeros(3)
+    elif kwargs["v_cen"] is None:
+        r = float(kwargs["edges"][-1])
+        kwargs["v_cen"] = ctx.sphere_moments(pos[:, 0], pos[:, 1], pos[:, 2], mass, vel=columns, center=kwargs["center"], r=r,
+                                             r_vel=VEL_RADIUS_FRACTION * r)["v_cen"]
+    raw = ctx.radial_profile(pos[:, 0], pos[:, 1], pos[:, 2], mass, vel=columns, **kwargs)
+    info = {k: raw[k] for k in ("n_valid", "n_inner", "n_binned", "mass_inner")}
+    info["v_cen"] = np.asarray(kwargs["v_cen"], dtype=np.float64)
+    return Profile(kwargs["edges"], raw["count"], raw["sums"], info, PROFILE_GEOMETRIES[kwargs["geometry"]], G, vel is not None)
+
+
+def check_virial_arguments(center, rho_threshold, r_max, refinements):
+    try:
+        c = np.asarray(center, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError(f"center must be three finite coordinates, not {center!r}") from None
+    if c.shape != (3,) or not np.isfinite(c).all():
+        raise ValueError(f"center must be three finite coordinates, not {center!r}")
+    if isinstance(refinements, bool) or not isinstance(refinements, (int, np.integer)) or not 0 <= refinements <= 8:
+        raise ValueError(f"refinements must be an integer from 0 to 8, not {refinements!r}")
+    return c.copy(), _positive_length("rho_threshold", rho_threshold), _positive_length("r_max", r_max), int(refinements)
+
+
+def find_virial_radius(shell_masses, rho_threshold, r_max, refinements=3):
+    """The virial radius by the rule of topsy_amd.virial_radius, from shell_masses(edges) -> (mass per shell, mass inside
+    edges[0]).  Returns (radius, (lower, upper) = the last bracket).  Raises ValueError without a crossing."""
+    edges = profile_edges("log", VIRIAL_BINS, r_max / VIRIAL_LOG_SPAN, r_max)
+    for level in range(refinements + 1):
+        mass, mass_inner = shell_masses(edges)
+        enclosed = np.concatenate([[mass_inner], mass_inner + np.cumsum(mass)])
+        rho = 3.0 * enclosed / (4.0 * np.pi * edges ** 3)
+        below = rho < rho_threshold
+        if level == 0:
+            crossing = np.flatnonzero(~below[:-1] & below[1:])
+            if len(crossing) == 0:
+                raise ValueError(f"the mean enclosed density never falls from above to below rho_threshold = {rho_threshold!r} "
+                                 f"between r_max / {VIRIAL_LOG_SPAN:g} and r_max = {r_max!r}: it runs from {rho[0]!r} to {rho[-1]!r}")
+            k = int(crossing[0]) + 1
+        else:
+            # the bracket's lower edge was above the threshold and its upper edge below: the first edge below it
+            inside = np.flatnonzero(below[1:])
+            k = int(inside[0]) + 1 if len(inside) else len(edges) - 1
+        lower, upper = float(edges[k - 1]), float(edges[k])
+        if level < refinements:
+            edges = profile_edges("lin", VIRIAL_BINS, lower, upper)
+    fraction = (rho[k - 1] - rho_threshold) / (rho[k - 1] - rho[k]) if rho[k - 1] > rho[k] else 0.0
+    return lower + min(max(float(fraction), 0.0), 1.0) * (upper - lower), (lower, upper)
+
+
+def compute_virial_radius(ctx, pos, mass, center, rho_threshold, r_max, refinements):
+    """find_virial_radius of checked arguments on an existing context (tsp_radial_profile: shells, no velocities)."""
+    def shell_masses(edges):
+        raw = ctx.radial_profile(pos[:, 0], pos[:, 1], pos[:, 2], mass, edges=edges, geometry=0, center=center)
+        return raw["sums"][:, 0], raw["mass_inner"]
+    return find_virial_radius(shell_masses, rho_threshold, r_max, refinements)
+
+
 class ArrayDataLoader(AbstractDataLoader):
     """Particles given as numpy arrays (e.g. pulled from a pynbody snapshot by the caller:
     snap['pos'], snap['smooth'], snap['mass'], ...; reference PynbodyDataInMemory, loader.py:79-154).
@@ -762,6 +964,25 @@ class ArrayDataLoader(AbstractDataLoader):
         pos, mass, vel = check_moments_arrays(self._pos, self._mass, self._vel)
         moments = self._with_context(lambda ctx: compute_moments(ctx, pos, mass, vel, c, r, r_vel))
         return orientation_matrix(moments, orient, method, up), moments
+
+    def profile(self, r_max=None, center=None, r_min=0.0, n_bins=100, bins="lin", geometry="sphere", frame=None, half_height=None,
+                v_cen=None, G=None):
+        """The radial Profile of the particles about `center` (None: the initial centre), found on the GPU
+        (tsp_radial_profile) from the host arrays, with the velocities when the loader has them: the arguments of
+        topsy_amd.radial_profile."""
+        edges = profile_edges(bins, n_bins, r_min, r_max)
+        center = self.get_initial_center() if center is None else center
+        kwargs, G = check_profile_arguments(center, edges, geometry, frame, half_height, v_cen, G, self._vel is not None)
+        pos, mass, vel = check_moments_arrays(self._pos, self._mass, self._vel)
+        return self._with_context(lambda ctx: compute_profile(ctx, pos, mass, vel, kwargs, G))
+
+    def virial_radius(self, rho_threshold, r_max, center=None, refinements=3):
+        """The radius about `center` (None: the initial centre) inside which the mean density is rho_threshold, by the rule of
+        topsy_amd.virial_radius, found on the GPU from the host arrays."""
+        center = self.get_initial_center() if center is None else center
+        c, rho_threshold, r_max, refinements = check_virial_arguments(center, rho_threshold, r_max, refinements)
+        pos, mass, _ = check_moments_arrays(self._pos, self._mass, None)
+        return self._with_context(lambda ctx: compute_virial_radius(ctx, pos, mass, c, rho_threshold, r_max, refinements))[0]
 
     def get_initial_rotation(self):
         if self._rotation is None:

@@ -217,6 +217,10 @@ class MultiGpuContext:
         """The moments inside a sphere of the whole (caller-ordered) snapshot, on the first context like smoothing_lengths."""
         return self.contexts[0].sphere_moments(x, y, z, mass, **kwargs)
 
+    def radial_profile(self, x, y, z, mass, **kwargs):
+        """The binned shell / annulus sums of the whole (caller-ordered) snapshot, on the first context like smoothing_lengths."""
+        return self.contexts[0].radial_profile(x, y, z, mass, **kwargs)
+
     def generate_synthetic(self, n_total, first=0, count=None, seed=1337, h_cap=0.0, with_quantity=False, with_rgb=False):
         count = n_total - first if count is None else count
         # the generator's index bijection makes every index range a uniform sample: contiguous shards are balanced

@@ -131,6 +131,14 @@ class SurfaceView(FrameInterface):
         """The visualizer's orient: the camera is the visualizer's."""
         return self._vis.orient(orient, radius, center=center, method=method)
 
+    def profile(self, r_max=None, **kwargs):
+        """The visualizer's profile: the camera is the visualizer's."""
+        return self._vis.profile(r_max, **kwargs)
+
+    def scale_to_virial(self, rho_threshold, r_max, factor=1.0):
+        """The visualizer's scale_to_virial: the camera is the visualizer's."""
+        return self._vis.scale_to_virial(rho_threshold, r_max, factor)
+
     def centre_on_halo(self, n):
         """The visualizer's centre_on_halo: the camera is the visualizer's."""
         return self._vis.centre_on_halo(n)

@@ -318,6 +318,34 @@ class VisualizerBase(FrameInterface):
         self.rotation_matrix = matrix
         return matrix
 
+    def _array_loader(self, what):
+        if not isinstance(self.data_loader, loader.ArrayDataLoader):
+            raise ValueError(f"{type(self.data_loader).__name__} keeps no host arrays to take {what} from: it needs from_arrays / "
+                             f"ArrayDataLoader")
+        return self.data_loader
+
+    def profile(self, r_max=None, center=None, frame=None, **kwargs):
+        """The radial Profile (topsy_amd.radial_profile) of what the view shows: about `center` (None: -position_offset, what
+        the view is centred on) in `frame` (None: rotation_matrix, so that geometry="disc" bins in annuli about the view axis:
+        after orient("faceon") v_phi is the disc's rotation curve).  The other keywords are radial_profile's (r_min, n_bins,
+        bins, geometry, half_height, v_cen, G).  The sums are found on the GPU from the loader's host arrays."""
+        ld = self._array_loader("a profile")
+        if center is None:
+            center = -np.asarray(self.position_offset, dtype=np.float64)
+        if frame is None:
+            frame = np.asarray(self.rotation_matrix, dtype=np.float64)
+        return ld.profile(r_max, center=center, frame=frame, **kwargs)
+
+    def scale_to_virial(self, rho_threshold, r_max, factor=1.0):
+        """Set scale to `factor` times the virial radius (topsy_amd.virial_radius: mean enclosed density rho_threshold, searched
+        out to r_max) of what the view is centred on, -position_offset: after centre_on_halo(N) the view then frames halo N.
+        Returns the new scale (the virial radius is scale / factor)."""
+        ld = self._array_loader("a virial radius")
+        factor = loader._positive_length("factor", factor)
+        r_vir = ld.virial_radius(rho_threshold, r_max, center=-np.asarray(self.position_offset, dtype=np.float64))
+        self.scale = factor * r_vir
+        return self.scale
+
     def save(self, filename="output.npy"):
         self._sph.render(DrawReason.EXPORT)
         if filename.endswith(".npy"):
