@@ -36,7 +36,11 @@ enum {
     TSP_ENODEV = -3,   /* no usable GPU */
     TSP_ESTATE = -4,   /* call order violated (e.g. render before upload / before kernel LUT) */
     TSP_ECOMM = -5,    /* RCCL error */
-    TSP_ENOMEM = -6
+    TSP_ENOMEM = -6    /* a device allocation failed.  Every entry point that takes a context may return it (the render
+                          workspace, the post-pass staging and the scratch of the per-call entry points are allocated on
+                          demand): on that return the caller's outputs are untouched, the context -- image, accumulator,
+                          statistics, resident particles, their order and its layout -- is as the call found it,
+                          tsp_last_error names the allocation, and the context stays usable */
 };
 
 /* Render modes: which per-particle channels feed the image (reference SPH subclasses). */

@@ -72,6 +72,22 @@ int alloc_group(tsp_context *ctx, std::initializer_list<DeviceBuffer> bufs, std:
     return TSP_OK;
 }
 
+int scratch_alloc(tsp_context *ctx, const char *site, DeviceScratch &buf, size_t bytes) {
+    TSP_REQUIRE(!buf.p, TSP_ESTATE, "scratch buffer of site %s is allocated twice", site);
+    if (ctx->debug_fail_alloc > 0 && --ctx->debug_fail_alloc == 0) {
+        set_error("injected allocation failure at %s (debug_fail_alloc)", site);
+        return TSP_ENOMEM;
+    }
+    const hipError_t e = hipMalloc(&buf.p, bytes ? bytes : 16);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();     // (a later launch check must not report this allocation)
+        buf.p = nullptr;
+        set_error("hipMalloc of %zu bytes failed at %s: %s", bytes, site, hipGetErrorString(e));
+        return e == hipErrorOutOfMemory ? TSP_ENOMEM : TSP_EHIP;
+    }
+    return TSP_OK;
+}
+
 int check_workspace(const tsp_context *ctx) {
     const Workspace &ws = ctx->ws;
     struct Pair { int64_t cap; const void *p; const char *name; } pairs[] = {
@@ -387,8 +403,8 @@ int tsp_upload_band_magnitudes(tsp_context *ctx, int n_bands, const double *mags
     TSP_HIP(hipSetDevice(ctx->device));
     const int64_t n = ctx->p.n;
     DeviceScratch d_mags, d_w;
-    TSP_HIP(d_mags.alloc((size_t)n_bands * n * sizeof(double)));
-    TSP_HIP(d_w.alloc((size_t)3 * n_bands * sizeof(double)));
+    TSP_SCRATCH_ALLOC(ctx, SITE("band_magnitudes"), d_mags, (size_t)n_bands * n * sizeof(double));
+    TSP_SCRATCH_ALLOC(ctx, SITE("band_weights"), d_w, (size_t)3 * n_bands * sizeof(double));
     TSP_HIP(hipMemcpyAsync(d_mags.p, mags, (size_t)n_bands * n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
     TSP_HIP(hipMemcpyAsync(d_w.p, weights, (size_t)3 * n_bands * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
     int rc;
@@ -444,7 +460,6 @@ int tsp_reorder_spatial(tsp_context *ctx, int n_strata, uint64_t seed, int64_t *
     TSP_REQUIRE(n_strata >= 1 && n_strata <= 4096, TSP_EINVAL, "n_strata %d out of range", n_strata);
     TSP_REQUIRE(ctx->p.n > 0, TSP_ESTATE, "no particles resident");
     TSP_HIP(hipSetDevice(ctx->device));
-    ctx->surface_keys = false;         // (the keys hold indices of the old order)
     return reorder_spatial(ctx, n_strata, seed, perm_out);
 }
 

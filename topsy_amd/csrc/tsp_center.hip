@@ -202,13 +202,13 @@ int shrink_sphere_center(tsp_context *ctx, int64_t n, const float *x, const floa
     const int grid = (int)std::min<int64_t>((nblocks + 1) / 2, (int64_t)ctx->cu_count * 8);
 
     DeviceScratch dx, dy, dz, dw, dboxes, dpartials, dmin;
-    TSP_SCRATCH_ALLOC("tsp_shrink_sphere_center", dx, (size_t)npad * sizeof(float));
-    TSP_SCRATCH_ALLOC("tsp_shrink_sphere_center", dy, (size_t)npad * sizeof(float));
-    TSP_SCRATCH_ALLOC("tsp_shrink_sphere_center", dz, (size_t)npad * sizeof(float));
-    TSP_SCRATCH_ALLOC("tsp_shrink_sphere_center", dw, (size_t)npad * sizeof(float));
-    TSP_SCRATCH_ALLOC("tsp_shrink_sphere_center", dboxes, (size_t)nblocks * 6 * sizeof(float));
-    TSP_SCRATCH_ALLOC("tsp_shrink_sphere_center", dpartials, (size_t)(grid + 1) * sizeof(Partial));
-    TSP_SCRATCH_ALLOC("tsp_shrink_sphere_center", dmin, sizeof(unsigned));
+    TSP_SCRATCH_ALLOC(ctx, SITE("center_x"), dx, (size_t)npad * sizeof(float));
+    TSP_SCRATCH_ALLOC(ctx, SITE("center_y"), dy, (size_t)npad * sizeof(float));
+    TSP_SCRATCH_ALLOC(ctx, SITE("center_z"), dz, (size_t)npad * sizeof(float));
+    TSP_SCRATCH_ALLOC(ctx, SITE("center_mass"), dw, (size_t)npad * sizeof(float));
+    TSP_SCRATCH_ALLOC(ctx, SITE("center_boxes"), dboxes, (size_t)nblocks * 6 * sizeof(float));
+    TSP_SCRATCH_ALLOC(ctx, SITE("center_partials"), dpartials, (size_t)(grid + 1) * sizeof(Partial));
+    TSP_SCRATCH_ALLOC(ctx, SITE("center_min_mass"), dmin, sizeof(unsigned));
 
     auto t0 = std::chrono::steady_clock::now();
     const float *host[4] = {x, y, z, mass};

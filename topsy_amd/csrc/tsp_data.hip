@@ -363,9 +363,14 @@ int reorder_spatial(tsp_context *ctx, int n_strata, uint64_t seed, int64_t *perm
     hipStream_t st = ctx->stream;
     float lo[3], inv[3];
     int wide = 0;              // bit k: axis k is keyed in float64 (its extent overflows float32)
+    // The layout of the new order is built here and becomes the context's only once the particles are in that order: a call
+    // that fails before then (an allocation below) leaves particles and layout describing the same, old, order.
+    std::vector<int64_t> strata_offsets, cell_offsets;
+    int cell_bits = 0;
+    float cell_width[3] = {0, 0, 0};
     {   // bounding box of the finite positions
         DeviceScratch mm;
-        TSP_HIP(mm.alloc(6 * sizeof(unsigned)));
+        TSP_SCRATCH_ALLOC(ctx, SITE("reorder_bounds"), mm, 6 * sizeof(unsigned));
         const unsigned init[6] = {0xffffffffu, 0xffffffffu, 0xffffffffu, 0, 0, 0};
         TSP_HIP(hipMemcpyAsync(mm.p, init, sizeof(init), hipMemcpyHostToDevice, st));
         hipLaunchKernelGGL(bbox_kernel, dim3(1024), dim3(256), 0, st, p.x, p.y, p.z, n, mm.as<unsigned>());
@@ -391,10 +396,10 @@ int reorder_spatial(tsp_context *ctx, int n_strata, uint64_t seed, int64_t *perm
     DeviceScratch order;       // order[new] = old index (relative to the current order)
     {
         DeviceScratch keys, keys2, vals, tmp;
-        TSP_HIP(keys.alloc((size_t)n * 8));
-        TSP_HIP(keys2.alloc((size_t)n * 8));
-        TSP_HIP(vals.alloc((size_t)n * 4));
-        TSP_HIP(order.alloc((size_t)n * 4));
+        TSP_SCRATCH_ALLOC(ctx, SITE("reorder_keys"), keys, (size_t)n * 8);
+        TSP_SCRATCH_ALLOC(ctx, SITE("reorder_keys_sorted"), keys2, (size_t)n * 8);
+        TSP_SCRATCH_ALLOC(ctx, SITE("reorder_index"), vals, (size_t)n * 4);
+        TSP_SCRATCH_ALLOC(ctx, SITE("reorder_order"), order, (size_t)n * 4);
         hipLaunchKernelGGL(morton_key_kernel, dim3(4096), dim3(256), 0, st, p.x, p.y, p.z, n,
                            make_float3(lo[0], lo[1], lo[2]), make_float3(inv[0], inv[1], inv[2]), wide, n_strata, seed,
                            keys.as<uint64_t>(), vals.as<uint32_t>());
@@ -402,17 +407,17 @@ int reorder_spatial(tsp_context *ctx, int n_strata, uint64_t seed, int64_t *perm
         size_t tmp_bytes = 0;
         TSP_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, keys.as<uint64_t>(), keys2.as<uint64_t>(),
                                                    vals.as<uint32_t>(), order.as<uint32_t>(), n, 0, 60, st));
-        TSP_HIP(tmp.alloc(tmp_bytes));
+        TSP_SCRATCH_ALLOC(ctx, SITE("reorder_sort_tmp"), tmp, tmp_bytes);
         TSP_HIP(hipcub::DeviceRadixSort::SortPairs(tmp.p, tmp_bytes, keys.as<uint64_t>(), keys2.as<uint64_t>(),
                                                    vals.as<uint32_t>(), order.as<uint32_t>(), n, 0, 60, st));
         // stratum boundaries in the new order (keys2 holds the sorted keys)
         DeviceScratch d_off;
-        TSP_HIP(d_off.alloc((size_t)(n_strata + 1) * sizeof(int64_t)));
+        TSP_SCRATCH_ALLOC(ctx, SITE("reorder_strata_offsets"), d_off, (size_t)(n_strata + 1) * sizeof(int64_t));
         hipLaunchKernelGGL(key_prefix_offsets_kernel, dim3((n_strata + 256) / 256), dim3(256), 0, st, keys2.as<uint64_t>(), n,
                            (int64_t)n_strata + 1, 48, d_off.as<int64_t>());
         TSP_HIP(hipGetLastError());
-        ctx->strata_offsets.assign((size_t)n_strata + 1, 0);
-        TSP_HIP(hipMemcpyAsync(ctx->strata_offsets.data(), d_off.p, (size_t)(n_strata + 1) * sizeof(int64_t),
+        strata_offsets.assign((size_t)n_strata + 1, 0);
+        TSP_HIP(hipMemcpyAsync(strata_offsets.data(), d_off.p, (size_t)(n_strata + 1) * sizeof(int64_t),
                                hipMemcpyDeviceToHost, st));
         // Cells for view culling (the role of the reference's CellLayout, src/topsy/cell_layout.py): inside a stratum the
         // Morton order stores every cell of a (2^k)^3 grid over the bounding box as ONE contiguous run; k <= 4 (the
@@ -422,18 +427,17 @@ int reorder_spatial(tsp_context *ctx, int n_strata, uint64_t seed, int64_t *perm
         while (k < 4 && n / ((int64_t)n_strata << (3 * (k + 1))) >= 16) ++k;
         const int64_t n_entries = ((int64_t)n_strata << (3 * k)) + 1;
         DeviceScratch d_cell;
-        TSP_HIP(d_cell.alloc((size_t)n_entries * sizeof(int64_t)));
+        TSP_SCRATCH_ALLOC(ctx, SITE("reorder_cell_offsets"), d_cell, (size_t)n_entries * sizeof(int64_t));
         hipLaunchKernelGGL(key_prefix_offsets_kernel, dim3((unsigned)((n_entries + 255) / 256)), dim3(256), 0, st, keys2.as<uint64_t>(), n,
                            n_entries, 48 - 3 * k, d_cell.as<int64_t>());
         TSP_HIP(hipGetLastError());
-        ctx->cell_offsets.assign((size_t)n_entries, 0);
-        TSP_HIP(hipMemcpyAsync(ctx->cell_offsets.data(), d_cell.p, (size_t)n_entries * sizeof(int64_t), hipMemcpyDeviceToHost, st));
-        ctx->cell_bits = k;
+        cell_offsets.assign((size_t)n_entries, 0);
+        TSP_HIP(hipMemcpyAsync(cell_offsets.data(), d_cell.p, (size_t)n_entries * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+        cell_bits = k;
         for (int a = 0; a < 3; ++a) {
-            ctx->cell_lo[a] = lo[a];
             // a cell spans 2^(16 - k) quantisation steps of 1 / inv world units each (inv = 0: a degenerate axis, one cell);
             // +inf for the one cell (k = 0) of a wide axis: the host selects a cell whose centre or reach is not finite
-            ctx->cell_width[a] = inv[a] > 0.0f ? (float)(1 << (16 - k)) / inv[a] : 0.0f;
+            cell_width[a] = inv[a] > 0.0f ? (float)(1 << (16 - k)) / inv[a] : 0.0f;
         }
         // Lane decorrelation (round 5): kernel S gives one lane per particle and 64 consecutive particles per wave step.  Morton
         // neighbours are neighbours on screen, so the lanes of a step scatter their footprints into the same few pixels of the LDS
@@ -457,7 +461,8 @@ int reorder_spatial(tsp_context *ctx, int n_strata, uint64_t seed, int64_t *perm
     }
     // permute every resident attribute through one spare buffer
     DeviceScratch spare;
-    TSP_HIP(spare.alloc((size_t)n * 4));
+    TSP_SCRATCH_ALLOC(ctx, SITE("reorder_spare"), spare, (size_t)n * 4);
+    ctx->surface_keys = false;         // (the keys hold indices of the old order)
     float **arrs[] = {&p.x, &p.y, &p.z, &p.h, &p.m, &p.q, &p.r, &p.g, &p.b};
     for (float **a : arrs) {
         if (!*a) continue;
@@ -473,6 +478,13 @@ int reorder_spatial(tsp_context *ctx, int n_strata, uint64_t seed, int64_t *perm
         uint32_t *t = p.perm; p.perm = spare.as<uint32_t>(); spare.p = t;
     } else {
         p.perm = static_cast<uint32_t *>(order.release());
+    }
+    ctx->strata_offsets.swap(strata_offsets);
+    ctx->cell_offsets.swap(cell_offsets);
+    ctx->cell_bits = cell_bits;
+    for (int a = 0; a < 3; ++a) {
+        ctx->cell_lo[a] = lo[a];
+        ctx->cell_width[a] = cell_width[a];
     }
     if (perm_out) {
         std::vector<uint32_t> hp((size_t)n);
@@ -586,8 +598,8 @@ int measure_read_bandwidth(tsp_context *ctx, int64_t bytes, int iters, double *g
     bytes &= ~(int64_t)4095;
     if (bytes < 4096) bytes = 4096;
     DeviceScratch buf_s, sink_s;
-    TSP_HIP(buf_s.alloc((size_t)bytes));
-    TSP_HIP(sink_s.alloc(4));
+    TSP_SCRATCH_ALLOC(ctx, SITE("bandwidth_buffer"), buf_s, (size_t)bytes);
+    TSP_SCRATCH_ALLOC(ctx, SITE("bandwidth_sink"), sink_s, 4);
     float4 *buf = buf_s.as<float4>();
     float *sink = sink_s.as<float>();
     TSP_HIP(hipMemsetAsync(buf, 0x11, (size_t)bytes, ctx->stream));

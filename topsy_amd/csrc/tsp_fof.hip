@@ -318,7 +318,7 @@ int fof_groups(tsp_context *ctx, int64_t n, const float *x, const float *y, cons
 
         // 5. (the sorted keys are free too: they take the sorted ranking keys; sx the sorted positions, sy the ranks)
         DeviceScratch rkeys, tmp;
-        TSP_SCRATCH_ALLOC(who, rkeys, (size_t)nv * sizeof(uint64_t));
+        TSP_SCRATCH_ALLOC(ctx, SITE("fof_rank_keys"), rkeys, (size_t)nv * sizeof(uint64_t));
         uint32_t *pos = ix.dz.as<uint32_t>(), *sorted_pos = ix.sx.as<uint32_t>();
         int32_t *rank_of = ix.sy.as<int32_t>();
         TSP_HIP(hipMemsetAsync(ix.d_count + 1, 0, 3 * sizeof(unsigned long long), st));
@@ -328,7 +328,7 @@ int fof_groups(tsp_context *ctx, int64_t n, const float *x, const float *y, cons
         size_t tmp_bytes = 0;
         TSP_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, rkeys.as<uint64_t>(), ix.keys2.as<uint64_t>(), pos, sorted_pos,
                                                    (int)nv, 0, 64, st));
-        TSP_SCRATCH_ALLOC(who, tmp, tmp_bytes);
+        TSP_SCRATCH_ALLOC(ctx, SITE("fof_sort_tmp"), tmp, tmp_bytes);
         TSP_HIP(hipcub::DeviceRadixSort::SortPairs(tmp.p, tmp_bytes, rkeys.as<uint64_t>(), ix.keys2.as<uint64_t>(), pos, sorted_pos,
                                                    (int)nv, 0, 64, st));
         TSP_HIP(hipMemsetAsync(rank_of, 0, (size_t)nv * sizeof(int32_t), st));

@@ -173,7 +173,7 @@ struct tsp_context {
     bool overlap_mid_huge = false;    // option: kernels G and H2 on two streams (measured: no gain at 1.25e8, +6 % at 1e7)
     int64_t slice_records = 0;        // option: deferred records kernels G / H2 take per launch (0 = 2^27 mid / 2^30 huge); a block of any size draws in slices
     int debug_fail_stage = 0;         // test aid: the next render fails with TSP_ENOMEM after kernel S (1) / after kernel G (2); cleared by the failure
-    int64_t debug_fail_alloc = 0;     // test aid: the k-th allocation of alloc_group() from now on fails once, as hipMalloc would (0 = off)
+    int64_t debug_fail_alloc = 0;     // test aid: the k-th allocation of alloc_group() or scratch_alloc() from now on fails once, as hipMalloc would (0 = off)
     int stream_occ[3][2] = {};        // kernel S: workgroups resident per CU by [mode][one-channel window | all channels] (occupancy query, once per context)
     bool debug_no_raster = false;    // measurement aid: kernel S classifies and emits records but rasterises nothing (the image is then incomplete)
     int cu_count = 256;
@@ -184,28 +184,29 @@ struct tsp_context {
 };
 
 namespace tsp {
-// hipMalloc'd scratch that is released on every exit path
+// Per-call device scratch that is released on every exit path.  It is allocated by scratch_alloc() alone (TSP_SCRATCH_ALLOC in
+// an entry point), so that every allocation has a named site, counts against option debug_fail_alloc and fails one way.
 struct DeviceScratch {
     void *p = nullptr;
     DeviceScratch() = default;
     DeviceScratch(const DeviceScratch &) = delete;
     DeviceScratch &operator=(const DeviceScratch &) = delete;
     ~DeviceScratch() { if (p) (void)hipFree(p); }
-    hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 16); }
     template <typename T> T *as() const { return static_cast<T *>(p); }
     void *release() { void *q = p; p = nullptr; return q; }
     void reset(void *q) { if (p) (void)hipFree(p); p = q; }
 };
-// buf.alloc(bytes) for a DeviceScratch of the entry point `who`; a failure sets the error text and returns from the caller
-#define TSP_SCRATCH_ALLOC(who, buf, bytes)                                                                               \
-    do {                                                                                                                 \
-        const hipError_t e_ = (buf).alloc(bytes);                                                                        \
-        if (e_ != hipSuccess) {                                                                                          \
-            (void)hipGetLastError();                                                                                     \
-            tsp::set_error("%s: cannot allocate %zu bytes of device memory: %s", (who), (size_t)(bytes),                 \
-                           hipGetErrorString(e_));                                                                       \
-            return e_ == hipErrorOutOfMemory ? TSP_ENOMEM : TSP_EHIP;                                                    \
-        }                                                                                                                \
+// `bytes` (16 at least) of device memory into the empty `buf`.  A failure -- hipMalloc's, or the injected one of option
+// debug_fail_alloc, which counts these allocations and those of alloc_group() alike -- leaves buf empty, puts the site's name
+// into tsp_last_error, clears HIP's sticky last error (a later launch check must not report this allocation) and returns
+// TSP_ENOMEM (TSP_EHIP for another runtime error).  Site names are unique and written as SITE("site"), like alloc_group()'s.
+int scratch_alloc(tsp_context *ctx, const char *site, DeviceScratch &buf, size_t bytes);
+// scratch_alloc() in an entry point: a failure returns its code from the caller.  Entry points allocate before they write to
+// the caller's outputs or change the context, so that a failed call leaves both as they were.
+#define TSP_SCRATCH_ALLOC(ctx, site, buf, bytes)                                     \
+    do {                                                                             \
+        const int rc_ = tsp::scratch_alloc((ctx), (site), (buf), (size_t)(bytes));   \
+        if (rc_ != TSP_OK) return rc_;                                               \
     } while (0)
 
 // Every device buffer that can be (re)allocated after tsp_create and the uploads -- the render workspace, the colormap and
@@ -216,6 +217,7 @@ struct DeviceScratch {
 // TSP_ENOMEM (TSP_EHIP for another runtime error) with the site's name in tsp_last_error.  Site names are unique (a CPU test
 // scans the sources), written first so that they can be found: {"site", (void **)&ptr, bytes}, or SITE("site") where a name
 // is passed on.
+#define SITE(name) name
 struct DeviceBuffer {
     const char *site;
     void **p;
@@ -234,7 +236,6 @@ struct Capacity {      // a capacity field and the value it takes once its group
     }
 };
 int alloc_group(tsp_context *ctx, std::initializer_list<DeviceBuffer> bufs, std::initializer_list<Capacity> caps);
-#define SITE(name) name
 
 // Host-side invariant of the workspace: a capacity above 0 means every buffer it describes exists.  Checked before the kernels
 // that use the buffers are launched, so that a missed allocation site is an error (TSP_ESTATE) and never a write through null.

@@ -238,11 +238,13 @@ int sphere_moments(tsp_context *ctx, int64_t n, const float *x, const float *y, 
     const int grid = (int)std::min<int64_t>((nblocks + 1) / 2, (int64_t)ctx->cu_count * 8);
 
     const float *host[7] = {x, y, z, mass, vx, vy, vz};
+    static const char *const dev_site[7] = {SITE("moments_x"),  SITE("moments_y"),  SITE("moments_z"), SITE("moments_mass"),
+                                            SITE("moments_vx"), SITE("moments_vy"), SITE("moments_vz")};
     DeviceScratch dev[7], dboxes, dpartials, dcount;
-    for (int a = 0; a < n_arrays; ++a) TSP_SCRATCH_ALLOC("tsp_sphere_moments", dev[a], (size_t)npad * sizeof(float));
-    TSP_SCRATCH_ALLOC("tsp_sphere_moments", dboxes, (size_t)nblocks * 6 * sizeof(float));
-    TSP_SCRATCH_ALLOC("tsp_sphere_moments", dpartials, (size_t)(grid + 1) * sizeof(Sums));
-    TSP_SCRATCH_ALLOC("tsp_sphere_moments", dcount, sizeof(unsigned long long));
+    for (int a = 0; a < n_arrays; ++a) TSP_SCRATCH_ALLOC(ctx, dev_site[a], dev[a], (size_t)npad * sizeof(float));
+    TSP_SCRATCH_ALLOC(ctx, SITE("moments_boxes"), dboxes, (size_t)nblocks * 6 * sizeof(float));
+    TSP_SCRATCH_ALLOC(ctx, SITE("moments_partials"), dpartials, (size_t)(grid + 1) * sizeof(Sums));
+    TSP_SCRATCH_ALLOC(ctx, SITE("moments_valid_count"), dcount, sizeof(unsigned long long));
 
     auto t0 = std::chrono::steady_clock::now();
     for (int a = 0; a < n_arrays; ++a) {

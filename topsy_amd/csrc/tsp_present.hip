@@ -447,12 +447,12 @@ int compose(tsp_context *ctx, int W, int H, const tsp_present_base *base, const 
     const size_t frame_bytes = (size_t)W * H * (hdr ? 8 : 4);
     const size_t out_bytes = yuv420 ? (size_t)W * H + 2 * ((size_t)(W / 2) * (H / 2)) : frame_bytes;
     DeviceScratch d_tex, d_prims, d_lut, d_frame, d_yuv, d_filtered;
-    TSP_SCRATCH_ALLOC("tsp_present", d_frame, frame_bytes);
-    if (yuv420) TSP_SCRATCH_ALLOC("tsp_present", d_yuv, out_bytes);
-    TSP_SCRATCH_ALLOC("tsp_present", d_prims, prims.size() * sizeof(PresentPrim));
-    TSP_SCRATCH_ALLOC("tsp_present", d_tex, (size_t)n_texels * sizeof(float4));
-    if (h_lut) TSP_SCRATCH_ALLOC("tsp_present", d_lut, (size_t)n_lut * sizeof(float4));
-    if (surf) TSP_SCRATCH_ALLOC("tsp_present", d_filtered, (size_t)ctx->R * ctx->R * sizeof(float2));
+    TSP_SCRATCH_ALLOC(ctx, SITE("present_frame"), d_frame, frame_bytes);
+    if (yuv420) TSP_SCRATCH_ALLOC(ctx, SITE("present_yuv"), d_yuv, out_bytes);
+    TSP_SCRATCH_ALLOC(ctx, SITE("present_prims"), d_prims, prims.size() * sizeof(PresentPrim));
+    TSP_SCRATCH_ALLOC(ctx, SITE("present_textures"), d_tex, (size_t)n_texels * sizeof(float4));
+    if (h_lut) TSP_SCRATCH_ALLOC(ctx, SITE("present_lut"), d_lut, (size_t)n_lut * sizeof(float4));
+    if (surf) TSP_SCRATCH_ALLOC(ctx, SITE("present_filtered"), d_filtered, (size_t)ctx->R * ctx->R * sizeof(float2));
 
     for (int l = 0; l < n_layers; ++l)
         if (tex_at[l] >= 0)

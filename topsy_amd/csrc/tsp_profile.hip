@@ -339,13 +339,15 @@ int radial_profile(tsp_context *ctx, int64_t n, const float *x, const float *y, 
     p.skip_r2 = spec->geometry == 0 ? E2[n_bins] : (E2[n_bins] + spec->half_height * spec->half_height) * (1.0 + 1e-5);
 
     const float *host[7] = {x, y, z, mass, vx, vy, vz};
+    static const char *const dev_site[7] = {SITE("profile_x"),  SITE("profile_y"),  SITE("profile_z"), SITE("profile_mass"),
+                                            SITE("profile_vx"), SITE("profile_vy"), SITE("profile_vz")};
     DeviceScratch dev[7], dboxes, dpartials, dresult, dedges, dcount;
-    for (int a = 0; a < n_arrays; ++a) TSP_SCRATCH_ALLOC("tsp_radial_profile", dev[a], (size_t)npad * sizeof(float));
-    TSP_SCRATCH_ALLOC("tsp_radial_profile", dboxes, (size_t)nblocks * 6 * sizeof(float));
-    TSP_SCRATCH_ALLOC("tsp_radial_profile", dpartials, profile_partial_bytes(grid, n_bins));
-    TSP_SCRATCH_ALLOC("tsp_radial_profile", dresult, (size_t)n_entries * sizeof(double));
-    TSP_SCRATCH_ALLOC("tsp_radial_profile", dedges, (size_t)n_rows * sizeof(double));
-    TSP_SCRATCH_ALLOC("tsp_radial_profile", dcount, 2 * sizeof(unsigned long long));
+    for (int a = 0; a < n_arrays; ++a) TSP_SCRATCH_ALLOC(ctx, dev_site[a], dev[a], (size_t)npad * sizeof(float));
+    TSP_SCRATCH_ALLOC(ctx, SITE("profile_boxes"), dboxes, (size_t)nblocks * 6 * sizeof(float));
+    TSP_SCRATCH_ALLOC(ctx, SITE("profile_partials"), dpartials, profile_partial_bytes(grid, n_bins));
+    TSP_SCRATCH_ALLOC(ctx, SITE("profile_result"), dresult, (size_t)n_entries * sizeof(double));
+    TSP_SCRATCH_ALLOC(ctx, SITE("profile_edges"), dedges, (size_t)n_rows * sizeof(double));
+    TSP_SCRATCH_ALLOC(ctx, SITE("profile_counters"), dcount, 2 * sizeof(unsigned long long));
 
     auto t0 = std::chrono::steady_clock::now();
     for (int a = 0; a < n_arrays; ++a) {

@@ -276,10 +276,10 @@ int build_morton_index(tsp_context *ctx, const char *who, int64_t n, const float
     DeviceScratch &dx = ix.dx, &dy = ix.dy, &dz = ix.dz, &keys2 = ix.keys2, &vals = ix.vals, &vals2 = ix.vals2, &sx = ix.sx,
                   &sy = ix.sy, &sz = ix.sz, &mm = ix.mm;
     DeviceScratch keys;
-    TSP_SCRATCH_ALLOC(who, dx, fbytes);
-    TSP_SCRATCH_ALLOC(who, dy, fbytes);
-    TSP_SCRATCH_ALLOC(who, dz, fbytes);
-    TSP_SCRATCH_ALLOC(who, mm, 6 * sizeof(unsigned) + 4 * sizeof(unsigned long long));
+    TSP_SCRATCH_ALLOC(ctx, SITE("index_x"), dx, fbytes);
+    TSP_SCRATCH_ALLOC(ctx, SITE("index_y"), dy, fbytes);
+    TSP_SCRATCH_ALLOC(ctx, SITE("index_z"), dz, fbytes);
+    TSP_SCRATCH_ALLOC(ctx, SITE("index_bounds"), mm, 6 * sizeof(unsigned) + 4 * sizeof(unsigned long long));
     TSP_HIP(hipMemcpyAsync(dx.p, x, fbytes, hipMemcpyHostToDevice, st));
     TSP_HIP(hipMemcpyAsync(dy.p, y, fbytes, hipMemcpyHostToDevice, st));
     TSP_HIP(hipMemcpyAsync(dz.p, z, fbytes, hipMemcpyHostToDevice, st));
@@ -317,10 +317,10 @@ int build_morton_index(tsp_context *ctx, const char *who, int64_t n, const float
     }
     g.eps = (float)(1e-5 * maxabs) + 1e-30f;
 
-    TSP_SCRATCH_ALLOC(who, keys, (size_t)n * sizeof(uint64_t));
-    TSP_SCRATCH_ALLOC(who, keys2, (size_t)n * sizeof(uint64_t));
-    TSP_SCRATCH_ALLOC(who, vals, (size_t)n * sizeof(uint32_t));
-    TSP_SCRATCH_ALLOC(who, vals2, (size_t)n * sizeof(uint32_t));
+    TSP_SCRATCH_ALLOC(ctx, SITE("index_keys"), keys, (size_t)n * sizeof(uint64_t));
+    TSP_SCRATCH_ALLOC(ctx, SITE("index_keys_sorted"), keys2, (size_t)n * sizeof(uint64_t));
+    TSP_SCRATCH_ALLOC(ctx, SITE("index_order"), vals, (size_t)n * sizeof(uint32_t));
+    TSP_SCRATCH_ALLOC(ctx, SITE("index_order_sorted"), vals2, (size_t)n * sizeof(uint32_t));
     hipLaunchKernelGGL(smooth_key_kernel, dim3(grid), dim3(256), 0, st, dx.as<float>(), dy.as<float>(), dz.as<float>(), n, g,
                        keys.as<uint64_t>(), vals.as<uint32_t>(), d_count);
     TSP_HIP(hipGetLastError());
@@ -336,15 +336,15 @@ int build_morton_index(tsp_context *ctx, const char *who, int64_t n, const float
         size_t tmp_bytes = 0;
         TSP_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, keys.as<uint64_t>(), keys2.as<uint64_t>(), vals.as<uint32_t>(),
                                                    vals2.as<uint32_t>(), (int)n, 0, 64, st));
-        TSP_SCRATCH_ALLOC(who, tmp, tmp_bytes);
+        TSP_SCRATCH_ALLOC(ctx, SITE("index_sort_tmp"), tmp, tmp_bytes);
         TSP_HIP(hipcub::DeviceRadixSort::SortPairs(tmp.p, tmp_bytes, keys.as<uint64_t>(), keys2.as<uint64_t>(), vals.as<uint32_t>(),
                                                    vals2.as<uint32_t>(), (int)n, 0, 64, st));
         TSP_HIP(hipStreamSynchronize(st));
     }
     keys.reset(nullptr);
-    TSP_SCRATCH_ALLOC(who, sx, (size_t)nv * sizeof(float));
-    TSP_SCRATCH_ALLOC(who, sy, (size_t)nv * sizeof(float));
-    TSP_SCRATCH_ALLOC(who, sz, (size_t)nv * sizeof(float));
+    TSP_SCRATCH_ALLOC(ctx, SITE("index_sorted_x"), sx, (size_t)nv * sizeof(float));
+    TSP_SCRATCH_ALLOC(ctx, SITE("index_sorted_y"), sy, (size_t)nv * sizeof(float));
+    TSP_SCRATCH_ALLOC(ctx, SITE("index_sorted_z"), sz, (size_t)nv * sizeof(float));
     hipLaunchKernelGGL(smooth_gather_kernel, dim3(grid), dim3(256), 0, st, dx.as<float>(), dy.as<float>(), dz.as<float>(),
                        vals2.as<uint32_t>(), nv, sx.as<float>(), sy.as<float>(), sz.as<float>());
     TSP_HIP(hipGetLastError());
@@ -404,8 +404,8 @@ int sph_sum(tsp_context *ctx, int64_t n, const float *x, const float *y, const f
 
     // h and a into Morton order; the raw y and z buffers are free once the positions are gathered
     DeviceScratch dh, da;
-    TSP_SCRATCH_ALLOC("tsp_sph_sum", dh, fbytes);
-    TSP_SCRATCH_ALLOC("tsp_sph_sum", da, fbytes);
+    TSP_SCRATCH_ALLOC(ctx, SITE("sph_sum_h"), dh, fbytes);
+    TSP_SCRATCH_ALLOC(ctx, SITE("sph_sum_a"), da, fbytes);
     TSP_HIP(hipMemcpyAsync(dh.p, h, fbytes, hipMemcpyHostToDevice, st));
     TSP_HIP(hipMemcpyAsync(da.p, a, fbytes, hipMemcpyHostToDevice, st));
     float *sh = ix.dy.as<float>(), *sa = ix.dz.as<float>();

@@ -178,8 +178,8 @@ int render_surface(tsp_context *ctx, const Camera &cam, float cut, const int64_t
         acc += h_lens[i];
     }
     pack[3 * n_ranges] = acc;
-    TSP_HIP(d_ranges.alloc(pack.size() * sizeof(int64_t)));
-    TSP_HIP(d_count.alloc(sizeof(unsigned long long)));
+    TSP_SCRATCH_ALLOC(ctx, SITE("surface_ranges"), d_ranges, pack.size() * sizeof(int64_t));
+    TSP_SCRATCH_ALLOC(ctx, SITE("surface_drawn_count"), d_count, sizeof(unsigned long long));
     TSP_HIP(hipMemcpyAsync(d_ranges.p, pack.data(), pack.size() * sizeof(int64_t), hipMemcpyHostToDevice, st));
     TSP_HIP(hipMemsetAsync(d_count.p, 0, sizeof(unsigned long long), st));
     unsigned long long *keys = reinterpret_cast<unsigned long long *>(ctx->image64);
@@ -243,11 +243,11 @@ int density_order_stats(tsp_context *ctx, const int64_t *ranks, int n_ranks, flo
     DeviceScratch keys, keys2, tmp, d_ranks, d_out;
     size_t tmp_bytes = 0;
     TSP_HIP(hipcub::DeviceRadixSort::SortKeys(nullptr, tmp_bytes, (uint32_t *)nullptr, (uint32_t *)nullptr, n, 0, 32, st));
-    TSP_HIP(keys.alloc((size_t)n * 4));
-    TSP_HIP(keys2.alloc((size_t)n * 4));
-    TSP_HIP(tmp.alloc(tmp_bytes));
-    TSP_HIP(d_ranks.alloc((size_t)n_ranks * sizeof(int64_t)));
-    TSP_HIP(d_out.alloc((size_t)n_ranks * 4));
+    TSP_SCRATCH_ALLOC(ctx, SITE("rho_keys"), keys, (size_t)n * 4);
+    TSP_SCRATCH_ALLOC(ctx, SITE("rho_keys_sorted"), keys2, (size_t)n * 4);
+    TSP_SCRATCH_ALLOC(ctx, SITE("rho_sort_tmp"), tmp, tmp_bytes);
+    TSP_SCRATCH_ALLOC(ctx, SITE("rho_ranks"), d_ranks, (size_t)n_ranks * sizeof(int64_t));
+    TSP_SCRATCH_ALLOC(ctx, SITE("rho_values"), d_out, (size_t)n_ranks * 4);
     const unsigned grid = (unsigned)std::min<int64_t>((n + 255) / 256, (int64_t)ctx->cu_count * 16);
     hipLaunchKernelGGL(rho_key_kernel, dim3(grid), dim3(256), 0, st, ctx->p.m, ctx->p.h, n, keys.as<uint32_t>());
     TSP_HIP(hipGetLastError());
@@ -377,9 +377,9 @@ int surface_present(tsp_context *ctx, const tsp_surface_params &prm, float *cont
     const int64_t npix = (int64_t)R * R;
     hipStream_t st = ctx->stream;
     DeviceScratch filtered, lut;
-    TSP_HIP(filtered.alloc((size_t)npix * sizeof(float2)));
+    TSP_SCRATCH_ALLOC(ctx, SITE("surface_filtered"), filtered, (size_t)npix * sizeof(float2));
     if (rgba8_out && prm.weighted_average) {
-        TSP_HIP(lut.alloc((size_t)prm.n_lut * sizeof(float4)));
+        TSP_SCRATCH_ALLOC(ctx, SITE("surface_lut"), lut, (size_t)prm.n_lut * sizeof(float4));
         TSP_HIP(hipMemcpyAsync(lut.p, prm.lut_rgba, (size_t)prm.n_lut * sizeof(float4), hipMemcpyHostToDevice, st));
     }
     TSP_HIP(hipEventRecord(ctx->ev[EV_T3], st));
