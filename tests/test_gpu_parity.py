@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 from conftest import make_cloud
+from parity_scenes import _rot, abs_terms_image, check_2ch, oracle_render
 
 pytestmark = pytest.mark.gpu
 
@@ -19,38 +20,11 @@ def native():
     return _native
 
 
-def oracle_render(pos, h, a, b, c, mode, M, sf, R, mips, ranges=None):
-    from oracle import oracle_c
-    x, y, z = (np.ascontiguousarray(pos[:, k]) for k in range(3))
-    return oracle_c.splat(x, y, z, h, a, b, c, mode=mode, M=M, sf=sf, R=R, mips=mips, ranges=ranges)
-
-
-def abs_terms_image(pos, h, m, q, M, sf, R, mips):
-    """sum of |val * q| per pixel: the scale of the weighted channel's rounding noise."""
-    img, _ = oracle_render(pos, h, m, np.abs(q), None, 0, M, sf, R, mips)
-    return img[..., 1]
-
-
-def check_2ch(got, want, abs_terms, rtol=1e-5):
-    d0 = np.abs(got[..., 0] - want[..., 0])
-    assert (d0 <= rtol * np.abs(want[..., 0]) + 1e-30).all(), \
-        f"density channel: max rel err {np.max(d0 / np.maximum(np.abs(want[..., 0]).astype(np.float64), 1e-300))}"
-    d1 = np.abs(got[..., 1] - want[..., 1])
-    assert (d1 <= rtol * abs_terms + 1e-30).all(), "weighted channel beyond atol scaled by sum|terms|"
-
-
 CAMERAS = [
     ("identity", np.eye(3), np.zeros(3), 200.0),
     ("zoom_rot", None, np.array([1.5, -2.0, 0.25]), 35.0),
     ("wide", None, np.zeros(3), 900.0),
 ]
-
-
-def _rot(a, b):
-    ca, sa, cb, sb = np.cos(a), np.sin(a), np.cos(b), np.sin(b)
-    rx = np.array([[ca, 0, sa], [0, 1, 0], [-sa, 0, ca]])
-    ry = np.array([[1, 0, 0], [0, cb, -sb], [0, sb, cb]])
-    return rx @ ry
 
 
 @pytest.mark.parametrize("pipe", ["generic", "default"])
@@ -277,7 +251,10 @@ def test_reference_kats_through_hip(native, mips, golden):
 @pytest.mark.parametrize("R", [1, 2, 8, 33, 65])
 def test_tiny_and_odd_resolutions(native, mips, R):
     """Resolutions below / not a multiple of every tile size (64-px window, 64x32 and 128x64 tiles), weighted and density (the
-    single-channel builds: kernel S's one-column path, kernel N's 16 x 32 strips, H2's asm walk)."""
+    single-channel builds).  By width (P = 2 h R / 90 px; test_parity_scenes_cpu.py pins these figures) the cloud reaches
+    kernel S alone at R = 1, 2 and 8 (P <= 1.3, 2.7 and 10.6 px: its one-column path among them), 383 mid footprints and no huge
+    one at R = 33 (kernel N's 16 x 32 / 16 x 16 strips), and all three classes -- kernel H2 and its asm walk included -- only at
+    R = 65.  Footprints of every class on images below one tile: test_gpu_small_images.py."""
     from oracle import oracle_np
     M, sf = oracle_np.transform_matrix(_rot(0.2, 0.1), np.zeros(3), 90.0)
     pos, h, m, q, _ = make_cloud(3000, seed=21)
@@ -291,7 +268,10 @@ def test_tiny_and_odd_resolutions(native, mips, R):
         ctx.render(M, sf)
         got = ctx.read_image()
         want, nfrag = oracle_render(pos, h, m, q if mode == "weighted" else None, None, 0, M, sf, R, mips)
-        assert ctx.stats()["n_fragments"] == nfrag, mode
+        st = ctx.stats()
+        assert st["n_fragments"] == nfrag, mode
+        if R == 65:
+            assert st["n_huge"] > 0
         if mode == "weighted":
             check_2ch(got, want, abs_terms_image(pos, h, m, q, M, sf, R, mips))
         else:
@@ -651,7 +631,7 @@ def test_asymmetric_kernel_lut_uses_full_tables(native, mips):
     pos, h, m, q, _ = make_cloud(20000, seed=9)
     rs = np.random.RandomState(2)
     skew = mips.copy()
-    skew *= (1.0 + 0.05 * rs.uniform(size=skew.shape)).astype(np.float32)      # no symmetry left, corners no longer zero
+    skew *= (1.0 + 0.05 * rs.uniform(size=skew.shape)).astype(np.float32)      # no symmetry left; the corners stay exactly zero (0 * x = 0): lit corners are test_gpu_lut_contract.py
     for lut in (mips, skew):
         ctx = native.Context(300, 2)
         ctx.set_kernel_mips(lut)

@@ -130,7 +130,7 @@ struct tsp_context {
     bool have_sphere_mips = false;    // tsp_set_sphere_mips was called
     bool surface_keys = false;        // image64 holds the 64-bit occlusion keys of tsp_render_surface, not float64 sums
     bool lut_mirror_symmetric = false;    // every mip level equals its left-right and top-bottom mirror images bit for bit
-    bool lut_zero_outside_disc = false;   // every level-0 texel whose centre is >= 2h from the centre is exactly 0
+    bool lut_zero_outside_disc = false;   // on every mip level, each texel whose centre is >= 2h from the centre is exactly 0
     tsp::Particles p;
     tsp::Counters *counters = nullptr;
     tsp::Workspace ws;
