@@ -47,7 +47,8 @@ enum {
 enum {
     TSP_MODE_WEIGHTED = 0, /* SPH: ch0 += k*m/h^2, ch1 += k*m/h^2*q      (sph.wgsl:76-83,139-146)  C=2 */
     TSP_MODE_DEPTH = 1,    /* DepthSPH: ch1 weights by clip-space z       (sph.wgsl:86-91)          C=2 */
-    TSP_MODE_RGB = 2       /* RGBSPH: ch0..2 += k*(r,g,b)/h^2, ch3 += 1   (sph.wgsl:69-73,161-165)  C=4 */
+    TSP_MODE_RGB = 2,      /* RGBSPH: ch0..2 += k*(r,g,b)/h^2, ch3 += 1   (sph.wgsl:69-73,161-165)  C=4 */
+    TSP_MODE_KINEMATIC = 3 /* line-of-sight velocity moments: ch0..2 += k*(m, m u, m u^2)/h^2, ch3 += 1 ("Kinematic maps" below)  C=4 */
 };
 
 /* Pipeline selection for tsp_render (flags argument). 0 = default (fast three-class pipeline). */
@@ -96,7 +97,9 @@ const char *tsp_last_error(void);
  * 115: new entry point tsp_sphere_moments and the struct tsp_moments (the moments of the particles inside a sphere: what a
  * face-on or side-on orientation is taken from); nothing else changed.
  * 116: new entry point tsp_radial_profile and the structs tsp_profile_spec / tsp_profile_info (binned shell and annulus sums: radial
- * profiles, the virial radius); nothing else changed. */
+ * profiles, the virial radius); nothing else changed.
+ * 117: kinematic maps: TSP_MODE_KINEMATIC and the entry points tsp_upload_velocities, tsp_set_line_of_sight, tsp_velocity_moments,
+ * tsp_colormap_moment; no struct changed, nothing else changed. */
 int tsp_version(void);
 int tsp_stats_size(void);
 
@@ -452,6 +455,53 @@ int tsp_radial_profile(tsp_context *ctx, int64_t n, const float *x, const float 
                        const float *vx, const float *vy, const float *vz,      /* all three or none (NULL) */
                        const tsp_profile_spec *spec, int64_t *count_out /* n_bins */, double *sums_out /* n_bins * 11 */,
                        tsp_profile_info *info_out);
+
+/* Kinematic maps: the mass-weighted mean line-of-sight velocity and its dispersion per pixel, from resident velocities (what
+ * pynbody's image(qty="vz", av_z=True) draws after analysis.angmom.sideon; the reference has no such mode).  The rgb kernels
+ * accumulate three independent weighted sums and an exact fragment count; fed the "colours" (m, m u, m u^2) of a particle, u its
+ * velocity along the line of sight, one splat pass leaves per pixel
+ *     S = sum k m / h^2,   A = sum k m u / h^2,   B = sum k m u^2 / h^2,   n = the fragment count
+ * (k the kernel value of the fragment), with the arithmetic, the tolerances and the count of TSP_MODE_RGB.
+ *   - Velocities.  tsp_upload_velocities: float32, caller's order (permuted by the library after tsp_reorder_spatial, as
+ *     tsp_upload_quantity); all three arrays, or all three NULL, which frees them; anything else TSP_EINVAL.  TSP_ESTATE before the
+ *     particles are uploaded.  tsp_upload_particles and tsp_generate_synthetic drop them; tsp_download_particles does not return them.
+ *   - Line of sight.  tsp_set_line_of_sight: axis finite with |sqrt(axis . axis) - 1| <= 1e-5 (formed in float64), v_ref finite;
+ *     otherwise TSP_EINVAL and the line of sight set before stays.  For a camera with rotation matrix Q (clip = Q (x + offset) /
+ *     scale) the axis is Q's third row.  -0 components are taken as +0.
+ *   - Weights.  Per particle, once per change of the line of sight or of the particles (not per block, not for a change of pan or
+ *     zoom), in float32 with these operations in this order, none fused:
+ *         u = ((axis[0] * (vx - v_ref[0]) + axis[1] * (vy - v_ref[1])) + axis[2] * (vz - v_ref[2]))
+ *         r = m;  g = m * u;  b = g * u;      m or u not finite: r = g = b = +0 (the particle's fragments are still counted)
+ *         hh = h * h;  wr = r / hh;  wg = g / hh;  wb = b / hh
+ *     A pure stream, 20 bytes read and 12 written per particle.  The weights live where TSP_MODE_RGB keeps its own (a render in
+ *     either mode after the other recomputes them from the untouched r, g, b or m, velocities: 12 bytes per particle for both).
+ *   - tsp_render(mode = TSP_MODE_KINEMATIC) needs a 4-channel context (TSP_EINVAL), flags = TSP_PIPE_DEFAULT (TSP_EINVAL: the
+ *     generic kernel has no kinematic form), and mass, velocities and a line of sight (TSP_ESTATE).  A clear = 0 block continues an
+ *     image only in the 4-channel mode that started it, and a kinematic one only along the same axis and v_ref (compared bit for
+ *     bit): otherwise TSP_ESTATE.  As every refused render, it leaves image, accumulator and tsp_stats as they were.
+ *   - tsp_velocity_moments: valid while the presentation image is a kinematic one -- the last successful tsp_render was kinematic;
+ *     tsp_write_image, tsp_set_reduced_image, tsp_comm_reduce_image and tsp_tile_periodic keep that, tsp_render_surface and a render
+ *     in another mode end it -- and has 4 active channels; otherwise TSP_ESTATE.  It reads the float32 presentation image (after a
+ *     cross-rank reduce: the sum), and writes maps_out[R][R][4] = (S, (float)mean, (float)sigma, n) with, in float64, every
+ *     operation correctly rounded and none fused:
+ *         if S > 0 and S, A, B are finite:  mean = A / S;  var = B / S - mean * mean;  var < 0: var = 0;  sigma = sqrt(var)
+ *         otherwise mean = sigma = NaN (0x7fc00000).
+ *     B / S - mean^2 cancels: it loses about 6e-8 * (mean / sigma)^2 of relative accuracy in sigma^2 (the float32 rounding of the
+ *     weights and channels against the size of mean^2).  That is what v_ref is for: subtract the bulk velocity (e.g. v_cen of
+ *     tsp_sphere_moments) before the squares are formed, and add it back to mean if wanted.
+ *   - tsp_colormap_moment: the scalar map of tsp_colormap_scalar, unweighted, of map `which` (1: mean, 2: sigma) -> RGBA8, bit for
+ *     bit what that map gives on the image (value, 0).  Same conditions as tsp_velocity_moments; which or the LUT out of range:
+ *     TSP_EINVAL.
+ *   Neither of the two changes the image, the accumulator or tsp_stats.  Both form the maps in the staging buffer of
+ *   tsp_colormap_rgb's float output (allocated on first use: TSP_ENOMEM).
+ * Not provided: velocities on a tsp_group or sharded over several contexts by the library (a caller that shards uploads each
+ * shard's velocities itself; the reduced image is a valid input of tsp_velocity_moments), canvas-sized frames (tsp_present) of
+ * the maps. */
+int tsp_upload_velocities(tsp_context *ctx, const float *vx, const float *vy, const float *vz);
+int tsp_set_line_of_sight(tsp_context *ctx, const float axis[3], const float v_ref[3]);
+int tsp_velocity_moments(tsp_context *ctx, float *maps_out /* R * R * 4 */);
+int tsp_colormap_moment(tsp_context *ctx, int which /* 1 mean, 2 sigma */, const float *lut_rgba, int n_lut, float vmin, float vmax,
+                        int log_scale, uint8_t *out_rgba8);
 
 /* Surface rendering: DepthSPHWithOcclusion + ColorAsSurfaceMap (reference src/topsy/sph.py:448-656, shaders/sph.wgsl:94-122,
  * 149-158, shaders/smooth.wgsl, shaders/surface.wgsl, colormap/surface.py).  Float32 throughout, operations in the order written.

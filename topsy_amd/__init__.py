@@ -274,6 +274,28 @@ def SurfaceView(visualizer, **colormap_params):
     return surface.SurfaceView(visualizer, **colormap_params)
 
 
+def VelocityView(visualizer, v_ref="center", **parameters):
+    """The kinematic maps of `visualizer`'s scene (needs from_arrays(..., vel=vel)): per pixel the mass-weighted mean
+    line-of-sight velocity and its dispersion along the view axis, drawn on the GPU from resident velocities.  v_ref, subtracted
+    from the velocities first: "center" (the mean velocity of the inner fifth of the sphere of radius vis.scale about what the
+    view is centred on, the rule vis.profile uses), three components, or None (zero).  get_maps() (dict: surface_density, v_los,
+    sigma_los, count), get_presentation_image("v_los" | "sigma_los") ((R, R, 4) uint8), view["v_los", "vmax"] etc.  After
+    vis.orient("sideon", r) v_los is the picture of the rotation curve vis.profile gives.  One GPU, no periodic tiling; no
+    canvas-sized frames, not a recorder's target."""
+    from . import kinematics
+    return kinematics.VelocityView(visualizer, v_ref=v_ref, **parameters)
+
+
+def velocity_maps(pos, smooth, mass, vel, rotation=None, center=(0, 0, 0), scale=config.DEFAULT_SCALE,
+                  resolution=config.DEFAULT_RESOLUTION, v_ref=None, device_id=0):
+    """The kinematic maps of arrays, without a visualizer, on GPU `device_id` (C: tsp_render in TSP_MODE_KINEMATIC +
+    tsp_velocity_moments): the dict of VelocityView.get_maps for a camera looking along the third row of `rotation` (None: the
+    identity) at `center` with half-width `scale` and `resolution` pixels a side.  v_ref: None (zero), three components or "center"."""
+    from . import kinematics
+    return kinematics.velocity_maps(pos, smooth, mass, vel, rotation=rotation, center=center, scale=scale, resolution=resolution,
+                                    v_ref=v_ref, device_id=device_id)
+
+
 def __getattr__(name):
     """topsy_amd.VisualizationRecorder (movie recording and export, topsy_amd/recorder), topsy_amd.FofCatalogue and
     topsy_amd.Profile (topsy_amd/loader.py), imported on first use."""

@@ -12,13 +12,13 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("TOPSY_SPLAT_LIB") or os.path.join(_HERE, "libtopsy_splat.so")    # TOPSY_SPLAT_LIB: an alternative build (A/B measurements)
 
-MODE_WEIGHTED, MODE_DEPTH, MODE_RGB = 0, 1, 2
+MODE_WEIGHTED, MODE_DEPTH, MODE_RGB, MODE_KINEMATIC = 0, 1, 2, 3
 PIPE_DEFAULT, PIPE_GENERIC = 0, 1
 SAMPLE_BILINEAR_MIP0, SAMPLE_BILINEAR_MIP = 0x10, 0x20      # diagnostic sampling rules (generic kernel)
 UNIQUE_ID_BYTES = 128
 ABI_VERSION = 112            # the oldest tsp_version() whose structs this binding matches; entry points added since
                              # (113: tsp_shrink_sphere_center, 114: tsp_fof_groups, 115: tsp_sphere_moments,
-                             # 116: tsp_radial_profile) are required by name in load_library()
+                             # 116: tsp_radial_profile, 117: the kinematic maps) are required by name in load_library()
 PRESENT_SCALAR, PRESENT_BIVARIATE, PRESENT_RGB, PRESENT_RGB_HDR = 0, 1, 2, 3
 LAYER_QUAD, LAYER_LINES = 0, 1
 
@@ -128,6 +128,10 @@ SIGNATURES = {
     "tsp_upload_particles": (ctypes.c_int, [_ctx, ctypes.c_int64, _fp, _fp, _fp, _fp, _fp]),
     "tsp_upload_quantity": (ctypes.c_int, [_ctx, _fp]),
     "tsp_upload_rgb": (ctypes.c_int, [_ctx, _fp, _fp, _fp]),
+    "tsp_upload_velocities": (ctypes.c_int, [_ctx, _fp, _fp, _fp]),
+    "tsp_set_line_of_sight": (ctypes.c_int, [_ctx, _fp, _fp]),
+    "tsp_velocity_moments": (ctypes.c_int, [_ctx, _fp]),
+    "tsp_colormap_moment": (ctypes.c_int, [_ctx, ctypes.c_int, _fp, ctypes.c_int, ctypes.c_float, ctypes.c_float, ctypes.c_int, _u8p]),
     "tsp_upload_band_magnitudes": (ctypes.c_int, [_ctx, ctypes.c_int, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]),
     "tsp_generate_synthetic": (ctypes.c_int, [_ctx, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_uint64,
                                               ctypes.c_float, ctypes.c_int, ctypes.c_int]),
@@ -328,6 +332,37 @@ class Context:
         r, g, b = _f32(r, n, "r"), _f32(g, n, "g"), _f32(b, n, "b")
         _check(self._lib.tsp_upload_rgb(self._h, _ptr(r), _ptr(g), _ptr(b)))
 
+    def upload_velocities(self, vx, vy=None, vz=None):
+        """The resident velocities of MODE_KINEMATIC (tsp_upload_velocities): three float32 arrays in the caller's order, or
+        upload_velocities(None), which frees them."""
+        if vx is None and vy is None and vz is None:
+            _check(self._lib.tsp_upload_velocities(self._h, None, None, None))
+            return
+        n = self.num_particles
+        v = [None if a is None else _f32(a, n, name) for a, name in ((vx, "vx"), (vy, "vy"), (vz, "vz"))]
+        _check(self._lib.tsp_upload_velocities(self._h, *[_ptr(a) for a in v]))
+
+    def set_line_of_sight(self, axis, v_ref=(0.0, 0.0, 0.0)):
+        """The unit axis the next MODE_KINEMATIC blocks take the velocities along, and the velocity subtracted first
+        (tsp_set_line_of_sight); both are rounded to float32 here."""
+        axis, v_ref = _f32(axis, 3, "axis"), _f32(v_ref, 3, "v_ref")
+        _check(self._lib.tsp_set_line_of_sight(self._h, _ptr(axis), _ptr(v_ref)))
+
+    def velocity_moments(self):
+        """(R, R, 4) float32 (S, mean, sigma, n) of the kinematic image (tsp_velocity_moments): the surface-density sum, the
+        mass-weighted mean line-of-sight velocity, its dispersion (NaN where S is not > 0) and the fragment count."""
+        out = np.empty((self.resolution, self.resolution, 4), dtype=np.float32)
+        _check(self._lib.tsp_velocity_moments(self._h, _ptr(out)))
+        return out
+
+    def colormap_moment(self, which, lut_rgba, vmin, vmax, log=False):
+        """(R, R, 4) uint8: the scalar map of moment `which` (1: mean, 2: sigma) of the kinematic image (tsp_colormap_moment)."""
+        lut = _f32(lut_rgba, name="lut")
+        out = np.empty((self.resolution, self.resolution, 4), dtype=np.uint8)
+        _check(self._lib.tsp_colormap_moment(self._h, int(which), _ptr(lut), lut.size // 4, float(vmin), float(vmax), int(bool(log)),
+                                             out.ctypes.data_as(_u8p)))
+        return out
+
     def upload_band_magnitudes(self, mags, weights):
         """rgb channels from SSP band magnitudes on the device: channel_c = sum_b weights[c, b] * 10^(-0.4 * mags[b]).
         mags: (n_bands, n) float64; weights: (3, n_bands) float64 (reference loader.py:112-121: diag(0.5, 1, 1) over I, V, U)."""
@@ -395,7 +430,7 @@ class Context:
         sp, lp, nr, _keep = _ranges(starts, lens)
         _check(self._lib.tsp_render(self._h, _ptr(M), float(scale_factor), sp, lp, nr, int(bool(clear)), int(mode),
                                     int(flags), ctypes.byref(ms)))
-        self.active_channels = 4 if mode == MODE_RGB else 2
+        self.active_channels = 4 if mode in (MODE_RGB, MODE_KINEMATIC) else 2
         return ms.value
 
     def read_image(self):

@@ -155,7 +155,7 @@ static int upload_permuted(tsp_context *ctx, float **dst, const float *src, int6
 
 static void free_particles(tsp_context *ctx) {
     Particles &p = ctx->p;
-    float **arrs[] = {&p.x, &p.y, &p.z, &p.h, &p.m, &p.q, &p.r, &p.g, &p.b};
+    float **arrs[] = {&p.x, &p.y, &p.z, &p.h, &p.m, &p.q, &p.r, &p.g, &p.b, &p.vx, &p.vy, &p.vz};
     for (float **a : arrs) {
         if (*a) (void)hipFree(*a);
         *a = nullptr;
@@ -165,7 +165,8 @@ static void free_particles(tsp_context *ctx) {
         if (*a) (void)hipFree(*a);
         *a = nullptr;
     }
-    p.wm_valid = p.wrgb_valid = false;
+    p.wm_valid = false;
+    p.wrgb_source = W_NONE;
     if (p.perm) (void)hipFree(p.perm);
     p.perm = nullptr;
     p.n = 0;
@@ -219,7 +220,7 @@ using namespace tsp;
 extern "C" {
 
 const char *tsp_last_error(void) { return g_err; }
-int tsp_version(void) { return 116; }     // 116: tsp_radial_profile; 115: tsp_sphere_moments; 114: tsp_fof_groups; 113: tsp_shrink_sphere_center; 112: tsp_present_surface, tsp_present_surface_yuv420; 111: tsp_content_neg_inf; 110: tsp_sph_sum; 109: tsp_present_yuv420; 108: tsp_present; 107: surface rendering; 106: tsp_smoothing_lengths; 101: tsp_stats gained ms_mega, n_mega (16 bytes); 102: the per-kernel fragment counts (32 bytes); 103: n_chunk_culled (8 bytes); 104: matrix-core / kernel-I options removed; 105: kernel M's options removed (kernel G draws the mid footprints)
+int tsp_version(void) { return 117; }     // 117: kinematic maps (tsp_upload_velocities, tsp_set_line_of_sight, TSP_MODE_KINEMATIC, tsp_velocity_moments, tsp_colormap_moment); 116: tsp_radial_profile; 115: tsp_sphere_moments; 114: tsp_fof_groups; 113: tsp_shrink_sphere_center; 112: tsp_present_surface, tsp_present_surface_yuv420; 111: tsp_content_neg_inf; 110: tsp_sph_sum; 109: tsp_present_yuv420; 108: tsp_present; 107: surface rendering; 106: tsp_smoothing_lengths; 101: tsp_stats gained ms_mega, n_mega (16 bytes); 102: the per-kernel fragment counts (32 bytes); 103: n_chunk_culled (8 bytes); 104: matrix-core / kernel-I options removed; 105: kernel M's options removed (kernel G draws the mid footprints)
 int tsp_stats_size(void) { return (int)sizeof(tsp_stats); }
 
 int tsp_device_count(void) {
@@ -370,8 +371,47 @@ int tsp_upload_rgb(tsp_context *ctx, const float *r, const float *g, const float
     if ((rc = upload_permuted(ctx, &ctx->p.r, r, ctx->p.n))) return rc;
     if ((rc = upload_permuted(ctx, &ctx->p.g, g, ctx->p.n))) return rc;
     if ((rc = upload_permuted(ctx, &ctx->p.b, b, ctx->p.n))) return rc;
-    ctx->p.wrgb_valid = false;
+    ctx->p.wrgb_source = W_NONE;
     TSP_HIP(hipStreamSynchronize(ctx->stream));
+    return TSP_OK;
+}
+
+int tsp_upload_velocities(tsp_context *ctx, const float *vx, const float *vy, const float *vz) {
+    TSP_REQUIRE(ctx, TSP_EINVAL, "NULL context");
+    TSP_REQUIRE((vx && vy && vz) || (!vx && !vy && !vz), TSP_EINVAL, "vx, vy and vz must be given together or not at all");
+    TSP_HIP(hipSetDevice(ctx->device));
+    Particles &p = ctx->p;
+    if (p.wrgb_source == W_KINEMATIC) p.wrgb_source = W_NONE;     // (the weights were formed from the velocities that go)
+    if (!vx) {
+        float **arrs[] = {&p.vx, &p.vy, &p.vz};
+        for (float **a : arrs) {
+            if (*a) TSP_HIP(hipFree(*a));
+            *a = nullptr;
+        }
+        return TSP_OK;
+    }
+    TSP_REQUIRE(p.n > 0, TSP_ESTATE, "upload particles before the velocities");
+    int rc;
+    if ((rc = upload_permuted(ctx, &p.vx, vx, p.n))) return rc;
+    if ((rc = upload_permuted(ctx, &p.vy, vy, p.n))) return rc;
+    if ((rc = upload_permuted(ctx, &p.vz, vz, p.n))) return rc;
+    TSP_HIP(hipStreamSynchronize(ctx->stream));
+    return TSP_OK;
+}
+
+int tsp_set_line_of_sight(tsp_context *ctx, const float axis[3], const float v_ref[3]) {
+    TSP_REQUIRE(ctx && axis && v_ref, TSP_EINVAL, "NULL argument");
+    double norm2 = 0.0;
+    for (int k = 0; k < 3; ++k) {
+        TSP_REQUIRE(std::isfinite(axis[k]) && std::isfinite(v_ref[k]), TSP_EINVAL, "axis and v_ref must be finite");
+        norm2 += (double)axis[k] * (double)axis[k];
+    }
+    TSP_REQUIRE(std::fabs(std::sqrt(norm2) - 1.0) <= 1e-5, TSP_EINVAL, "axis must have unit length to 1e-5, not %.9g", std::sqrt(norm2));
+    for (int k = 0; k < 3; ++k) {
+        ctx->los[k] = axis[k] == 0.0f ? 0.0f : axis[k];                // (-0 and +0 are one line of sight)
+        ctx->los[3 + k] = v_ref[k] == 0.0f ? 0.0f : v_ref[k];
+    }
+    ctx->have_los = true;
     return TSP_OK;
 }
 
@@ -412,7 +452,7 @@ int tsp_upload_band_magnitudes(tsp_context *ctx, int n_bands, const double *mags
     const unsigned grid = (unsigned)std::min<int64_t>((n + 255) / 256, (int64_t)ctx->cu_count * 16);
     hipLaunchKernelGGL(band_contraction_kernel, dim3(grid), dim3(256), 0, ctx->stream, d_mags.as<double>(), d_w.as<double>(), n_bands, n,
                        ctx->p.perm, ctx->p.r, ctx->p.g, ctx->p.b);
-    ctx->p.wrgb_valid = false;
+    ctx->p.wrgb_source = W_NONE;
     TSP_HIP(hipGetLastError());
     TSP_HIP(hipStreamSynchronize(ctx->stream));
     return TSP_OK;
@@ -523,9 +563,17 @@ static int render_block(tsp_context *ctx, const float *M, float scale_factor, co
                         int n_ranges, int clear, int mode, int flags, double *gpu_ms_out) {
     TSP_REQUIRE(ctx && M, TSP_EINVAL, "NULL argument");
     TSP_REQUIRE(ctx->have_mips, TSP_ESTATE, "tsp_set_kernel_mips must be called before tsp_render");
-    TSP_REQUIRE(mode == TSP_MODE_WEIGHTED || mode == TSP_MODE_DEPTH || mode == TSP_MODE_RGB, TSP_EINVAL, "bad mode %d",
-                mode);
-    if (mode == TSP_MODE_RGB) {
+    TSP_REQUIRE(mode == TSP_MODE_WEIGHTED || mode == TSP_MODE_DEPTH || mode == TSP_MODE_RGB || mode == TSP_MODE_KINEMATIC, TSP_EINVAL,
+                "bad mode %d", mode);
+    const bool kinematic = mode == TSP_MODE_KINEMATIC;
+    if (kinematic) {
+        TSP_REQUIRE(ctx->Ccap == 4, TSP_EINVAL, "TSP_MODE_KINEMATIC needs a 4-channel context");
+        TSP_REQUIRE(!(flags & (TSP_PIPE_GENERIC | TSP_SAMPLE_BILINEAR_MIP0 | TSP_SAMPLE_BILINEAR_MIP)), TSP_EINVAL,
+                    "TSP_MODE_KINEMATIC draws with the three-class pipeline only (flags must be TSP_PIPE_DEFAULT)");
+        TSP_REQUIRE(ctx->p.n == 0 || ctx->p.m, TSP_ESTATE, "mass array not uploaded");
+        TSP_REQUIRE(ctx->p.n == 0 || (ctx->p.vx && ctx->p.vy && ctx->p.vz), TSP_ESTATE, "velocities not uploaded (tsp_upload_velocities)");
+        TSP_REQUIRE(ctx->have_los, TSP_ESTATE, "no line of sight set (tsp_set_line_of_sight)");
+    } else if (mode == TSP_MODE_RGB) {
         TSP_REQUIRE(ctx->Ccap == 4, TSP_EINVAL, "TSP_MODE_RGB needs a 4-channel context");
         TSP_REQUIRE(ctx->p.n == 0 || (ctx->p.r && ctx->p.g && ctx->p.b), TSP_ESTATE, "rgb arrays not uploaded");
     } else {
@@ -533,9 +581,17 @@ static int render_block(tsp_context *ctx, const float *M, float scale_factor, co
     }
     // the active channel count follows the mode (a 4-channel context can also hold 2-channel renders);
     // a block that does not clear must continue in the layout of the image it adds to
-    const int newC = (mode == TSP_MODE_RGB) ? 4 : 2;
+    const int newC = (mode == TSP_MODE_RGB || kinematic) ? 4 : 2;
     TSP_REQUIRE(clear || newC == ctx->C, TSP_ESTATE, "cannot accumulate a %d-channel block onto a %d-channel image",
                 newC, ctx->C);
+    // ... and, of the two 4-channel modes, in the one that started it, along the same line of sight
+    const int source = newC == 4 ? (kinematic ? W_KINEMATIC : W_RGB) : W_NONE;
+    if (!clear && newC == 4 && ctx->image_source != W_NONE) {
+        TSP_REQUIRE(ctx->image_source == source, TSP_ESTATE, "cannot accumulate %s block onto %s image: start with clear = 1",
+                    kinematic ? "a kinematic" : "an rgb", kinematic ? "an rgb" : "a kinematic");
+        TSP_REQUIRE(!kinematic || !memcmp(ctx->image_los, ctx->los, sizeof(ctx->los)), TSP_ESTATE,
+                    "the kinematic image was started along another line of sight (axis or v_ref): start with clear = 1");
+    }
     ctx->C = newC;
     TSP_REQUIRE(n_ranges >= 0 && (n_ranges == 0 || (starts && lens) || (!starts && !lens)), TSP_EINVAL, "bad ranges");
     TSP_HIP(hipSetDevice(ctx->device));
@@ -579,12 +635,16 @@ static int render_block(tsp_context *ctx, const float *M, float scale_factor, co
             // pack must outlive the async copy
             TSP_HIP(hipStreamSynchronize(ctx->stream));
         } else {
-            rc = launch_pipeline(ctx, cam, s.data(), l.data(), nr, total, mode);
+            ctx->kinematic_block = kinematic;      // (the rgb instantiation, fed the kinematic weights: ensure_weights)
+            rc = launch_pipeline(ctx, cam, s.data(), l.data(), nr, total, kinematic ? (int)TSP_MODE_RGB : mode);
+            ctx->kinematic_block = false;
         }
     }
     if (rc) return rc;
     if ((rc = launch_image_convert(ctx, true))) return rc;     // round the float64 master image once
     ctx->image_is_reduced = false;                             // `image` is this rank's partial image again
+    ctx->image_source = source;
+    if (kinematic) memcpy(ctx->image_los, ctx->los, sizeof(ctx->los));
     TSP_HIP(hipEventRecord(ctx->ev[EV_RENDER_END], ctx->stream));
     TSP_HIP(hipStreamSynchronize(ctx->stream));
     float ms = 0.f;
@@ -661,14 +721,52 @@ int tsp_colormap_scalar(tsp_context *ctx, const float *lut_rgba, int n_lut, floa
     return TSP_OK;
 }
 
+// the R * R * 4 float staging that the HDR rgb map and the moment maps share
+static int ensure_outf(tsp_context *ctx) {
+    if (ctx->outf) return TSP_OK;
+    return alloc_group(ctx, {{"outf", (void **)&ctx->outf, (size_t)ctx->R * ctx->R * 4 * sizeof(float)}}, {});
+}
+
+// the moment maps of the kinematic presentation image into ctx->outf (on ctx->stream)
+static int moment_maps(tsp_context *ctx) {
+    TSP_REQUIRE(ctx->image_source == W_KINEMATIC && ctx->C == 4, TSP_ESTATE,
+                "the image is not a kinematic one (render with TSP_MODE_KINEMATIC first)");
+    TSP_HIP(hipSetDevice(ctx->device));
+    if (int rc = ensure_outf(ctx)) return rc;
+    return launch_velocity_moments(ctx, ctx->image, (int64_t)ctx->R * ctx->R, ctx->outf);
+}
+
+int tsp_velocity_moments(tsp_context *ctx, float *maps_out) {
+    TSP_REQUIRE(ctx && maps_out, TSP_EINVAL, "NULL argument");
+    if (int rc = moment_maps(ctx)) return rc;
+    TSP_HIP(hipMemcpyAsync(maps_out, ctx->outf, (size_t)ctx->R * ctx->R * 4 * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    TSP_HIP(hipStreamSynchronize(ctx->stream));
+    return TSP_OK;
+}
+
+int tsp_colormap_moment(tsp_context *ctx, int which, const float *lut_rgba, int n_lut, float vmin, float vmax, int log_scale,
+                        uint8_t *out_rgba8) {
+    TSP_REQUIRE(ctx && out_rgba8, TSP_EINVAL, "NULL argument");
+    TSP_REQUIRE(which == 1 || which == 2, TSP_EINVAL, "which must be 1 (mean) or 2 (sigma), not %d", which);
+    TSP_REQUIRE(lut_rgba && n_lut >= 2 && n_lut <= 65536, TSP_EINVAL, "bad colormap LUT (n=%d)", n_lut);
+    int rc = moment_maps(ctx);
+    if (rc) return rc;
+    if ((rc = ensure_lut(ctx, lut_rgba, n_lut))) return rc;
+    const int64_t npix = (int64_t)ctx->R * ctx->R;
+    // the scalar map, unweighted, reads the first float of every 4-float pixel: the maps shifted by `which` put the moment there
+    if ((rc = launch_colormap_scalar(ctx, ctx->outf + which, npix, 4, ctx->lut, n_lut, vmin, vmax, log_scale, 0, ctx->out8))) return rc;
+    TSP_HIP(hipMemcpyAsync(out_rgba8, ctx->out8, (size_t)npix * 4, hipMemcpyDeviceToHost, ctx->stream));
+    TSP_HIP(hipStreamSynchronize(ctx->stream));
+    return TSP_OK;
+}
+
 int tsp_colormap_rgb(tsp_context *ctx, float vmin, float vmax, float gamma, uint8_t *out_rgba8, float *out_rgba_f32) {
     TSP_REQUIRE(ctx && (out_rgba8 || out_rgba_f32), TSP_EINVAL, "NULL argument");
     TSP_REQUIRE(ctx->C == 4, TSP_EINVAL, "rgb colormap needs a 4-channel image");
     TSP_HIP(hipSetDevice(ctx->device));
     const int64_t npix = (int64_t)ctx->R * ctx->R;
     int rc;
-    if (out_rgba_f32 && !ctx->outf && (rc = alloc_group(ctx, {{"outf", (void **)&ctx->outf, (size_t)npix * 4 * sizeof(float)}}, {})))
-        return rc;
+    if (out_rgba_f32 && (rc = ensure_outf(ctx))) return rc;
     rc = launch_colormap_rgb(ctx, ctx->image, npix, ctx->C, vmin, vmax, gamma, out_rgba8 ? ctx->out8 : nullptr,
                                  out_rgba_f32 ? ctx->outf : nullptr);
     if (rc) return rc;
@@ -964,6 +1062,7 @@ int tsp_render_surface(tsp_context *ctx, const float *M, float scale_factor, flo
     const int rc = render_surface(ctx, cam, density_cut, s.data(), l.data(), (int)s.size(), total, clear, &ms_draw, &ms_resolve);
     if (rc) return rc;
     ctx->C = 2;
+    ctx->image_source = W_NONE;
     ctx->surface_keys = true;
     ctx->image_is_reduced = false;
     ctx->stats.ms_stream = ms_draw;

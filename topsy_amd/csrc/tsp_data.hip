@@ -9,6 +9,7 @@
 #include <algorithm>
 #include <cfloat>
 #include <cmath>
+#include <cstring>
 #include <vector>
 
 #include "tsp_internal.h"
@@ -274,15 +275,26 @@ __global__ __launch_bounds__(256) void weights_kernel(const float *__restrict__ 
 
 int ensure_weights(tsp_context *ctx, bool rgb) {
     Particles &p = ctx->p;
-    if (p.n == 0 || (rgb ? p.wrgb_valid : p.wm_valid)) return TSP_OK;
+    if (p.n == 0) return TSP_OK;
+    // the rgb kernels draw two things: bands (r, g, b) and, in a kinematic block, the velocity moments of one line of sight
+    const int want = ctx->kinematic_block ? W_KINEMATIC : W_RGB;
+    if (rgb ? (p.wrgb_source == want && (want == W_RGB || !memcmp(ctx->w_los, ctx->los, sizeof(ctx->los)))) : p.wm_valid) return TSP_OK;
     int rc;
     const unsigned grid = (unsigned)std::min<int64_t>((p.n + 255) / 256, (int64_t)ctx->cu_count * 32);
     const size_t bytes = (size_t)p.n * sizeof(float);
     if (rgb) {
-        if ((rc = alloc_group(ctx, {{"weights_r", (void **)&p.wr, bytes}, {"weights_g", (void **)&p.wg, bytes}, {"weights_b", (void **)&p.wb, bytes}}, {})))
+        // (a change of mode or of the line of sight alone refills the arrays it finds: they have the size of the particles)
+        const bool refill = p.wrgb_source != W_NONE && p.wr && p.wg && p.wb;
+        p.wrgb_source = W_NONE;
+        if (!refill && (rc = alloc_group(ctx, {{"weights_r", (void **)&p.wr, bytes}, {"weights_g", (void **)&p.wg, bytes}, {"weights_b", (void **)&p.wb, bytes}}, {})))
             return rc;
-        hipLaunchKernelGGL(weights_kernel, dim3(grid), dim3(256), 0, ctx->stream, p.h, p.r, p.g, p.b, p.n, p.wr, p.wg, p.wb);
-        p.wrgb_valid = true;
+        if (want == W_KINEMATIC) {
+            if ((rc = launch_kinematic_weights(ctx))) return rc;
+            memcpy(ctx->w_los, ctx->los, sizeof(ctx->los));
+        } else {
+            hipLaunchKernelGGL(weights_kernel, dim3(grid), dim3(256), 0, ctx->stream, p.h, p.r, p.g, p.b, p.n, p.wr, p.wg, p.wb);
+        }
+        p.wrgb_source = want;
     } else {
         if ((rc = alloc_group(ctx, {{"weights_m", (void **)&p.wm, bytes}}, {}))) return rc;
         hipLaunchKernelGGL(weights_kernel, dim3(grid), dim3(256), 0, ctx->stream, p.h, p.m, (const float *)nullptr, (const float *)nullptr, p.n,
@@ -359,7 +371,8 @@ int reorder_spatial(tsp_context *ctx, int n_strata, uint64_t seed, int64_t *perm
     Particles &p = ctx->p;
     const int64_t n = p.n;
     ctx->ws.bounds_valid = false;
-    p.wm_valid = p.wrgb_valid = false;       // (recomputed in the new order by the next render)
+    p.wm_valid = false;                      // (recomputed in the new order by the next render)
+    p.wrgb_source = W_NONE;
     hipStream_t st = ctx->stream;
     float lo[3], inv[3];
     int wide = 0;              // bit k: axis k is keyed in float64 (its extent overflows float32)
@@ -463,7 +476,7 @@ int reorder_spatial(tsp_context *ctx, int n_strata, uint64_t seed, int64_t *perm
     DeviceScratch spare;
     TSP_SCRATCH_ALLOC(ctx, SITE("reorder_spare"), spare, (size_t)n * 4);
     ctx->surface_keys = false;         // (the keys hold indices of the old order)
-    float **arrs[] = {&p.x, &p.y, &p.z, &p.h, &p.m, &p.q, &p.r, &p.g, &p.b};
+    float **arrs[] = {&p.x, &p.y, &p.z, &p.h, &p.m, &p.q, &p.r, &p.g, &p.b, &p.vx, &p.vy, &p.vz};
     for (float **a : arrs) {
         if (!*a) continue;
         hipLaunchKernelGGL(gather_f32_kernel, dim3(4096), dim3(256), 0, st, *a, order.as<uint32_t>(), spare.as<float>(), n);

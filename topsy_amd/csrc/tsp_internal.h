@@ -39,14 +39,19 @@ struct Particles {
     float *x = nullptr, *y = nullptr, *z = nullptr, *h = nullptr, *m = nullptr;
     float *q = nullptr;                      // nullptr -> density render (q = 0)
     float *r = nullptr, *g = nullptr, *b = nullptr;
+    float *vx = nullptr, *vy = nullptr, *vz = nullptr;   // velocities (tsp_upload_velocities): read by the kinematic weight pass only
     uint32_t *perm = nullptr;                // new -> old index after tsp_reorder_spatial (else nullptr)
     // camera-independent vertex weights (sph.wgsl:76-83 `mass / (h*h)`, :69-73 `rgb / (h*h)`), formed once per upload by
     // ensure_weights() with the float32 operations the shader performs per vertex and frame: what kernel S streams
     // instead of m (r, g, b) -- the same bytes per particle, no division per particle and frame
     float *wm = nullptr;
     float *wr = nullptr, *wg = nullptr, *wb = nullptr;
-    bool wm_valid = false, wrgb_valid = false;   // cleared whenever h / m / rgb change (upload, generate, reorder)
+    bool wm_valid = false;                   // cleared whenever h / m change (upload, generate, reorder)
+    // what wr / wg / wb hold: nothing valid, (r, g, b) / h^2, or the kinematic weights (m, m u, m u^2) / h^2 of the line of sight
+    // tsp_context::w_los (tsp_kinematics.hip).  W_NONE whenever h / m / rgb / velocities change (upload, generate, reorder)
+    int wrgb_source = 0;
 };
+enum { W_NONE = 0, W_RGB = 1, W_KINEMATIC = 2 };     // Particles::wrgb_source, tsp_context::image_source
 
 // Bounds of every block of BOUNDS_BLOCK consecutive particles (view culling of whole chunks, kernel S): two float4 per block,
 // (xmin, ymin, zmin, hmax) and (xmax, ymax, zmax, -).  NaN coordinates are ignored (such a particle draws nothing).
@@ -181,6 +186,13 @@ struct tsp_context {
     void *comm = nullptr;
     int n_ranks = 1, rank = 0;
     bool image_is_reduced = false;    // `image` already holds the cross-rank sum of the current frame (tsp_comm_reduce_image)
+    // kinematic maps (TSP_MODE_KINEMATIC, tsp_kinematics.hip).  A line of sight is six floats: the unit axis, then v_ref
+    bool have_los = false;
+    float los[6] = {};                // tsp_set_line_of_sight: what the next kinematic block draws along
+    float w_los[6] = {};              // what p.wr / wg / wb were formed with (while p.wrgb_source == W_KINEMATIC)
+    int image_source = tsp::W_NONE;   // which 4-channel mode started the image (W_NONE: a 2-channel render, or none yet)
+    float image_los[6] = {};          // ... and, for W_KINEMATIC, along which line of sight
+    bool kinematic_block = false;     // set by tsp_render around a kinematic block: the rgb pipeline then asks for the kinematic weights
 };
 
 namespace tsp {
@@ -255,7 +267,12 @@ int launch_colormap_bivariate(tsp_context *ctx, const float *d_img, int64_t npix
 int generate_synthetic(tsp_context *ctx, int64_t n_total, int64_t first, int64_t count, uint64_t seed,
                        float h_cap, int with_quantity, int with_rgb);
 int reorder_spatial(tsp_context *ctx, int n_strata, uint64_t seed, int64_t *perm_out);
-int ensure_weights(tsp_context *ctx, bool rgb);    // (re)computes p.wm or p.wr / wg / wb on ctx->stream when the particles changed
+// (re)computes p.wm or p.wr / wg / wb on ctx->stream when the particles changed; rgb: also when wr / wg / wb hold the weights of the
+// other 4-channel mode (ctx->kinematic_block selects which are wanted) or of another line of sight
+int ensure_weights(tsp_context *ctx, bool rgb);
+// tsp_kinematics.hip: the kinematic weights into p.wr / wg / wb (on ctx->stream) and the per-pixel moment maps of a kinematic image
+int launch_kinematic_weights(tsp_context *ctx);
+int launch_velocity_moments(tsp_context *ctx, const float *d_img, int64_t npix, float *d_maps);
 int ensure_block_bounds(tsp_context *ctx);     // (re)computes ws.block_bounds on ctx->stream when the particles changed
 int measure_read_bandwidth(tsp_context *ctx, int64_t bytes, int iters, double *gbps_out);
 int launch_image_convert(tsp_context *ctx, bool to_float);

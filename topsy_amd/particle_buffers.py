@@ -24,6 +24,7 @@ class ParticleBuffers:
         self.quantity_name = None
         self._quantity_on_device = _UNSET
         self._have_rgb = False
+        self._have_velocities = False
         self._last_ranges = (None, None)
         self._max_draw_calls_per_buffer = max_draw_calls_per_buffer
         self.block_boundaries = None          # stratum offsets when the library reordered the particles
@@ -117,6 +118,20 @@ class ParticleBuffers:
             rgb = np.where(np.isnan(rgb), np.float32(0.0), rgb)      # reference loader.py:120
             self.context.upload_rgb(rgb[:, 0], rgb[:, 1], rgb[:, 2])
             self._have_rgb = True
+
+    def ensure_velocities(self):
+        """The loader's velocities (get_velocities(): (n, 3) in the loader's order), uploaded once: what sph.KinematicSPH draws."""
+        if self._have_velocities:
+            return
+        vel = getattr(self._loader, "get_velocities", lambda: None)()
+        if vel is None:
+            raise ValueError(f"{type(self._loader).__name__} has no velocities: the kinematic maps need from_arrays(..., vel=vel)")
+        if not hasattr(self.context, "upload_velocities"):
+            raise NotImplementedError("the kinematic maps run on one GPU: this context shards its particles over several")
+        logger.info("Uploading velocity arrays")
+        vel = np.asarray(vel, dtype=np.float32)
+        self.context.upload_velocities(vel[:, 0], vel[:, 1], vel[:, 2])
+        self._have_velocities = True
 
     # -- per-block ranges (update_particle_ranges, particle_buffers.py:76-82) -----------------
     def update_particle_ranges(self, particle_mins, particle_lens):

@@ -189,6 +189,31 @@ class RGBSPH(SPH):
         self._visualizer.particle_buffers.ensure_rgb()
 
 
+class KinematicSPH(SPH):
+    """Line-of-sight velocity moments of what the view shows: channels (S, A, B, n) = the sums of k m / h^2, k m u / h^2 and
+    k m u^2 / h^2 and the fragment count, u = (v - v_ref) . (the view axis, rotation_matrix[2]) -- MODE_KINEMATIC, drawn by the
+    rgb kernels (include/topsy_splat.h "Kinematic maps").  Progressive blocks and refinement as RGBSPH; a refinement continues
+    along the line of sight that started the frame (the library refuses another)."""
+    render_format = "rgba32float"
+    _buffer_name = "velocities"
+    _nchannels_input = 5
+    _nchannels_output = 4
+    _mode = _native.MODE_KINEMATIC
+
+    def __init__(self, visualizer, render_resolution, wrapping=False, share_render_progression=None):
+        super().__init__(visualizer, render_resolution, wrapping, share_render_progression)
+        self.v_ref = np.zeros(3)       # subtracted from the velocities before the moments are formed
+
+    def line_of_sight(self):
+        """The unit view axis: the third row of rotation_matrix, normalised in float64."""
+        axis = np.asarray(self.rotation_matrix, dtype=np.float64)[2]
+        return axis / np.sqrt(axis @ axis)
+
+    def _prepare_buffers(self):
+        self._visualizer.particle_buffers.ensure_velocities()
+        self._context.set_line_of_sight(self.line_of_sight(), self.v_ref)
+
+
 class DepthSPH(SPH):
     """Channel 1 carries clip-space z instead of the quantity (reference sph.py:443-446)."""
     _mode = _native.MODE_DEPTH
