@@ -99,7 +99,9 @@ const char *tsp_last_error(void);
  * 116: new entry point tsp_radial_profile and the structs tsp_profile_spec / tsp_profile_info (binned shell and annulus sums: radial
  * profiles, the virial radius); nothing else changed.
  * 117: kinematic maps: TSP_MODE_KINEMATIC and the entry points tsp_upload_velocities, tsp_set_line_of_sight, tsp_velocity_moments,
- * tsp_colormap_moment; no struct changed, nothing else changed. */
+ * tsp_colormap_moment; no struct changed, nothing else changed.
+ * 118: new entry point tsp_render_undo; tsp_group_render draws a block on every member or on none (it used to leave the block in
+ * the accumulators of the members that had succeeded); no struct changed, nothing else changed. */
 int tsp_version(void);
 int tsp_stats_size(void);
 
@@ -206,6 +208,17 @@ int64_t tsp_num_particles(tsp_context *ctx);
  * all: on any error return the accumulator, the image, the channel layout and tsp_stats are as the call found them. */
 int tsp_render(tsp_context *ctx, const float *M, float scale_factor, const int64_t *starts,
                const int64_t *lens, int n_ranges, int clear, int mode, int flags, double *gpu_ms_out);
+
+/* Takes the last tsp_render back: for a driver that runs one block on several contexts and must leave it drawn on all of them or
+ * on none (tsp_group_render does this itself).  Valid only while tsp_render is the last call that changed this context's image
+ * -- no tsp_write_image, tsp_set_reduced_image, tsp_comm_reduce_image, tsp_tile_periodic, tsp_render_surface, upload or reorder
+ * since, and not when that tsp_render replaced a surface image; otherwise TSP_ESTATE, and nothing changes.
+ *   - After a tsp_render that succeeded: the accumulator, the channel layout, tsp_stats and what the image remembers of its mode
+ *     (rgb / kinematic, the line of sight) are as that call found them.
+ *   - After a tsp_render that failed there is nothing to put back (it draws whole or not at all).
+ * In both cases the float32 image is formed again from the accumulator and the context counts as not reduced, so the driver's
+ * next reduce sums every member's partial image anew.  A second call returns TSP_ESTATE.  Allocates nothing. */
+int tsp_render_undo(tsp_context *ctx);
 
 /* Read the render target (R*R*C float32).  SPH._get_image_unscaled, src/topsy/sph.py:127-140. */
 int tsp_read_image(tsp_context *ctx, float *out);
@@ -781,7 +794,16 @@ int tsp_set_reduced_image(tsp_context *ctx, const float *sum);
  * frame (tsp_read_image, tsp_colormap_*, tsp_content_*, tsp_tile_periodic) is called on tsp_group_context(group, 0) after
  * tsp_group_end_frame; per-shard state can be inspected through tsp_group_context(group, g).  The reduce contract of
  * tsp_comm_reduce_image holds: end_frame reduces at most once per rendered frame, and a later tsp_group_render -- a REFINE
- * block with clear = 0 included -- continues from every shard's own float64 accumulator.  Calls on one group must be
+ * block with clear = 0 included -- continues from every shard's own float64 accumulator.  A block draws on every member or on
+ * none: when one member's tsp_render fails, tsp_group_render puts the members that succeeded back as it found them
+ * (tsp_render_undo) before it returns that member's error ("context g (device d): ..."), every member's float32 image is its
+ * own partial image again, and the next tsp_group_end_frame sums them anew -- so a retried clear = 0 block is counted once.
+ * Exceptions, both about a member touched through tsp_group_context: one whose tsp_render is refused before it touches
+ * anything -- its accumulator holds the keys of tsp_render_surface and the block has clear = 0, or its device cannot be
+ * selected -- has nothing to take back and is left as it is, reduced state included (if it is context 0 and still presents a
+ * reduced frame, that frame stands and is not summed again); and one on which the block replaced a surface image keeps the
+ * block, because tsp_render_undo does not restore surface keys.
+ * Calls on one group must be
  * serialised by the caller.  tsp_group_get_stats: counters summed over the shards, times of the slowest shard. */
 typedef struct tsp_group tsp_group;
 int tsp_group_create(int n_devices, const int *device_ids, int resolution, int n_channels, tsp_group **out);

@@ -31,8 +31,26 @@ class FakeContext:
         self.m = None if mass is None else np.ascontiguousarray(mass, dtype=np.float32)
         self.n = len(self.x)
 
+    def _refuse_without_particles(self, what):
+        # tsp_upload_quantity / _rgb / _band_magnitudes: TSP_ESTATE while no particle is resident (a NumPy empty array still has
+        # a non-NULL data pointer, so a zero-length upload is refused like any other)
+        if self.n == 0:
+            from topsy_amd import _native
+            raise _native.BackendError(f"libtopsy_splat error -3: upload particles before {what}")
+
     def upload_quantity(self, q):
+        if q is not None:
+            self._refuse_without_particles("the quantity")
         self.q = None if q is None else np.ascontiguousarray(q, dtype=np.float32)
+
+    def upload_rgb(self, r, g, b):
+        self._refuse_without_particles("rgb")
+        self.rgb = np.stack([np.asarray(v, dtype=np.float32) for v in (r, g, b)], axis=1)
+
+    def upload_band_magnitudes(self, mags, weights):
+        self._refuse_without_particles("the band magnitudes")
+        assert mags.flags["C_CONTIGUOUS"] and mags.shape[1] == self.n
+        self.mags = mags.copy()
 
     def reorder_spatial(self, n_strata=1, seed=1337, want_permutation=False):
         self.reordered = True
@@ -54,8 +72,27 @@ class FakeContext:
     def set_option(self, name, value):
         pass
 
+    fail_render = None        # an exception the next render raises instead of drawing (a failed block changes nothing)
+
+    def render_undo(self):
+        self.n_undos = getattr(self, "n_undos", 0) + 1
+        if not self.undoable:
+            from topsy_amd import _native
+            raise _native.BackendError("libtopsy_splat error -3: nothing to undo")
+        self.undoable = False
+        self.reduced = False
+        if self.image_entry is not None:
+            self.image = self.image_entry
+
+    undoable, image_entry = False, None
+
     def render(self, matrix, scale_factor, starts=None, lens=None, clear=True, mode=0, flags=0):
         from oracle import oracle_c
+        if self.fail_render is not None:
+            e, self.fail_render = self.fail_render, None
+            self.undoable, self.image_entry = True, None
+            raise e
+        self.undoable, self.image_entry = True, self.image.copy()
         if clear:
             self.image[:] = 0
         if starts is None:
@@ -311,3 +348,148 @@ def test_cell_sorted_loader_is_sharded_interleaved_and_renders_the_same_image(fa
     np.testing.assert_allclose(got[..., 0], want[..., 0], rtol=1e-5, atol=0)
     plain = _Vis(n, R, [0, 1, 2, 3], with_cells=False)
     assert plain.particle_buffers.context.assignment == "contiguous"
+
+
+def _few_particles(n):
+    rs = np.random.RandomState(n)
+    x = np.arange(n, dtype=np.float32)
+    return x, rs.normal(size=n).astype(np.float32), rs.uniform(size=(3, n)).astype(np.float32), rs.uniform(2.0, 9.0, size=(3, n))
+
+
+@pytest.mark.parametrize("assignment,block", [("contiguous", 4096), ("interleaved", 4096), ("interleaved", 2)])
+@pytest.mark.parametrize("n", [0, 1, 2, 3, 4, 5])
+def test_uploads_with_empty_shards(fake_backend, assignment, block, n):
+    """Fewer particles than members (contiguous), or no more than one interleave block (every member past the first is empty):
+    the member contexts refuse an upload before particles are resident, as the library does, so the driver must leave the empty
+    ones out -- and every particle's values must still arrive at the member that holds it."""
+    from topsy_amd import multigpu
+    G = 4
+    ctx = multigpu.MultiGpuContext(16, 4, list(range(G)), assignment=assignment, interleave_block=block)
+    x, q, rgb, mags = _few_particles(n)
+    ctx.set_kernel_mips(np.zeros(5440, dtype=np.float32))
+    ctx.upload_particles(x, x, x, np.ones(n, np.float32), np.ones(n, np.float32))
+    sizes = [c.n for c in ctx.contexts]
+    assert sum(sizes) == n == ctx.num_particles and (0 in sizes or n >= G)
+    if assignment == "interleaved" and block == 4096:
+        assert sizes == [n, 0, 0, 0]
+    ctx.upload_quantity(q)
+    ctx.upload_rgb(rgb[0], rgb[1], rgb[2])
+    ctx.upload_band_magnitudes(mags, np.eye(3))
+    for c in ctx.contexts:
+        if c.n == 0:
+            assert c.q is None and not hasattr(c, "rgb") and not hasattr(c, "mags")
+            continue
+        own = c.x.astype(np.int64)
+        assert np.array_equal(c.q, q[own]) and np.array_equal(c.rgb, rgb[:, own].T) and np.array_equal(c.mags, mags[:, own])
+    ctx.upload_quantity(None)                                  # dropping the quantity reaches every member, empty or not
+    assert all(c.q is None for c in ctx.contexts)
+    perm = ctx.reorder_spatial(3, 1, want_permutation=True)
+    assert perm.dtype == np.int64 and np.array_equal(np.sort(perm), np.arange(n))
+    assert all(c.reordered == (c.n > 0) for c in ctx.contexts)
+    offs = ctx.strata_offsets()
+    if n:
+        assert offs[0] == 0 and offs[-1] == n and (np.diff(offs) >= 0).all()
+    assert ctx.cell_layouts() == []
+    back = ctx.download_particles(("x",))
+    assert np.array_equal(np.sort(back["x"]), x)
+    ctx.render(np.eye(4, dtype=np.float32), 1.0, [0], [np.iinfo(np.int64).max], clear=True)
+    assert sum(int(c.last_ranges[1].sum()) for c in ctx.contexts) == n
+    ctx.close()
+
+
+@pytest.mark.parametrize("devices", [[0, 0, 0], [0, 1, 2]], ids=["host", "rccl"])
+@pytest.mark.parametrize("failing", [0, 1, 2])
+def test_failed_block_is_undone_on_every_member(fake_backend, devices, failing):
+    """The rollback choreography of MultiGpuContext.render: member `failing` raises, every other member then gets exactly one
+    undo, the frame is marked for a new reduce, the exception is the failing member's and names it -- and the retried block
+    leaves the image a run without the failure leaves."""
+    from topsy_amd import _native, kernel_lut, multigpu
+    n, R = 600, 32
+    rs = np.random.RandomState(4)
+    pos = (rs.normal(size=(n, 3)) * 20.0).astype(np.float32)
+    h = rs.uniform(1.0, 8.0, n).astype(np.float32)
+    m = rs.uniform(0.5, 2.0, n).astype(np.float32)
+    M = np.eye(4, dtype=np.float32)
+    M[:3, :3] /= 60.0
+    M[2, :] = [0.0, 0.0, 0.5 / 60.0, 0.5]
+
+    def frames(fail):
+        ctx = multigpu.MultiGpuContext(R, 2, devices)
+        ctx.set_kernel_mips(kernel_lut.kernel_mips())
+        ctx.upload_particles(pos[:, 0], pos[:, 1], pos[:, 2], h, m)
+        first = [0, 200, 400], [100, 100, 100]
+        second = [100, 300, 500], [100, 100, 100]
+        ctx.render(M, 1.0 / 60.0, *first, clear=True)
+        before = ctx.read_image().copy()
+        partial = [c.image.copy() for c in ctx.contexts]
+        if fail:
+            boom = _native.BackendError("libtopsy_splat error -2: injected")
+            ctx.contexts[failing].fail_render = boom
+            assert not ctx._needs_reduce
+            with pytest.raises(_native.BackendError, match=f"context {failing} .*injected") as info:
+                ctx.render(M, 1.0 / 60.0, *second, clear=False)
+            assert info.value.__cause__ is boom
+            assert ctx._needs_reduce
+            for g, c in enumerate(ctx.contexts):
+                assert c.n_undos == 1, "every member is put back exactly once (the failing one re-forms its partial image)"
+                assert np.array_equal(c.image, partial[g]) and not c.reduced
+            assert np.array_equal(ctx.read_image(), before)           # summed anew: the frame before the failed call
+        ctx.render(M, 1.0 / 60.0, *second, clear=False)
+        out = ctx.read_image().copy()
+        ctx.close()
+        return out
+
+    assert np.array_equal(frames(True), frames(False))
+    # A call that never reaches the library on a member (the binding rejects an argument) must not take back that member's
+    # EARLIER block -- its undo state still belongs to it -- and must not ask for a reduce that cannot succeed: after a frame
+    # that was already reduced, the root keeps presenting that frame unless the root itself was put back.
+    def reduced_frame():
+        ctx = multigpu.MultiGpuContext(R, 2, devices)
+        ctx.set_kernel_mips(kernel_lut.kernel_mips())
+        ctx.upload_particles(pos[:, 0], pos[:, 1], pos[:, 2], h, m)
+        ctx.render(M, 1.0 / 60.0, [0], [n], clear=True)
+        return ctx, ctx.read_image().copy()
+
+    for who in ("all", "one"):
+        ctx, frame = reduced_frame()
+        assert not ctx._needs_reduce
+        for g, c in enumerate(ctx.contexts):
+            if who == "all" or g == failing:
+                c.fail_render = ValueError("matrix has 15 elements, expected 16")
+        with pytest.raises(ValueError, match="15 elements"):
+            ctx.render(M, 1.0 / 60.0, [0], [n], clear=False)
+        reached = [who == "one" and g != failing for g in range(3)]
+        assert [getattr(c, "n_undos", 0) for c in ctx.contexts] == [int(r) for r in reached]
+        assert ctx._needs_reduce == reached[0]
+        if who == "one" and failing != 0 and ctx.collective == "rccl":
+            # the root was put back, member `failing` still counts as reduced: the collective would wait for it for ever
+            with pytest.raises(_native.BackendError, match=rf"contexts \[{failing}\] could not be put back"):
+                ctx.read_image()
+            assert ctx._needs_reduce
+        else:
+            assert np.array_equal(ctx.read_image(), frame), "the frame before the failed call"
+        ctx.render(M, 1.0 / 60.0, [0], [n], clear=True)                  # ... and a render that succeeds presents again
+        assert np.array_equal(ctx.read_image(), frame)
+        ctx.close()
+    # a wrong argument is refused by the driver itself, before any member is touched
+    ctx, frame = reduced_frame()
+    with pytest.raises(ValueError):
+        ctx.render(np.eye(4, dtype=np.float32).ravel()[:15], 1.0 / 60.0, [0], [n], clear=False)
+    with pytest.raises(ValueError, match="equal length"):
+        ctx.render(M, 1.0 / 60.0, [0, 5], [n], clear=False)
+    assert all(c.n_renders == 1 and getattr(c, "n_undos", 0) == 0 for c in ctx.contexts) and not ctx._needs_reduce
+    assert np.array_equal(ctx.read_image(), frame)
+    ctx.close()
+
+    # a member that drew the block but cannot be put back: the failing member's error stays, the other is appended, every
+    # member's channel layout is the one before the call
+    ctx, frame = reduced_frame()
+    other = (failing + 1) % 3
+    ctx.contexts[failing].fail_render = _native.BackendError("libtopsy_splat error -2: injected")
+    ctx.contexts[other].render_undo = lambda: (_ for _ in ()).throw(_native.BackendError("libtopsy_splat error -5: hipMemcpyAsync failed"))
+    for c in ctx.contexts:
+        c.active_channels = 2
+    with pytest.raises(_native.BackendError, match=rf"context {failing} .*injected; and context {other} could not be put back .*hipMemcpyAsync"):
+        ctx.render(M, 1.0 / 60.0, [0], [n], clear=False)
+    assert all(c.active_channels == 2 for c in ctx.contexts)
+    ctx.close()

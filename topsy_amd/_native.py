@@ -143,6 +143,7 @@ SIGNATURES = {
     "tsp_num_particles": (ctypes.c_int64, [_ctx]),
     "tsp_render": (ctypes.c_int, [_ctx, _fp, ctypes.c_float, _i64p, _i64p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                   ctypes.c_int, ctypes.POINTER(ctypes.c_double)]),
+    "tsp_render_undo": (ctypes.c_int, [_ctx]),
     "tsp_read_image": (ctypes.c_int, [_ctx, _fp]),
     "tsp_write_image": (ctypes.c_int, [_ctx, _fp]),
     "tsp_colormap_scalar": (ctypes.c_int, [_ctx, _fp, ctypes.c_int, ctypes.c_float, ctypes.c_float, ctypes.c_int,
@@ -432,6 +433,11 @@ class Context:
                                     int(flags), ctypes.byref(ms)))
         self.active_channels = 4 if mode in (MODE_RGB, MODE_KINEMATIC) else 2
         return ms.value
+
+    def render_undo(self):
+        """Take the last render() back (tsp_render_undo): what a driver of several contexts calls on every member when a block
+        failed on one of them.  The caller restores `active_channels` (the library's layout is the one before that render)."""
+        _check(self._lib.tsp_render_undo(self._h))
 
     def read_image(self):
         out = np.empty((self.resolution, self.resolution, self.active_channels), dtype=np.float32)

@@ -172,6 +172,7 @@ static void free_particles(tsp_context *ctx) {
     p.n = 0;
     ctx->ws.bounds_valid = false;
     ctx->surface_keys = false;         // the keys name particles that are gone: a surface block must start with clear = 1
+    ctx->forget_render_undo();
     ctx->strata_offsets.clear();
     ctx->cell_offsets.clear();
     ctx->cell_bits = 0;
@@ -220,7 +221,7 @@ using namespace tsp;
 extern "C" {
 
 const char *tsp_last_error(void) { return g_err; }
-int tsp_version(void) { return 117; }     // 117: kinematic maps (tsp_upload_velocities, tsp_set_line_of_sight, TSP_MODE_KINEMATIC, tsp_velocity_moments, tsp_colormap_moment); 116: tsp_radial_profile; 115: tsp_sphere_moments; 114: tsp_fof_groups; 113: tsp_shrink_sphere_center; 112: tsp_present_surface, tsp_present_surface_yuv420; 111: tsp_content_neg_inf; 110: tsp_sph_sum; 109: tsp_present_yuv420; 108: tsp_present; 107: surface rendering; 106: tsp_smoothing_lengths; 101: tsp_stats gained ms_mega, n_mega (16 bytes); 102: the per-kernel fragment counts (32 bytes); 103: n_chunk_culled (8 bytes); 104: matrix-core / kernel-I options removed; 105: kernel M's options removed (kernel G draws the mid footprints)
+int tsp_version(void) { return 118; }     // 118: tsp_render_undo, tsp_group_render all-or-nothing across the members; 117: kinematic maps (tsp_upload_velocities, tsp_set_line_of_sight, TSP_MODE_KINEMATIC, tsp_velocity_moments, tsp_colormap_moment); 116: tsp_radial_profile; 115: tsp_sphere_moments; 114: tsp_fof_groups; 113: tsp_shrink_sphere_center; 112: tsp_present_surface, tsp_present_surface_yuv420; 111: tsp_content_neg_inf; 110: tsp_sph_sum; 109: tsp_present_yuv420; 108: tsp_present; 107: surface rendering; 106: tsp_smoothing_lengths; 101: tsp_stats gained ms_mega, n_mega (16 bytes); 102: the per-kernel fragment counts (32 bytes); 103: n_chunk_culled (8 bytes); 104: matrix-core / kernel-I options removed; 105: kernel M's options removed (kernel G draws the mid footprints)
 int tsp_stats_size(void) { return (int)sizeof(tsp_stats); }
 
 int tsp_device_count(void) {
@@ -531,17 +532,24 @@ static int render_block(tsp_context *ctx, const float *M, float scale_factor, co
 int tsp_render(tsp_context *ctx, const float *M, float scale_factor, const int64_t *starts, const int64_t *lens,
                int n_ranges, int clear, int mode, int flags, double *gpu_ms_out) {
     TSP_REQUIRE(ctx && M, TSP_EINVAL, "NULL argument");
+    ctx->forget_render_undo();                           // (image64_entry is about to be overwritten)
     TSP_REQUIRE(clear || !ctx->surface_keys, TSP_ESTATE, "the accumulator holds the keys of tsp_render_surface: start with clear = 1");
     TSP_HIP(hipSetDevice(ctx->device));
     const size_t bytes = (size_t)ctx->R * ctx->R * ctx->Ccap * sizeof(double);
     if (!ctx->image64_entry) {
         const int rc = alloc_group(ctx, {{"image64_entry", (void **)&ctx->image64_entry, bytes}}, {});
-        if (rc) return rc;
+        if (rc) {
+            if (!ctx->surface_keys) ctx->undo.kind = 2;      // (nothing was touched)
+            return rc;
+        }
     }
     TSP_HIP(hipMemcpyAsync(ctx->image64_entry, ctx->image64, bytes, hipMemcpyDeviceToDevice, ctx->stream));
     const int C_entry = ctx->C;
     const tsp_stats stats_entry = ctx->stats;
     const int64_t culled_entry = ctx->chunk_culled_particles;
+    const int source_entry = ctx->image_source;
+    float los_entry[6];
+    memcpy(los_entry, ctx->image_los, sizeof(los_entry));
     const int rc = render_block(ctx, M, scale_factor, starts, lens, n_ranges, clear, mode, flags, gpu_ms_out);
     if (rc != TSP_OK) {
         const std::string why = tsp_last_error();        // (the restore below must not replace the reason of the failure)
@@ -553,10 +561,43 @@ int tsp_render(tsp_context *ctx, const float *M, float scale_factor, const int64
         const hipError_t e = e0 != hipSuccess ? e0 : (e1 != hipSuccess ? e1 : e2);
         if (e != hipSuccess) set_error("%s; and the accumulator could not be restored (%s)", why.c_str(), hipGetErrorString(e));
         else set_error("%s", why.c_str());
+        if (e == hipSuccess && !ctx->surface_keys) ctx->undo.kind = 2;
     } else {
+        // what tsp_render_undo puts back (not over a surface image: its keys cannot be re-formed into the presentation image)
+        if (!ctx->surface_keys) {
+            ctx->undo.kind = 1;
+            ctx->undo.C = C_entry; ctx->undo.stats = stats_entry; ctx->undo.chunk_culled_particles = culled_entry;
+            ctx->undo.image_source = source_entry;
+            memcpy(ctx->undo.image_los, los_entry, sizeof(los_entry));
+        }
         ctx->surface_keys = false;
     }
     return rc;
+}
+
+// Takes back the last tsp_render: valid while no other call has changed the image since.  After a block that drew, the
+// accumulator (image64_entry still holds it), the channel layout, the statistics and the image tags are put back as that call
+// found them; after a block that failed, tsp_render has done so itself.  Either way the float32 presentation image is formed
+// again from the accumulator and the context is marked not reduced: the state in which a device group sums its members again.
+// Allocates nothing.
+int tsp_render_undo(tsp_context *ctx) {
+    TSP_REQUIRE(ctx, TSP_EINVAL, "NULL context");
+    TSP_REQUIRE(ctx->undo.kind != 0, TSP_ESTATE, "nothing to undo: the last call that changed the image was not tsp_render");
+    TSP_HIP(hipSetDevice(ctx->device));
+    if (ctx->undo.kind == 1) {
+        const size_t bytes = (size_t)ctx->R * ctx->R * ctx->Ccap * sizeof(double);
+        if (ctx->stream2) TSP_HIP(hipStreamSynchronize(ctx->stream2));
+        TSP_HIP(hipMemcpyAsync(ctx->image64, ctx->image64_entry, bytes, hipMemcpyDeviceToDevice, ctx->stream));
+        ctx->C = ctx->undo.C; ctx->stats = ctx->undo.stats; ctx->chunk_culled_particles = ctx->undo.chunk_culled_particles;
+        ctx->image_source = ctx->undo.image_source;
+        memcpy(ctx->image_los, ctx->undo.image_los, sizeof(ctx->image_los));
+    }
+    ctx->forget_render_undo();
+    const int rc = launch_image_convert(ctx, true);
+    if (rc) return rc;
+    ctx->image_is_reduced = false;
+    TSP_HIP(hipStreamSynchronize(ctx->stream));
+    return TSP_OK;
 }
 
 static int render_block(tsp_context *ctx, const float *M, float scale_factor, const int64_t *starts, const int64_t *lens,
@@ -680,6 +721,7 @@ int tsp_write_image(tsp_context *ctx, const float *in) {
     TSP_HIP(hipMemcpy(ctx->image, in, (size_t)ctx->R * ctx->R * ctx->C * sizeof(float), hipMemcpyHostToDevice));
     int rc = launch_image_convert(ctx, false);                 // keep the master copy consistent
     if (rc) return rc;
+    ctx->forget_render_undo();
     ctx->image_is_reduced = false;
     ctx->surface_keys = false;
     TSP_HIP(hipStreamSynchronize(ctx->stream));
@@ -693,6 +735,7 @@ int tsp_set_reduced_image(tsp_context *ctx, const float *sum) {
     TSP_REQUIRE(!ctx->image_is_reduced, TSP_ESTATE, "the render target was already reduced for this frame (call tsp_render before reducing again)");
     TSP_HIP(hipSetDevice(ctx->device));
     TSP_HIP(hipMemcpy(ctx->image, sum, (size_t)ctx->R * ctx->R * ctx->C * sizeof(float), hipMemcpyHostToDevice));
+    ctx->forget_render_undo();
     ctx->image_is_reduced = true;
     return TSP_OK;
 }
@@ -1053,6 +1096,7 @@ int tsp_render_surface(tsp_context *ctx, const float *M, float scale_factor, flo
     TSP_REQUIRE(n_ranges >= 0 && (n_ranges == 0 || (starts && lens) || (!starts && !lens)), TSP_EINVAL, "bad ranges");
     TSP_REQUIRE(ctx->have_sphere_mips, TSP_ESTATE, "tsp_set_sphere_mips must be called before tsp_render_surface");
     TSP_REQUIRE(clear || ctx->surface_keys, TSP_ESTATE, "clear = 0 continues a surface image; the accumulator holds none");
+    ctx->forget_render_undo();
     TSP_HIP(hipSetDevice(ctx->device));
     std::vector<int64_t> s, l;
     int64_t total = 0;
@@ -1216,6 +1260,7 @@ int tsp_set_option(tsp_context *ctx, const char *name, int64_t value) {
     if (!strcmp(name, "active_channels")) {   // layout tsp_write_image / the colormap calls assume
         TSP_REQUIRE((value == 2 || value == 4) && value <= ctx->Ccap, TSP_EINVAL, "bad channel count %lld", (long long)value);
         ctx->C = (int)value;
+        ctx->forget_render_undo();
         return TSP_OK;
     }
     set_error("unknown option '%s'", name);

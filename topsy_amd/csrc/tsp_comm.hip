@@ -113,6 +113,7 @@ int tsp_comm_reduce_image(tsp_context *ctx, int root, double *gpu_ms_out) {
         TSP_NCCL(g_rccl.Reduce(ctx->image, ctx->image, count, ncclFloat, ncclSum, root, (ncclComm_t)ctx->comm, ctx->stream));
     TSP_HIP(hipEventRecord(ctx->ev[EV_T5], ctx->stream));
     TSP_HIP(hipStreamSynchronize(ctx->stream));
+    ctx->forget_render_undo();
     ctx->image_is_reduced = true;
     float ms = 0.f;
     TSP_HIP(hipEventElapsedTime(&ms, ctx->ev[EV_T4], ctx->ev[EV_T5]));

@@ -476,6 +476,7 @@ int reorder_spatial(tsp_context *ctx, int n_strata, uint64_t seed, int64_t *perm
     DeviceScratch spare;
     TSP_SCRATCH_ALLOC(ctx, SITE("reorder_spare"), spare, (size_t)n * 4);
     ctx->surface_keys = false;         // (the keys hold indices of the old order)
+    ctx->forget_render_undo();
     float **arrs[] = {&p.x, &p.y, &p.z, &p.h, &p.m, &p.q, &p.r, &p.g, &p.b, &p.vx, &p.vy, &p.vz};
     for (float **a : arrs) {
         if (!*a) continue;

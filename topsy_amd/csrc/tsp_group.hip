@@ -210,7 +210,21 @@ int tsp_group_render(tsp_group *grp, const float *M, float scale_factor, const i
         if (s.empty()) { s.push_back(0); l.push_back(0); }
         return tsp_render(grp->ctx[g], M, scale_factor, s.data(), l.data(), (int)s.size(), clear, mode, flags, &ms[g]);
     });
-    if (rc) return rc;
+    if (rc) {
+        // A block draws on every shard or on none: the members whose tsp_render succeeded are put back as the call found them
+        // (tsp_render_undo; the failing members restored themselves), every presentation image is its member's own partial
+        // image again and the next end_frame sums them anew.  The error reported stays the failing member's.  A member whose
+        // tsp_render was refused before it touched anything (undo.kind 0: an accumulator of surface keys, a device error) is
+        // left as it is; if that is a root that still presents a reduced frame, the frame stands and nothing is summed again.
+        const std::string why = tsp_last_error();
+        std::string undo_error;
+        for (int g = 0; g < G; ++g)
+            if (grp->ctx[g]->undo.kind != 0 && tsp_render_undo(grp->ctx[g]) != TSP_OK)
+                undo_error += std::string("; and context ") + std::to_string(g) + " could not be put back (" + tsp_last_error() + ")";
+        if (!grp->ctx[0]->image_is_reduced) grp->needs_reduce = true;
+        set_error("%s%s", why.c_str(), undo_error.c_str());
+        return rc;
+    }
     grp->needs_reduce = true;
     if (gpu_ms_out) *gpu_ms_out = *std::max_element(ms.begin(), ms.end());
     return TSP_OK;

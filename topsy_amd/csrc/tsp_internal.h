@@ -193,6 +193,16 @@ struct tsp_context {
     int image_source = tsp::W_NONE;   // which 4-channel mode started the image (W_NONE: a 2-channel render, or none yet)
     float image_los[6] = {};          // ... and, for W_KINEMATIC, along which line of sight
     bool kinematic_block = false;     // set by tsp_render around a kinematic block: the rgb pipeline then asks for the kinematic weights
+    // tsp_render_undo: what the last tsp_render found, kept until another call changes the image (forget_render_undo)
+    struct RenderUndo {
+        int kind = 0;                 // 0: nothing to undo; 1: the block drew (image64_entry and the fields below put it back); 2: it failed (tsp_render restored everything itself)
+        int C = 0;
+        tsp_stats stats = {};
+        int64_t chunk_culled_particles = 0;
+        int image_source = tsp::W_NONE;
+        float image_los[6] = {};
+    } undo;
+    void forget_render_undo() { undo.kind = 0; }
 };
 
 namespace tsp {

@@ -78,6 +78,7 @@ int tile_periodic(tsp_context *ctx, int n, const float *h_offsets, const float *
     else
         hipLaunchKernelGGL(tile_periodic_kernel<4>, dim3(grid), dim3(256), 0, ctx->stream, ctx->image, d_out, ctx->R, n, d_off, d_w);
     TSP_HIP(hipGetLastError());
+    ctx->forget_render_undo();
     TSP_HIP(hipMemcpyAsync(ctx->image, d_out, img_bytes, hipMemcpyDeviceToDevice, ctx->stream));
     TSP_HIP(hipStreamSynchronize(ctx->stream));
     return TSP_OK;

@@ -19,13 +19,27 @@ def shard_range(n_total, rank, world_size):
     return int(b[rank]), int(b[rank + 1] - b[rank])
 
 
-def intersect_ranges(starts, lens, shard_start, shard_len):
+def clip_ranges(starts, lens, n_total):
+    """Global (start, len) blocks clipped to [0, n_total) the way tsp_render clips them, without ever forming start + len of
+    the caller's values: a length of INT64_MAX means "to the end", a negative start loses what lies before 0.  Returns int64
+    arrays of the same shape (a block that holds nothing keeps its place with length 0)."""
+    starts = np.array(starts, dtype=np.int64, ndmin=1)
+    lens = np.maximum(np.array(lens, dtype=np.int64, ndmin=1), 0)
+    before = np.minimum(starts, 0)                                  # <= 0: what a negative start cuts off the block
+    lens = np.where(lens > -(before + 1), lens + before, 0)         # (-(INT64_MIN + 1) = INT64_MAX: no overflow either way)
+    starts = np.clip(starts, 0, int(n_total))
+    return starts, np.minimum(lens, int(n_total) - starts)
+
+
+def intersect_ranges(starts, lens, shard_start, shard_len, n_total=None):
     """Clip global (start, len) blocks to one shard and re-base them to shard-local indices
-    (what global_to_split_monotonic does per physical buffer in the reference)."""
-    starts = np.asarray(starts, dtype=np.int64)
-    lens = np.asarray(lens, dtype=np.int64)
+    (what global_to_split_monotonic does per physical buffer in the reference).  The blocks are first clipped to the
+    snapshot's [0, n_total) as tsp_render and tsp_group_render do (n_total = None: to the end of this shard, which gives the
+    same intersection), so "to the end" lengths up to INT64_MAX and negative starts are safe."""
+    end = shard_start + shard_len
+    starts, lens = clip_ranges(starts, lens, end if n_total is None else max(int(n_total), end))
     lo = np.maximum(starts, shard_start)
-    hi = np.minimum(starts + lens, shard_start + shard_len)
+    hi = np.minimum(starts + lens, end)
     keep = hi > lo
     return (lo[keep] - shard_start), (hi[keep] - lo[keep])
 
@@ -60,7 +74,7 @@ class ShardedRenderer:
         """Render this rank's share of one block.  starts = lens = None means the whole snapshot (as in tsp_render)."""
         if starts is None and lens is None:
             starts, lens = [0], [self.n_total]
-        s, l = intersect_ranges(starts, lens, self.shard_start, self.shard_len)
+        s, l = intersect_ranges(starts, lens, self.shard_start, self.shard_len, self.n_total)
         return self.context.render(matrix, scale_factor, s, l, clear=clear, mode=mode, flags=flags)
 
     def reduce(self, root=0):

@@ -20,6 +20,9 @@ set into contiguous index ranges and intersects every draw range with them.  Thi
     a read-back / add / write-back through the host.  The host collective is for test boxes only: it keeps a FLOAT32 copy
     of the root's partial image and writes it back before a REFINE block, so the root's float64 accumulation is rounded to
     float32 once per frame there (RCCL leaves every accumulator untouched);
+  * a block draws on every shard or on none: when one context's render fails, the others take the block back
+    (tsp_render_undo) and the frame is reduced anew, so a retried REFINE block is counted once; a shard that holds no particle
+    (fewer particles than contexts, or than interleave blocks) takes part in every render but in no upload;
   * everything that looks at the finished image (read-back, colormap, autorange, periodic tiling) runs on the first
     context; the progressive mass scale N / N_drawn stays global because the render progression above is unchanged.
 
@@ -57,6 +60,7 @@ class MultiGpuContext:
         self._pool = ThreadPoolExecutor(max_workers=len(device_ids), thread_name_prefix="tsp-gpu")
         self._bounds = np.zeros(len(device_ids) + 1, dtype=np.int64)
         self._needs_reduce = False          # the shards hold partial images that have not been summed onto the root yet
+        self._reduce_blocked = None         # why the shards cannot be summed (set by a failed block under RCCL, cleared by a render)
         self.last_reduce_ms = 0.0
         # RCCL needs one device per rank; contexts that share a device (single-GPU boxes, tests) sum through the host
         self.collective = "rccl" if len(set(device_ids)) == len(device_ids) else "host"
@@ -107,11 +111,13 @@ class MultiGpuContext:
 
     def _local_ranges(self, starts, lens, g):
         if self._cyclic_ranges:
+            # clipped to [0, n) first, as tsp_render clips: start + len of a "to the end" length would overflow
+            starts, lens = distributed.clip_ranges(starts, lens, self.num_particles)
             lo, hi = self._cyclic_local(starts, g), self._cyclic_local(starts + lens, g)
             keep = hi > lo
             return lo[keep], (hi - lo)[keep]
         a, ln = self._shard(g)
-        return distributed.intersect_ranges(starts, lens, a, ln)
+        return distributed.intersect_ranges(starts, lens, a, ln, self.num_particles)
 
     def close(self):
         # the communicators go first, explicitly and rank by rank, in the calling thread (close() also runs from __del__ at
@@ -180,7 +186,9 @@ class MultiGpuContext:
         self._map(lambda g, c: c.upload_particles(*[self._take(v, g) for v in arrays]))
 
     def _upload_sliced(self, method, arrays, axis=0):
-        self._map(lambda g, c: getattr(c, method)(*[self._take(v, g, axis) for v in arrays]))
+        # an empty shard (fewer particles or interleave blocks than members) holds nothing to attach the values to: the
+        # library refuses an upload before any particle is resident, so it is skipped, as tsp_group_upload_* skips it
+        self._map(lambda g, c: getattr(c, method)(*[self._take(v, g, axis) for v in arrays]) if self._shard(g)[1] > 0 else None)
 
     def upload_quantity(self, q):
         if q is None:
@@ -193,8 +201,8 @@ class MultiGpuContext:
 
     def upload_band_magnitudes(self, mags, weights):
         mags = np.asarray(mags, dtype=np.float64)
-
-        self._map(lambda g, c: c.upload_band_magnitudes(np.ascontiguousarray(self._take(mags, g, axis=1)), weights))
+        self._map(lambda g, c: c.upload_band_magnitudes(np.ascontiguousarray(self._take(mags, g, axis=1)), weights)
+                  if self._shard(g)[1] > 0 else None)
 
     def smoothing_lengths(self, x, y, z, n_neighbours=32, period=None):
         """Smoothing lengths of the whole (caller-ordered) snapshot, computed on the first context: the neighbour search needs
@@ -294,20 +302,61 @@ class MultiGpuContext:
             starts, lens = [0], [self.num_particles]
         starts = np.asarray(starts, dtype=np.int64)
         lens = np.asarray(lens, dtype=np.int64)
+        # what the binding would refuse is refused here, before any member is touched (the frame stays as it is)
+        matrix = np.asarray(matrix, dtype=np.float32).reshape(16)
+        if starts.shape != lens.shape or starts.ndim != 1:
+            raise ValueError("starts and lens must be 1-D arrays of equal length")
+
         def go(g, c):
             s, l = self._local_ranges(starts, lens, g)
             if len(s) == 0:
                 s, l = np.zeros(1, dtype=np.int64), np.zeros(1, dtype=np.int64)
             return c.render(matrix, scale_factor, s, l, clear=clear, mode=mode, flags=flags)
-        ms = max(self._map(go))
-        self._needs_reduce = True
-        return ms
+        channels = [c.active_channels for c in self.contexts]
+        futures = [self._pool.submit(go, g, c) for g, c in enumerate(self.contexts)]
+        errors = [f.exception() for f in futures]
+        failed = [g for g, e in enumerate(errors) if e is not None]
+        if not failed:
+            self._needs_reduce = True
+            self._reduce_blocked = None
+            return max(f.result() for f in futures)
+        # A block draws on every shard or on none: the members that drew it are put back as the call found them and every
+        # presentation image becomes its member's own partial image again (tsp_render_undo).  Two kinds of member are left
+        # alone: one whose render the library refused before it touched anything (it has nothing to take back), and one whose
+        # call never reached the library, which still holds the undo state of an EARLIER block.
+        def undo(g, c):
+            """True: put back; False: left alone; an exception: a member that drew the block could not be put back"""
+            c.active_channels = channels[g]
+            if errors[g] is not None and not isinstance(errors[g], _native.BackendError):
+                return False
+            try:
+                c.render_undo()
+            except _native.BackendError as e:
+                return e if errors[g] is None else False
+            return True
+        undone = self._map(undo)
+        # The frame is summed anew only if the root was put back (its presentation image is then its own partial image).  A
+        # root that was left alone still presents what it presented before the call, the reduced frame included.  Under RCCL
+        # a member that was left alone may still count as reduced: the library would refuse its part of the collective while
+        # the other ranks wait in it, so such a frame is refused in end_frame, on the calling thread, until a render succeeds.
+        if undone[0] is True:
+            if self.collective == "rccl" and not self._needs_reduce and not all(u is True for u in undone):
+                left = [g for g, u in enumerate(undone) if u is not True]
+                self._reduce_blocked = f"contexts {left} could not be put back after a failed block: render again before presenting"
+            self._needs_reduce = True
+        g = failed[0]
+        if not isinstance(errors[g], _native.BackendError):
+            raise errors[g]
+        not_undone = "".join(f"; and context {j} could not be put back ({u})" for j, u in enumerate(undone) if isinstance(u, Exception))
+        raise _native.BackendError(f"context {g} (device {self.device_ids[g]}): {errors[g]}{not_undone}") from errors[g]
 
     def end_frame(self, root=0):
         """Sum the partial images onto the first context -- the ONE exchange step of a frame; a no-op when nothing was
         rendered since the last call.  Returns the milliseconds it took (GPU time for RCCL)."""
         if not self._needs_reduce:
             return 0.0
+        if self._reduce_blocked:
+            raise _native.BackendError(self._reduce_blocked)
         self._needs_reduce = False
         if self.collective == "rccl":
             self.last_reduce_ms = max(self._map(lambda g, c: c.comm_reduce_image(0)))
