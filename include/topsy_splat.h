@@ -101,7 +101,9 @@ const char *tsp_last_error(void);
  * 117: kinematic maps: TSP_MODE_KINEMATIC and the entry points tsp_upload_velocities, tsp_set_line_of_sight, tsp_velocity_moments,
  * tsp_colormap_moment; no struct changed, nothing else changed.
  * 118: new entry point tsp_render_undo; tsp_group_render draws a block on every member or on none (it used to leave the block in
- * the accumulators of the members that had succeeded); no struct changed, nothing else changed. */
+ * the accumulators of the members that had succeeded); no struct changed, nothing else changed.
+ * 119: kinematic frames: the bases TSP_PRESENT_MOMENT_MEAN / TSP_PRESENT_MOMENT_SIGMA of tsp_present and tsp_present_yuv420 (values
+ * that returned TSP_EINVAL before) and the new entry point tsp_moment_sort; no struct changed, nothing else changed. */
 int tsp_version(void);
 int tsp_stats_size(void);
 
@@ -507,14 +509,23 @@ int tsp_radial_profile(tsp_context *ctx, int64_t n, const float *x, const float 
  *     TSP_EINVAL.
  *   Neither of the two changes the image, the accumulator or tsp_stats.  Both form the maps in the staging buffer of
  *   tsp_colormap_rgb's float output (allocated on first use: TSP_ENOMEM).
+ *   - Canvas-sized frames of the maps, under a colorbar and the other layers: the bases TSP_PRESENT_MOMENT_MEAN and
+ *     TSP_PRESENT_MOMENT_SIGMA of tsp_present / tsp_present_yuv420 ("Frame composition" below).
+ *   - tsp_moment_sort: the order statistics of a moment map, for its colour range -- tsp_content_sort's sort (below) of other
+ *     values.  For every pixel of the kinematic presentation image the float32 moment `which` (1: mean, 2: sigma) is formed by the
+ *     rule of tsp_velocity_moments directly from the image (no staging buffer), with absolute != 0 its fabsf is taken, and the finite
+ *     values are sorted ascending into the buffers of tsp_content_sort (allocated on first use or growth: TSP_ENOMEM).  n_finite
+ *     receives their number; tsp_content_values then returns the values at ranks in [0, n_finite) exactly as after a content sort,
+ *     and tsp_content_neg_inf reports 0 (a moment is never -inf).  Same conditions as tsp_velocity_moments (TSP_ESTATE); which not
+ *     1 or 2, or a NULL argument: TSP_EINVAL.  The image, the accumulator and tsp_stats are unchanged.
  * Not provided: velocities on a tsp_group or sharded over several contexts by the library (a caller that shards uploads each
- * shard's velocities itself; the reduced image is a valid input of tsp_velocity_moments), canvas-sized frames (tsp_present) of
- * the maps. */
+ * shard's velocities itself; the reduced image is a valid input of tsp_velocity_moments and of the frames). */
 int tsp_upload_velocities(tsp_context *ctx, const float *vx, const float *vy, const float *vz);
 int tsp_set_line_of_sight(tsp_context *ctx, const float axis[3], const float v_ref[3]);
 int tsp_velocity_moments(tsp_context *ctx, float *maps_out /* R * R * 4 */);
 int tsp_colormap_moment(tsp_context *ctx, int which /* 1 mean, 2 sigma */, const float *lut_rgba, int n_lut, float vmin, float vmax,
                         int log_scale, uint8_t *out_rgba8);
+int tsp_moment_sort(tsp_context *ctx, int which /* 1 mean, 2 sigma */, int absolute, int64_t *n_finite);
 
 /* Surface rendering: DepthSPHWithOcclusion + ColorAsSurfaceMap (reference src/topsy/sph.py:448-656, shaders/sph.wgsl:94-122,
  * 149-158, shaders/smooth.wgsl, shaders/surface.wgsl, colormap/surface.py).  Float32 throughout, operations in the order written.
@@ -590,6 +601,17 @@ int tsp_surface_present(tsp_context *ctx, const tsp_surface_params *params, floa
  * tsp_colormap_bivariate (LUT of tsp_colormap_set_lut2d) and tsp_colormap_rgb (4-channel image).  TSP_PRESENT_RGB_HDR is the rgb
  * map on an rgba16float canvas: the unclamped float colour, alpha 1.
  *
+ * Moment bases (TSP_PRESENT_MOMENT_MEAN, TSP_PRESENT_MOMENT_SIGMA): the kinematic maps ("Kinematic maps" above) on the canvas.  The
+ * four raw channels (S, A, B, n) of the kinematic presentation image are sampled exactly as above (same k, ox, oy; the linear rule
+ * with its f == 0 selection and clamp-to-edge for k <= 1, else nearest).  From the sampled S, A, B the moment is formed by the rule
+ * of tsp_velocity_moments -- float64, every operation correctly rounded, none fused: S > 0 and S, A, B finite: mean = A / S,
+ * var = B / S - mean * mean clamped at 0, sigma = sqrt(var); otherwise NaN -- and rounded to float32.  Sampling the sums and dividing
+ * afterwards is the mass-weighted interpolation of the maps, the order in which the weighted scalar map works.  The moment is then
+ * mapped by the scalar map, unweighted, on (value, 0) with lut_rgba, n_lut, vmin, vmax and log_scale of the base (weighted,
+ * density_vmin, density_vmax and gamma are not read); a NaN takes the colour of vmin, as in tsp_colormap_moment.  At W = H = R
+ * without layers the frame is tsp_colormap_moment's image bit for bit.  The image must be a 4-channel kinematic one, the condition
+ * of tsp_velocity_moments (TSP_ESTATE otherwise); the LUT has 2..65536 entries (TSP_EINVAL); the canvas is rgba8unorm.
+ *
  * Layers, in order; every instance of a textured quad and every segment of a line set is one primitive, drawn in turn.
  *   Textured quad (overlay.wgsl, overlay.py): texture_rgba = th rows (row 0 at the top) of tw RGBA float32 texels; clip_origin
  *   (x0, y0), clip_extent (w, h) > 0, tex_origin (u0, v0), tex_extent (du, dv); n_instances clip offsets (dx, dy) and weights.
@@ -616,20 +638,21 @@ int tsp_surface_present(tsp_context *ctx, const tsp_surface_params *params, floa
  *
  * Limits (TSP_EINVAL otherwise, nothing written): 0 <= n_layers <= 1024, at most 65536 primitives in all; a quad has a texture of
  * 1..16384 texels per side, 1..128 instances, finite geometry with w, h > 0, |u0| + |du| and |v0| + |dv| <= 1024 and finite
- * offsets / weights; a line set 1..65536 segments, finite width >= 0.  The base layer needs a LUT of 2..65536 entries (scalar),
- * tsp_colormap_set_lut2d (bivariate, TSP_ESTATE) or a 4-channel image (rgb).  out: H x W x 4 uint8, or H x W x 4 float16
+ * offsets / weights; a line set 1..65536 segments, finite width >= 0.  The base layer needs a LUT of 2..65536 entries (scalar,
+ * moments), tsp_colormap_set_lut2d (bivariate, TSP_ESTATE), a 4-channel image (rgb) or a kinematic image (moments, TSP_ESTATE).  out: H x W x 4 uint8, or H x W x 4 float16
  * (binary16 bits, uint16) for TSP_PRESENT_RGB_HDR.  Device memory for textures, primitive table and output staging is allocated
  * for the call only (TSP_ENOMEM on failure).  A failed call leaves the accumulator, the presentation image and `out` untouched.
  * gpu_ms_out (or NULL): GPU time of the composition kernel (hipEvents). */
-enum { TSP_PRESENT_SCALAR = 0, TSP_PRESENT_BIVARIATE = 1, TSP_PRESENT_RGB = 2, TSP_PRESENT_RGB_HDR = 3 };
+enum { TSP_PRESENT_SCALAR = 0, TSP_PRESENT_BIVARIATE = 1, TSP_PRESENT_RGB = 2, TSP_PRESENT_RGB_HDR = 3, TSP_PRESENT_MOMENT_MEAN = 4,
+       TSP_PRESENT_MOMENT_SIGMA = 5 };
 enum { TSP_LAYER_QUAD = 0, TSP_LAYER_LINES = 1 };
 typedef struct tsp_present_base {
     int map;                         /* TSP_PRESENT_* */
     float vmin, vmax;                /* the already-scaled shader parameters, as tsp_colormap_* take them */
     float density_vmin, density_vmax;    /* bivariate */
     float gamma;                     /* rgb */
-    int log_scale, weighted;         /* scalar, bivariate */
-    const float *lut_rgba;           /* scalar: n_lut RGBA float32 entries */
+    int log_scale, weighted;         /* scalar, bivariate; moments: log_scale */
+    const float *lut_rgba;           /* scalar, moments: n_lut RGBA float32 entries */
     int n_lut;
 } tsp_present_base;
 typedef struct tsp_present_layer {

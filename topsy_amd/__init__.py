@@ -280,8 +280,9 @@ def VelocityView(visualizer, v_ref="center", **parameters):
     from the velocities first: "center" (the mean velocity of the inner fifth of the sphere of radius vis.scale about what the
     view is centred on, the rule vis.profile uses), three components, or None (zero).  get_maps() (dict: surface_density, v_los,
     sigma_los, count), get_presentation_image("v_los" | "sigma_los") ((R, R, 4) uint8), view["v_los", "vmax"] etc.  After
-    vis.orient("sideon", r) v_los is the picture of the rotation curve vis.profile gives.  One GPU, no periodic tiling; no
-    canvas-sized frames, not a recorder's target."""
+    vis.orient("sideon", r) v_los is the picture of the rotation curve vis.profile gives.  view.frames("v_los" | "sigma_los") is
+    the map with a visualizer's frame interface -- get_presentation_image((W, H)) under its colorbar and the scale bar, the 4:2:0
+    planes -- and a target of VisualizationRecorder.  One GPU, no periodic tiling."""
     from . import kinematics
     return kinematics.VelocityView(visualizer, v_ref=v_ref, **parameters)
 

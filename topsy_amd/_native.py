@@ -18,8 +18,9 @@ SAMPLE_BILINEAR_MIP0, SAMPLE_BILINEAR_MIP = 0x10, 0x20      # diagnostic samplin
 UNIQUE_ID_BYTES = 128
 ABI_VERSION = 112            # the oldest tsp_version() whose structs this binding matches; entry points added since
                              # (113: tsp_shrink_sphere_center, 114: tsp_fof_groups, 115: tsp_sphere_moments,
-                             # 116: tsp_radial_profile, 117: the kinematic maps) are required by name in load_library()
-PRESENT_SCALAR, PRESENT_BIVARIATE, PRESENT_RGB, PRESENT_RGB_HDR = 0, 1, 2, 3
+                             # 116: tsp_radial_profile, 117: the kinematic maps, 119: tsp_moment_sort) are required by name in
+                             # load_library()
+PRESENT_SCALAR, PRESENT_BIVARIATE, PRESENT_RGB, PRESENT_RGB_HDR, PRESENT_MOMENT_MEAN, PRESENT_MOMENT_SIGMA = 0, 1, 2, 3, 4, 5
 LAYER_QUAD, LAYER_LINES = 0, 1
 
 
@@ -184,6 +185,7 @@ SIGNATURES = {
     "tsp_present_surface_yuv420": (ctypes.c_int, [_ctx, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
                                                   _u8p, ctypes.POINTER(ctypes.c_double)]),
     "tsp_content_sort": (ctypes.c_int, [_ctx, ctypes.c_int, ctypes.c_float, _i64p, _i64p]),
+    "tsp_moment_sort": (ctypes.c_int, [_ctx, ctypes.c_int, ctypes.c_int, _i64p]),
     "tsp_content_values": (ctypes.c_int, [_ctx, _i64p, ctypes.c_int, _fp]),
     "tsp_content_neg_inf": (ctypes.c_int, [_ctx, _i64p]),
     "tsp_get_stats": (ctypes.c_int, [_ctx, ctypes.POINTER(Stats)]),
@@ -653,6 +655,13 @@ class Context:
         _check(self._lib.tsp_content_sort(self._h, int(kind), float(np.float32(scale)), ctypes.byref(nf), ctypes.byref(nnp)))
         return nf.value, nnp.value
 
+    def moment_sort(self, which, absolute=False):
+        """Sort the finite values of a moment map of the kinematic image (which: 1 mean, 2 sigma; absolute: of its absolute
+        value) on the device (tsp_moment_sort); returns n_finite.  content_values then reads the values at ranks below it."""
+        nf = ctypes.c_int64(0)
+        _check(self._lib.tsp_moment_sort(self._h, int(which), int(bool(absolute)), ctypes.byref(nf)))
+        return nf.value
+
     def content_values(self, ranks):
         r = np.ascontiguousarray(ranks, dtype=np.int64)
         out = np.empty(len(r), dtype=np.float32)
@@ -754,9 +763,9 @@ class Context:
     # ---- frame composition ----------------------------------------------------------------
     def present(self, width, height, base, layers=(), timings=None):
         """Compose a (height, width, 4) frame (tsp_present): the presentation image colormapped onto the canvas, then `layers`
-        in order.  base: dict with "map" ("scalar" | "bivariate" | "rgb" | "rgb-hdr"), "vmin", "vmax" and as the map needs
-        "lut" (scalar, (n, 4) float32), "log", "weighted", "density_vmin", "density_vmax" (bivariate, after colormap_set_lut2d),
-        "gamma" (rgb).  A layer is a dict with "kind" "quad" (texture (th, tw, 4) float32, clip (x0, y0, w, h), tex (u0, v0, du,
+        in order.  base: dict with "map" ("scalar" | "bivariate" | "rgb" | "rgb-hdr" | "moment-mean" | "moment-sigma", the last two
+        the maps of a kinematic image), "vmin", "vmax" and as the map needs "lut" (scalar, moments: (n, 4) float32), "log",
+        "weighted", "density_vmin", "density_vmax" (bivariate, after colormap_set_lut2d), "gamma" (rgb).  A layer is a dict with "kind" "quad" (texture (th, tw, 4) float32, clip (x0, y0, w, h), tex (u0, v0, du,
         dv), offsets (n, 2), weights (n,)) or "lines" (starts / ends (n, 4), transform (4, 4) row-major, color (4,), width).
         Returns uint8, or float16 for "rgb-hdr".  `timings`, a list, receives the composition kernel's GPU ms."""
         b, arr, keep = self._present_args(base, layers)
@@ -788,7 +797,8 @@ class Context:
     @staticmethod
     def _present_args(base, layers):
         """The ctypes structs of tsp_present's base and layers, and the arrays they point into (kept alive by the caller)."""
-        maps = {"scalar": PRESENT_SCALAR, "bivariate": PRESENT_BIVARIATE, "rgb": PRESENT_RGB, "rgb-hdr": PRESENT_RGB_HDR}
+        maps = {"scalar": PRESENT_SCALAR, "bivariate": PRESENT_BIVARIATE, "rgb": PRESENT_RGB, "rgb-hdr": PRESENT_RGB_HDR,
+                "moment-mean": PRESENT_MOMENT_MEAN, "moment-sigma": PRESENT_MOMENT_SIGMA}
         b = PresentBase()
         b.map = maps[base["map"]]
         b.vmin, b.vmax = float(np.float32(base["vmin"])), float(np.float32(base["vmax"]))
@@ -797,7 +807,7 @@ class Context:
         b.gamma = float(np.float32(base.get("gamma", 1.0)))
         b.log_scale, b.weighted = int(bool(base.get("log", False))), int(bool(base.get("weighted", False)))
         keep = []             # the arrays the structs point into stay alive for the call
-        if b.map == PRESENT_SCALAR:
+        if b.map in (PRESENT_SCALAR, PRESENT_MOMENT_MEAN, PRESENT_MOMENT_SIGMA):
             lut = _f32(base["lut"], name="lut")
             keep.append(lut)
             b.lut_rgba, b.n_lut = _ptr(lut), lut.size // 4

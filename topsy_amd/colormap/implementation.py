@@ -29,6 +29,13 @@ def percentile_from_order_statistics(fetch, first, n, q, transform=None):
     return _quantile_from_order_statistics(fetch, first, n, q, np.true_divide(q, np.float32(100)), transform)
 
 
+def percentile_f64_from_order_statistics(fetch, first, n, q):
+    """np.percentile(sample.astype(np.float64), q) (method 'linear') where the float32 `sample` is known only through its order
+    statistics, as in percentile_from_order_statistics: the host rules that convert to float64 first (kinematics.v_los_range,
+    sigma_los_range) divide q by a float64 100 and interpolate in float64."""
+    return _quantile_from_order_statistics(fetch, first, n, q, np.true_divide(q, np.float64(100)), lambda v: v.astype(np.float64))
+
+
 def quantile_from_order_statistics(fetch, n, quantiles):
     """np.quantile(sample, quantiles) (method 'linear') of the float32 `sample` known through its order statistics in numpy's sort
     order (NaN last): the same arithmetic as percentile_from_order_statistics with the quantiles as given, and numpy's NaN rule --

@@ -221,7 +221,7 @@ using namespace tsp;
 extern "C" {
 
 const char *tsp_last_error(void) { return g_err; }
-int tsp_version(void) { return 118; }     // 118: tsp_render_undo, tsp_group_render all-or-nothing across the members; 117: kinematic maps (tsp_upload_velocities, tsp_set_line_of_sight, TSP_MODE_KINEMATIC, tsp_velocity_moments, tsp_colormap_moment); 116: tsp_radial_profile; 115: tsp_sphere_moments; 114: tsp_fof_groups; 113: tsp_shrink_sphere_center; 112: tsp_present_surface, tsp_present_surface_yuv420; 111: tsp_content_neg_inf; 110: tsp_sph_sum; 109: tsp_present_yuv420; 108: tsp_present; 107: surface rendering; 106: tsp_smoothing_lengths; 101: tsp_stats gained ms_mega, n_mega (16 bytes); 102: the per-kernel fragment counts (32 bytes); 103: n_chunk_culled (8 bytes); 104: matrix-core / kernel-I options removed; 105: kernel M's options removed (kernel G draws the mid footprints)
+int tsp_version(void) { return 119; }     // 119: tsp_moment_sort, TSP_PRESENT_MOMENT_MEAN / _SIGMA (the kinematic maps as the base of tsp_present / tsp_present_yuv420); 118: tsp_render_undo, tsp_group_render all-or-nothing across the members; 117: kinematic maps (tsp_upload_velocities, tsp_set_line_of_sight, TSP_MODE_KINEMATIC, tsp_velocity_moments, tsp_colormap_moment); 116: tsp_radial_profile; 115: tsp_sphere_moments; 114: tsp_fof_groups; 113: tsp_shrink_sphere_center; 112: tsp_present_surface, tsp_present_surface_yuv420; 111: tsp_content_neg_inf; 110: tsp_sph_sum; 109: tsp_present_yuv420; 108: tsp_present; 107: surface rendering; 106: tsp_smoothing_lengths; 101: tsp_stats gained ms_mega, n_mega (16 bytes); 102: the per-kernel fragment counts (32 bytes); 103: n_chunk_culled (8 bytes); 104: matrix-core / kernel-I options removed; 105: kernel M's options removed (kernel G draws the mid footprints)
 int tsp_stats_size(void) { return (int)sizeof(tsp_stats); }
 
 int tsp_device_count(void) {
@@ -1046,9 +1046,18 @@ int tsp_content_sort(tsp_context *ctx, int kind, float scale, int64_t *n_finite,
     return content_sort(ctx, kind, scale, n_finite, n_nonpositive);
 }
 
+int tsp_moment_sort(tsp_context *ctx, int which, int absolute, int64_t *n_finite) {
+    TSP_REQUIRE(ctx && n_finite, TSP_EINVAL, "NULL argument");
+    TSP_REQUIRE(which == 1 || which == 2, TSP_EINVAL, "which must be 1 (mean) or 2 (sigma), not %d", which);
+    TSP_REQUIRE(ctx->image_source == W_KINEMATIC && ctx->C == 4, TSP_ESTATE,
+                "the image is not a kinematic one (render with TSP_MODE_KINEMATIC first)");
+    TSP_HIP(hipSetDevice(ctx->device));
+    return moment_sort(ctx, which, absolute, n_finite);
+}
+
 int tsp_content_values(tsp_context *ctx, const int64_t *ranks, int n_ranks, float *out) {
     TSP_REQUIRE(ctx && ranks && out && n_ranks >= 0, TSP_EINVAL, "bad argument");
-    TSP_REQUIRE(ctx->sort_keys_alt, TSP_ESTATE, "tsp_content_sort has not been called");
+    TSP_REQUIRE(ctx->sort_keys_alt, TSP_ESTATE, "tsp_content_sort / tsp_moment_sort has not been called");
     TSP_HIP(hipSetDevice(ctx->device));
     for (int i = 0; i < n_ranks; ++i) {
         TSP_REQUIRE(ranks[i] >= 0 && ranks[i] < ctx->sorted_count, TSP_EINVAL, "rank %lld outside [0, %lld)",
@@ -1063,7 +1072,7 @@ int tsp_content_values(tsp_context *ctx, const int64_t *ranks, int n_ranks, floa
 
 int tsp_content_neg_inf(tsp_context *ctx, int64_t *n_neg_inf) {
     TSP_REQUIRE(ctx && n_neg_inf, TSP_EINVAL, "NULL argument");
-    TSP_REQUIRE(ctx->sort_keys_alt, TSP_ESTATE, "tsp_content_sort has not been called");
+    TSP_REQUIRE(ctx->sort_keys_alt, TSP_ESTATE, "tsp_content_sort / tsp_moment_sort has not been called");
     *n_neg_inf = ctx->sorted_neg_inf;
     return TSP_OK;
 }

@@ -544,9 +544,35 @@ __global__ __launch_bounds__(256) void content_key_kernel(const float *__restric
     }
 }
 
-int content_sort(tsp_context *ctx, int kind, float scale, int64_t *n_finite, int64_t *n_nonpositive) {
-    const int64_t npix = (int64_t)ctx->R * ctx->R;
-    const int64_t n = npix * (kind == 2 ? 3 : (kind == 3 ? ctx->C : 1));
+// the float32 moment `which` (1: mean, 2: sigma) of every pixel of a kinematic image, formed from the image itself by the shared
+// rule (velocity_moments_f32, tsp_math.h), |.| of it when `absolute`: the keys of tsp_moment_sort.  counts as content_key_kernel's
+// (a moment is never -inf: counts[2] stays 0)
+__global__ __launch_bounds__(256) void moment_key_kernel(const float4 *__restrict__ img, int64_t npix, int which, int absolute,
+                                                         uint32_t *__restrict__ keys, unsigned long long *counts) {
+    unsigned long long nf = 0, nnp = 0;
+    for (int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x; t < npix; t += (int64_t)gridDim.x * 256) {
+        const float4 c = img[t];
+        float mean, sigma;
+        velocity_moments_f32(c.x, c.y, c.z, mean, sigma);
+        float v = which == 2 ? sigma : mean;
+        if (absolute) v = __builtin_fabsf(v);
+        const bool fin = finite_f32(v);
+        keys[t] = fin ? ordered_u32(v) : 0xFFFFFFFFu;
+        nf += fin;
+        nnp += fin && (v <= 0.0f);
+    }
+    for (int o = 32; o; o >>= 1) {
+        nf += __shfl_xor((long long)nf, o);
+        nnp += __shfl_xor((long long)nnp, o);
+    }
+    if ((threadIdx.x & 63) == 0) {
+        if (nf) atomicAdd(&counts[0], nf);
+        if (nnp) atomicAdd(&counts[1], nnp);
+    }
+}
+
+// room for n keys in the sort buffers, and the zeroed counts [finite, nonpositive, -inf] of the key kernel (on ctx->stream)
+static int sort_reserve(tsp_context *ctx, int64_t n, unsigned long long *&counts) {
     hipStream_t st = ctx->stream;
     if (ctx->sort_capacity < n) {
         size_t tmp_bytes = 0;     // (the size query reads no key)
@@ -557,11 +583,14 @@ int content_sort(tsp_context *ctx, int kind, float scale, int64_t *n_finite, int
                                    {{&ctx->sort_capacity, n}, {&ctx->sort_tmp_bytes, (int64_t)tmp_bytes}});
         if (rc) return rc;
     }
-    unsigned long long *counts = reinterpret_cast<unsigned long long *>(ctx->counters);   // scratch: reuse the counter block
+    counts = reinterpret_cast<unsigned long long *>(ctx->counters);   // scratch: reuse the counter block
     TSP_HIP(hipMemsetAsync(counts, 0, 3 * sizeof(unsigned long long), st));
-    const unsigned grid = (unsigned)std::min<int64_t>((n + 255) / 256, (int64_t)ctx->cu_count * 8);
-    hipLaunchKernelGGL(content_key_kernel, dim3(grid), dim3(256), 0, st, ctx->image, npix, ctx->C, kind, scale, ctx->sort_keys, counts);
-    TSP_HIP(hipGetLastError());
+    return TSP_OK;
+}
+
+// sort the n keys the key kernel wrote and read its counts back
+static int sort_keys_and_count(tsp_context *ctx, int64_t n, const unsigned long long *counts, int64_t *n_finite, int64_t *n_nonpositive) {
+    hipStream_t st = ctx->stream;
     size_t tmp_bytes = ctx->sort_tmp_bytes;
     TSP_HIP(hipcub::DeviceRadixSort::SortKeys(ctx->sort_tmp, tmp_bytes, ctx->sort_keys, ctx->sort_keys_alt, n, 0, 32, st));
     unsigned long long hc[3];
@@ -570,8 +599,30 @@ int content_sort(tsp_context *ctx, int kind, float scale, int64_t *n_finite, int
     ctx->sorted_count = (int64_t)hc[0];
     ctx->sorted_neg_inf = (int64_t)hc[2];
     *n_finite = (int64_t)hc[0];
-    *n_nonpositive = (int64_t)hc[1];
+    if (n_nonpositive) *n_nonpositive = (int64_t)hc[1];
     return TSP_OK;
+}
+
+int content_sort(tsp_context *ctx, int kind, float scale, int64_t *n_finite, int64_t *n_nonpositive) {
+    const int64_t npix = (int64_t)ctx->R * ctx->R;
+    const int64_t n = npix * (kind == 2 ? 3 : (kind == 3 ? ctx->C : 1));
+    unsigned long long *counts = nullptr;
+    if (int rc = sort_reserve(ctx, n, counts)) return rc;
+    const unsigned grid = (unsigned)std::min<int64_t>((n + 255) / 256, (int64_t)ctx->cu_count * 8);
+    hipLaunchKernelGGL(content_key_kernel, dim3(grid), dim3(256), 0, ctx->stream, ctx->image, npix, ctx->C, kind, scale, ctx->sort_keys, counts);
+    TSP_HIP(hipGetLastError());
+    return sort_keys_and_count(ctx, n, counts, n_finite, n_nonpositive);
+}
+
+int moment_sort(tsp_context *ctx, int which, int absolute, int64_t *n_finite) {
+    const int64_t npix = (int64_t)ctx->R * ctx->R;
+    unsigned long long *counts = nullptr;
+    if (int rc = sort_reserve(ctx, npix, counts)) return rc;
+    const unsigned grid = (unsigned)std::min<int64_t>((npix + 255) / 256, (int64_t)ctx->cu_count * 8);
+    hipLaunchKernelGGL(moment_key_kernel, dim3(grid), dim3(256), 0, ctx->stream, reinterpret_cast<const float4 *>(ctx->image), npix, which,
+                       absolute ? 1 : 0, ctx->sort_keys, counts);
+    TSP_HIP(hipGetLastError());
+    return sort_keys_and_count(ctx, npix, counts, n_finite, nullptr);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -287,6 +287,7 @@ int ensure_block_bounds(tsp_context *ctx);     // (re)computes ws.block_bounds o
 int measure_read_bandwidth(tsp_context *ctx, int64_t bytes, int iters, double *gbps_out);
 int launch_image_convert(tsp_context *ctx, bool to_float);
 int tile_periodic(tsp_context *ctx, int n, const float *h_offsets, const float *h_weights);
+int moment_sort(tsp_context *ctx, int which, int absolute, int64_t *n_finite);   // the same sort of a kinematic image's moment map
 int content_sort(tsp_context *ctx, int kind, float scale, int64_t *n_finite, int64_t *n_nonpositive);   // image64 -> image (true) or image -> image64 (false)
 int ensure_array(float **p, int64_t n);
 int smoothing_lengths(tsp_context *ctx, int64_t n, const float *x, const float *y, const float *z, int k, float period,

@@ -17,8 +17,6 @@ struct LineOfSight {
     float a[3], v[3];     // unit axis, reference velocity
 };
 
-__device__ __forceinline__ bool finite_f32(float x) { return __builtin_fabsf(x) < __builtin_inff(); }   // false for NaN
-
 __device__ __forceinline__ void kinematic_weight(const LineOfSight &los, float h, float m, float vx, float vy, float vz, float &wr,
                                                  float &wg, float &wb) {
     const float u = ((los.a[0] * (vx - los.v[0]) + los.a[1] * (vy - los.v[1])) + los.a[2] * (vz - los.v[2]));
@@ -71,19 +69,12 @@ int launch_kinematic_weights(tsp_context *ctx) {
     return TSP_OK;
 }
 
-// (S, A, B, n) -> (S, mean, sigma, n) per pixel; every operation a correctly rounded IEEE one
+// (S, A, B, n) -> (S, mean, sigma, n) per pixel; every operation a correctly rounded IEEE one (velocity_moments_f32, tsp_math.h)
 __global__ __launch_bounds__(256) void velocity_moments_kernel(const float4 *__restrict__ img, int64_t npix, float4 *__restrict__ maps) {
     for (int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x; p < npix; p += (int64_t)gridDim.x * 256) {
         const float4 c = img[p];
-        float mean = __uint_as_float(0x7fc00000u), sigma = mean;
-        if (c.x > 0.0f && finite_f32(c.x) && finite_f32(c.y) && finite_f32(c.z)) {
-            const double S = (double)c.x, A = (double)c.y, B = (double)c.z;
-            const double mu = __ddiv_rn(A, S);
-            double var = __ddiv_rn(B, S) - mu * mu;
-            if (var < 0.0) var = 0.0;
-            mean = (float)mu;
-            sigma = (float)__dsqrt_rn(var);
-        }
+        float mean, sigma;
+        velocity_moments_f32(c.x, c.y, c.z, mean, sigma);
         maps[p] = make_float4(c.x, mean, sigma, c.w);
     }
 }

@@ -271,6 +271,26 @@ __device__ __forceinline__ float map_rgb_channel(float value, float vmin, float 
 }
 
 // ------------------------------------------------------------------------------------------
+// the per-pixel moments of a kinematic image (include/topsy_splat.h "Kinematic maps"), shared by tsp_velocity_moments' kernel
+// (tsp_kinematics.hip), the moment bases of the frame composition (tsp_present.hip) and tsp_moment_sort (tsp_data.hip): from the
+// sums S, A, B in float64, every operation a correctly rounded IEEE one, mean = A / S and sigma = sqrt(max(B / S - mean^2, 0)),
+// each rounded to float32; both NaN unless S > 0 and S, A, B are finite
+// ------------------------------------------------------------------------------------------
+__device__ __forceinline__ bool finite_f32(float x) { return __builtin_fabsf(x) < __builtin_inff(); }   // false for NaN
+
+__device__ __forceinline__ void velocity_moments_f32(float S32, float A32, float B32, float &mean, float &sigma) {
+    mean = sigma = __uint_as_float(0x7fc00000u);
+    if (S32 > 0.0f && finite_f32(S32) && finite_f32(A32) && finite_f32(B32)) {
+        const double S = (double)S32, A = (double)A32, B = (double)B32;
+        const double mu = __ddiv_rn(A, S);
+        double var = __ddiv_rn(B, S) - mu * mu;
+        if (var < 0.0) var = 0.0;
+        mean = (float)mu;
+        sigma = (float)__dsqrt_rn(var);
+    }
+}
+
+// ------------------------------------------------------------------------------------------
 // the lit shading of the surface map (surface.wgsl:28-123), shared by tsp_surface_present's shading kernel (tsp_surface.hip)
 // and the surface base of the frame composition (tsp_present.hip)
 // ------------------------------------------------------------------------------------------

@@ -17,6 +17,10 @@
 // layer's sampling rule on both channels) and shades with the arithmetic of tsp_surface_present (surface_shade_rgba8,
 // tsp_math.h).  The filtered image is 8 bytes per texel and stays in L2.
 //
+// Moment bases (TSP_PRESENT_MOMENT_MEAN / _SIGMA): one more instantiation.  Every lane samples the four channels (S, A, B, n) of
+// the kinematic image by the base layer's rule (16 bytes per texel, up to four texels), forms the moment of the sampled sums in
+// float64 (velocity_moments_f32, tsp_math.h: the function tsp_velocity_moments' kernel calls) and maps it with the scalar map.
+//
 // Movie frames (tsp_present_yuv420): a second, small kernel converts the composed RGBA8 staging frame to I420 planes on the
 // device, so the composition kernel is the same and only 1.5 bytes per pixel are copied out.
 #include "tsp_internal.h"
@@ -130,8 +134,37 @@ __device__ __forceinline__ uint32_t surface_base_rgba8(const SurfaceArgs &a, flo
     return surface_shade_rgba8(c.x, Dc, Dl, Dr, Du, Dd, a.sp, a.lut);
 }
 
-// One pixel per lane: its base colour (Base = BaseArgs: the four maps; SurfaceArgs: the lit surface, HDR = false), the primitives
-// in draw order, the single write.
+// ---- moment bases (TSP_PRESENT_MOMENT_MEAN / _SIGMA): the four raw channels (S, A, B, n) of the kinematic image sampled by the
+// base layer's rule, the moment formed from the sampled sums (velocity_moments_f32, tsp_math.h: the mass-weighted interpolation),
+// then the scalar map, unweighted, on the rgba8unorm canvas
+struct MomentArgs {
+    const float *img;           // R x R x 4
+    int R, W, H;
+    float k, ox, oy;
+    int linear;                 // k <= 1
+    int sigma;                  // 0: the mean, 1: the dispersion
+    const float4 *lut;
+    int n_lut;
+    float vmin, range;
+    int log_scale;
+};
+
+__device__ __forceinline__ uint32_t moment_base_rgba8(const MomentArgs &a, float xc, float yc) {
+    const float ax = (xc - a.ox) * a.k, ay = (yc - a.oy) * a.k;
+    float4 v;
+    if (a.linear) {
+        v = bilinear(a.img, 4, a.R, a.R, ax, ay);
+    } else {
+        const int i = clampi((int)__builtin_floorf(ax), 0, a.R - 1), j = clampi((int)__builtin_floorf(ay), 0, a.R - 1);
+        v = load_texel(a.img, 4, (int64_t)j * a.R + i);
+    }
+    float mean, sigma;
+    velocity_moments_f32(v.x, v.y, v.z, mean, sigma);
+    return map_scalar_rgba8(a.sigma ? sigma : mean, 0.0f, a.lut, a.n_lut, a.vmin, a.range, a.log_scale, 0);
+}
+
+// One pixel per lane: its base colour (Base = BaseArgs: the four maps; SurfaceArgs: the lit surface; MomentArgs: a moment map of
+// the kinematic image; the last two with HDR = false), the primitives in draw order, the single write.
 template <bool HDR, typename Base>
 __global__ __launch_bounds__(256) void present_kernel(Base b, const PresentPrim *__restrict__ prims, int n_prims,
                                                       const float4 *__restrict__ tex, void *__restrict__ out) {
@@ -146,6 +179,8 @@ __global__ __launch_bounds__(256) void present_kernel(Base b, const PresentPrim 
     float4 pxf = make_float4(0.f, 0.f, 0.f, 1.f);
     if constexpr (std::is_same<Base, SurfaceArgs>::value) {
         px8 = surface_base_rgba8(b, xc, yc);
+    } else if constexpr (std::is_same<Base, MomentArgs>::value) {
+        px8 = moment_base_rgba8(b, xc, yc);
     } else {
         // ---- base layer: sample the raw channels, then map
         const float ax = (xc - b.ox) * b.k, ay = (yc - b.oy) * b.k;
@@ -394,7 +429,7 @@ int check_layer(const tsp_present_layer &L, int index, int64_t &n_prims, int64_t
     return TSP_OK;
 }
 
-// One frame: exactly one of `base` (the four maps of tsp_present) and `surf` (the lit surface) is given.  ms_out: base: the
+// One frame: exactly one of `base` (the maps of tsp_present) and `surf` (the lit surface) is given.  ms_out: base: the
 // composition (+ conversion); surf: [filter, composition (+ conversion)].
 int compose(tsp_context *ctx, int W, int H, const tsp_present_base *base, const tsp_surface_params *surf,
             const tsp_present_layer *layers, int n_layers, void *out, double *ms_out, bool yuv420) {
@@ -402,18 +437,22 @@ int compose(tsp_context *ctx, int W, int H, const tsp_present_base *base, const 
     if (yuv420) TSP_REQUIRE(W >= 2 && H >= 2 && W % 2 == 0 && H % 2 == 0, TSP_EINVAL, "4:2:0 needs an even canvas, not %d x %d", W, H);
     TSP_REQUIRE(n_layers >= 0 && n_layers <= MAX_LAYERS && (n_layers == 0 || layers), TSP_EINVAL, "bad layer list (%d layers)", n_layers);
     const int map = base ? base->map : -1;
+    const bool moment = map == TSP_PRESENT_MOMENT_MEAN || map == TSP_PRESENT_MOMENT_SIGMA;
     const float *h_lut = nullptr;       // the 1-D LUT of the call, if its base has one
     int n_lut = 0;
     if (base) {
-        TSP_REQUIRE(map >= TSP_PRESENT_SCALAR && map <= TSP_PRESENT_RGB_HDR, TSP_EINVAL, "unknown base map %d", map);
+        TSP_REQUIRE(map >= TSP_PRESENT_SCALAR && map <= TSP_PRESENT_MOMENT_SIGMA, TSP_EINVAL, "unknown base map %d", map);
         if (yuv420) TSP_REQUIRE(map != TSP_PRESENT_RGB_HDR, TSP_EINVAL, "4:2:0 frames are 8-bit: the rgb-hdr map has no such frame");
-        if (map == TSP_PRESENT_SCALAR) {
+        if (moment)
+            TSP_REQUIRE(ctx->image_source == W_KINEMATIC && ctx->C == 4, TSP_ESTATE,
+                        "the image is not a kinematic one (render with TSP_MODE_KINEMATIC first)");
+        if (map == TSP_PRESENT_SCALAR || moment) {
             TSP_REQUIRE(base->lut_rgba && base->n_lut >= 2 && base->n_lut <= 65536, TSP_EINVAL, "bad colormap LUT (n=%d)", base->n_lut);
             h_lut = base->lut_rgba;
             n_lut = base->n_lut;
         }
         if (map == TSP_PRESENT_BIVARIATE) TSP_REQUIRE(ctx->lut2d, TSP_ESTATE, "tsp_colormap_set_lut2d must be called first");
-        if (map >= TSP_PRESENT_RGB) TSP_REQUIRE(ctx->C == 4, TSP_EINVAL, "rgb maps need a 4-channel image");
+        if (map == TSP_PRESENT_RGB || map == TSP_PRESENT_RGB_HDR) TSP_REQUIRE(ctx->C == 4, TSP_EINVAL, "rgb maps need a 4-channel image");
     } else if (surf->weighted_average) {     // (checked by the caller: 2..65536 entries)
         h_lut = surf->lut_rgba;
         n_lut = surf->n_lut;
@@ -483,6 +522,25 @@ int compose(tsp_context *ctx, int W, int H, const tsp_present_base *base, const 
         a.sp = shade_params(*surf, W);
         a.lut = d_lut.as<float4>();
         hipLaunchKernelGGL((present_kernel<false, SurfaceArgs>), grid, dim3(256), 0, st, a, d_prims.as<PresentPrim>(), (int)prims.size(),
+                           d_tex.as<float4>(), d_frame.p);
+    } else if (moment) {
+        MomentArgs a;
+        a.img = ctx->image;
+        a.R = ctx->R;
+        a.W = W;
+        a.H = H;
+        a.k = k;
+        a.ox = ox;
+        a.oy = oy;
+        a.linear = k <= 1.0f;
+        a.sigma = map == TSP_PRESENT_MOMENT_SIGMA;
+        a.lut = d_lut.as<float4>();
+        a.n_lut = n_lut;
+        a.vmin = base->vmin;
+        a.range = base->vmax - base->vmin;
+        a.log_scale = base->log_scale ? 1 : 0;
+        TSP_HIP(hipEventRecord(ctx->ev[EV_T3], st));
+        hipLaunchKernelGGL((present_kernel<false, MomentArgs>), grid, dim3(256), 0, st, a, d_prims.as<PresentPrim>(), (int)prims.size(),
                            d_tex.as<float4>(), d_frame.p);
     } else {
         BaseArgs b;

@@ -5,20 +5,28 @@ It shares the visualizer's context, particles and camera, and renders into the s
 MODE_KINEMATIC): a later read of the visualizer re-renders its own frame, and the other way round.  The line of sight is the view
 axis, rotation_matrix[2]; after vis.orient("sideon", r) v_los shows the disc's rotation.
 
-Out of scope: several GPUs (MultiGpuContext, tsp_group_*: no sharded velocities), periodic tiling, canvas-sized frames
-(get_presentation_image is the R x R map, without colorbar or scale bar) and the recorder."""
+view.frames(kind) is the map as a frame source, VelocityFrames: frames.FrameInterface (the map on a canvas of any size under its
+colorbar, the scale bar, crosshairs and status line, composed on the GPU by tsp_present's moment bases) and the view-state
+properties, so that what is written against a visualizer's frames, topsy_amd.VisualizationRecorder included, works on it.  The
+automatic colour range comes from a device sort of the map (tsp_moment_sort): a handful of values are read back per frame, not the
+maps.
+
+Out of scope: several GPUs (MultiGpuContext, tsp_group_*: no sharded velocities) and periodic tiling."""
 import copy
 
 import numpy as np
 
 from . import _native, config, kernel_lut, loader, particle_buffers, sph
 from .drawreason import DrawReason
+from .frames import FrameInterface
 
 KINDS = ("v_los", "sigma_los")
 DEFAULT_COLORMAPS = {"v_los": "RdBu_r", "sigma_los": config.DEFAULT_COLORMAP}      # diverging about 0; the density default
-PARAMETERS = ("vmin", "vmax", "colormap_name")
+DEFAULT_LABELS = {"v_los": r"$v_{\rm los}$", "sigma_los": r"$\sigma_{\rm los}$"}
+PARAMETERS = ("vmin", "vmax", "colormap_name", "log")
 LUT_POINTS = 1000
 _WHICH = {"v_los": 1, "sigma_los": 2}       # the channel of tsp_velocity_moments' maps
+_PRESENT_MAP = {"v_los": "moment-mean", "sigma_los": "moment-sigma"}        # the base of Context.present
 
 
 def check_v_ref(v_ref):
@@ -65,15 +73,40 @@ def sigma_los_range(sigma_los):
     return (lo, hi) if hi > lo else (lo, lo + 1.0)
 
 
-def resolve_range(kind, values, vmin=None, vmax=None):
+def log_range(lo, hi):
+    """The ends of an automatic range for a logarithmic map, which compares log10 of the value with vmin and vmax: log10 of the
+    linear ends; a lower end that has no logarithm lies 3 dex below the upper one."""
+    hi = float(np.log10(hi)) if hi > 0.0 else 0.0
+    lo = float(np.log10(lo)) if lo > 0.0 else hi - 3.0
+    return (lo, hi) if hi > lo else (lo, lo + 1.0)
+
+
+def device_range(context, kind):
+    """v_los_range / sigma_los_range of the context's kinematic image, to the bit, from a device sort of the map (moment_sort) and
+    the few order statistics numpy's float64 percentile reads (content_values)."""
+    from .colormap.implementation import percentile_f64_from_order_statistics
+    n = context.moment_sort(_WHICH[check_kind(kind)], absolute=kind == "v_los")
+    if kind == "v_los":
+        top = float(percentile_f64_from_order_statistics(context.content_values, 0, n, 99.0)) if n else 0.0
+        top = top if top > 0.0 else 1.0
+        return -top, top
+    if not n:
+        return 0.0, 1.0
+    lo, hi = (float(v) for v in percentile_f64_from_order_statistics(context.content_values, 0, n, [1.0, 99.0]))
+    return (lo, hi) if hi > lo else (lo, lo + 1.0)
+
+
+def resolve_range(kind, values, vmin=None, vmax=None, log=False):
     """(vmin, vmax) of a map: what was set, the rest from the default rule of its kind; a v_los range with only one end set is
-    symmetric about 0."""
+    symmetric about 0.  `values`: the map, or a callable that returns the default rule's range (the device's).  log: the map is
+    logarithmic (sigma_los only), so the automatic ends are log_range's."""
     check_kind(kind)
     if vmin is None or vmax is None:
         if kind == "v_los" and (vmin is None) != (vmax is None):
             auto = (-float(vmax), None) if vmin is None else (None, -float(vmin))
         else:
-            auto = (v_los_range if kind == "v_los" else sigma_los_range)(values)
+            auto = values() if callable(values) else (v_los_range if kind == "v_los" else sigma_los_range)(values)
+            auto = log_range(*auto) if log else auto
         vmin = auto[0] if vmin is None else vmin
         vmax = auto[1] if vmax is None else vmax
     vmin, vmax = float(vmin), float(vmax)
@@ -100,16 +133,20 @@ class VelocityView:
                              f"from_arrays(..., vel=vel)")
         self._v_ref_option = check_v_ref(v_ref)
         self._v_ref_cache = None            # (centre, scale, v_cen) of the last "center"
-        self._params = {kind: {"vmin": None, "vmax": None, "colormap_name": DEFAULT_COLORMAPS[kind]} for kind in KINDS}
-        for key, value in parameters.items():       # v_los_vmax=..., sigma_los_colormap_name=...
-            if key not in self._parameter_names():
-                raise ValueError(f"unknown parameter {key!r}: one of {sorted(self._parameter_names())}")
-            setattr(self, key, value)
+        self._init_parameters(parameters)
         self._vis = visualizer
         self._sph = sph.KinematicSPH(visualizer, visualizer._render_resolution,
                                      share_render_progression=copy.copy(visualizer._sph._render_progression))
         self._luts = {}
         self._sync_camera()
+
+    def _init_parameters(self, parameters):
+        self._params = {kind: {"vmin": None, "vmax": None, "colormap_name": DEFAULT_COLORMAPS[kind], "log": False} for kind in KINDS}
+        self._frames = {}
+        for key, value in parameters.items():       # v_los_vmax=..., sigma_los_colormap_name=...
+            if key not in self._parameter_names():
+                raise ValueError(f"unknown parameter {key!r}: one of {sorted(self._parameter_names())}")
+            setattr(self, key, value)
 
     # -- camera and reference velocity: the visualizer's -----------------------------------------------
     def _camera(self):
@@ -184,19 +221,34 @@ class VelocityView:
         return self._luts[name]
 
     def get_range(self, kind):
-        """(vmin, vmax) get_presentation_image(kind) maps: what was set, else the default rule on the current maps."""
+        """(vmin, vmax) get_presentation_image(kind) maps: what was set, else the default rule on the current maps -- exactly
+        resolve_range(kind, get_maps()[kind], ...), taken from a sort of the map on the device (device_range): the maps are not
+        downloaded."""
         p = self._params[check_kind(kind)]
-        values = None if p["vmin"] is not None and p["vmax"] is not None else self.get_maps()[kind]
-        return resolve_range(kind, values, p["vmin"], p["vmax"])
+
+        def automatic():
+            self._ensure_rendered()
+            return device_range(self._sph._context, kind)
+        return resolve_range(kind, automatic, p["vmin"], p["vmax"], p["log"])
 
     def get_presentation_image(self, kind="v_los"):
         """(R, R, 4) uint8: the map `kind` ("v_los": a diverging colormap over a range symmetric about 0, out to the 99th percentile
         of |v_los|; "sigma_los": the density colormap from the 1st to the 99th percentile) -- view[kind, "vmin"], "vmax" and
-        "colormap_name" override.  Pixels without a value (NaN) take the colour of vmin."""
+        "colormap_name" override; with view["sigma_los", "log"] the map is of log10(sigma_los) and the ends are logarithms.  Pixels
+        without a value (NaN) take the colour of vmin.  The map on a canvas of any size, under a colorbar: frames(kind)."""
         vmin, vmax = self.get_range(kind)
         self._ensure_rendered()
         return self._sph._context.colormap_moment(_WHICH[kind], self._lut(self._params[kind]["colormap_name"]),
-                                                  np.float32(vmin), np.float32(vmax))
+                                                  np.float32(vmin), np.float32(vmax), self._params[kind]["log"])
+
+    def frames(self, kind="v_los", label=None):
+        """The map `kind` as a frame source (VelocityFrames, one per kind): get_presentation_image((W, H)) with colorbar and
+        scale bar, the 4:2:0 planes, and what topsy_amd.VisualizationRecorder needs.  label: the colorbar's label, when given."""
+        if check_kind(kind) not in self._frames:
+            self._frames[kind] = VelocityFrames(self, kind)
+        if label is not None:
+            self._frames[kind].label = label
+        return self._frames[kind]
 
     # -- parameters: view["v_los", "vmax"] = 250.0, or view.v_los_vmax = 250.0 ----------------------------
     @staticmethod
@@ -218,6 +270,10 @@ class VelocityView:
         if name == "colormap_name":
             if not isinstance(value, str):
                 raise ValueError(f"colormap_name must be a matplotlib colormap's name, not {value!r}")
+        elif name == "log":
+            value = bool(value)
+            if value and kind == "v_los":
+                raise ValueError("the v_los map has no logarithmic form: its range straddles 0")
         elif value is not None:
             value = float(value)
             if not np.isfinite(value):
@@ -242,6 +298,105 @@ def _parameter_property(kind, name):
 for _kind in KINDS:
     for _name in PARAMETERS:
         setattr(VelocityView, f"{_kind}_{_name}", _parameter_property(_kind, _name))
+
+
+class KinematicColormap:
+    """The colormap of a VelocityFrames as the small mapping the recorder reads and sets: "vmin", "vmax", "colormap_name" and "log"
+    are the view's (kind, name) parameters (None: automatic), "type" is "kinematic", any other key reads as None."""
+
+    def __init__(self, frames):
+        self._frames = frames
+
+    def __getitem__(self, key):
+        if key == "type":
+            return "kinematic"
+        return self._frames._view[self._frames.kind, key] if key in PARAMETERS else None
+
+    def __setitem__(self, key, value):
+        if key == "type":
+            if value != "kinematic":
+                raise ValueError(f"a kinematic map cannot become a colormap of type {value!r}")
+        elif key in PARAMETERS:
+            self._frames._view[self._frames.kind, key] = value
+        elif value is not None:
+            raise ValueError(f"a kinematic map has no parameter {key!r}")
+
+    get_parameter = __getitem__
+
+    def get_parameters(self):
+        """The parameters of the frame being composed: vmin and vmax are the range its base was resolved to."""
+        vmin, vmax = self._frames._resolved_range
+        return {"type": "kinematic", "vmin": vmin, "vmax": vmax, "colormap_name": self["colormap_name"], "log": self["log"]}
+
+
+class VelocityFrames(FrameInterface):
+    """One kinematic map of a VelocityView with the frame interface of a visualizer: camera, scene and parameters are the view's,
+    which are the visualizer's.  With view[kind, "vmin"] or "vmax" left None every frame resolves its own range from the device
+    sort, so the colorbar of a movie moves with the scene; colormap_autorange() pins the current range, which is how a movie gets
+    a fixed colorbar."""
+    canvas_format = "rgba8unorm"
+    _render_mode = "kinematic"
+
+    def __init__(self, view, kind, label=None):
+        self._view = view
+        self.kind = check_kind(kind)
+        self.label = label
+        self._vis = view._vis
+        self._sph = view._sph
+        self._colormap = KinematicColormap(self)
+        self._resolved_range = (None, None)
+        self._init_frames(view._vis.data_loader.get_position_units())
+
+    # -- the composed frame's base and colorbar (frames.FrameInterface) ------------------------------------
+    def _presentation_base(self, width, height):
+        view, p = self._view, self._view._params[self.kind]
+        view._ensure_rendered()     # the EXPORT frame at the visualizer's camera and v_ref, unless the target already holds it
+        vmin, vmax = view.get_range(self.kind)
+        self._resolved_range = (vmin, vmax)
+        return {"map": _PRESENT_MAP[self.kind], "lut": view._lut(p["colormap_name"]), "vmin": np.float32(vmin),
+                "vmax": np.float32(vmax), "log": p["log"]}
+
+    def _compose_frame(self, width, height, base, layers, yuv420):
+        ctx = self._sph._context
+        return (ctx.present_yuv420 if yuv420 else ctx.present)(width, height, base, layers)
+
+    def _has_colorbar(self):
+        return True
+
+    def _get_colorbar_label(self):
+        prefix = r"$\log_{10}$ " if self._view._params[self.kind]["log"] else ""
+        return prefix + (DEFAULT_LABELS[self.kind] if self.label is None else self.label)
+
+    def colormap_autorange(self):
+        """Pin the automatic range of the current scene and camera into view[kind, "vmin"] and view[kind, "vmax"]: the frames
+        that follow keep it (a fixed colorbar) until an end is set to None again, which makes every frame resolve its own."""
+        view, kind = self._view, self.kind
+        view[kind, "vmin"] = view[kind, "vmax"] = None
+        view[kind, "vmin"], view[kind, "vmax"] = view.get_range(kind)
+
+    # -- view state and parameters: the visualizer's and the view's ----------------------------------------
+    colormap = property(lambda self: self._colormap)
+    data_loader = property(lambda self: self._vis.data_loader)
+    rotation_matrix = property(lambda self: self._vis.rotation_matrix, lambda self, v: setattr(self._vis, "rotation_matrix", v))
+    scale = property(lambda self: self._vis.scale, lambda self, v: setattr(self._vis, "scale", v))
+    position_offset = property(lambda self: self._vis.position_offset, lambda self, v: setattr(self._vis, "position_offset", v))
+    quantity_name = property(lambda self: self._vis.quantity_name, lambda self, v: setattr(self._vis, "quantity_name", v))
+
+    def orient(self, orient, radius, center=None, method=None):
+        """The visualizer's orient: the camera is the visualizer's."""
+        return self._vis.orient(orient, radius, center=center, method=method)
+
+    def centre_on_halo(self, n):
+        """The visualizer's centre_on_halo: the camera is the visualizer's."""
+        return self._vis.centre_on_halo(n)
+
+    def profile(self, r_max=None, **kwargs):
+        """The visualizer's profile: the camera is the visualizer's."""
+        return self._vis.profile(r_max, **kwargs)
+
+    def scale_to_virial(self, rho_threshold, r_max, factor=1.0):
+        """The visualizer's scale_to_virial: the camera is the visualizer's."""
+        return self._vis.scale_to_virial(rho_threshold, r_max, factor)
 
 
 def check_maps_arguments(pos, smooth, mass, vel, rotation, center, scale, resolution):
