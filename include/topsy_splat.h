@@ -262,7 +262,8 @@ int tsp_colormap_rgb_host(tsp_context *ctx, const float *img, int H, int W, int 
  * src/topsy/periodic_sph.py:36-88, shaders/overlay.wgsl:18-51): one full-viewport quad per instance
  * displaced by offsets_xy[k] (clip units, +y up), sampled with a linear filter and clamp-to-edge,
  * additively blended into a cleared target.  The float64 accumulator keeps the untiled render, so a
- * later tsp_render(clear = 0) continues from the raw image and the tiling is re-applied afterwards. */
+ * later tsp_render(clear = 0) continues from the raw image and the tiling is re-applied afterwards.  TSP_ESTATE, nothing changed,
+ * while the accumulator holds the keys of tsp_render_surface (a surface image has no tiling). */
 int tsp_tile_periodic(tsp_context *ctx, int n, const float *offsets_xy, const float *weights);
 
 /* SPH smoothing lengths by k-nearest neighbours (the pynbody.sph.smooth call of reference loader.py:222-240).

@@ -351,13 +351,14 @@ int tsp_upload_particles(tsp_context *ctx, int64_t n, const float *x, const floa
 
 int tsp_upload_quantity(tsp_context *ctx, const float *q) {
     TSP_REQUIRE(ctx, TSP_EINVAL, "NULL context");
+    TSP_REQUIRE(!q || ctx->p.n > 0, TSP_ESTATE, "upload particles before the quantity");
     TSP_HIP(hipSetDevice(ctx->device));
+    ctx->forget_render_undo();                           // (an upload ends the validity of tsp_render_undo: topsy_splat.h)
     if (!q) {
         if (ctx->p.q) TSP_HIP(hipFree(ctx->p.q));
         ctx->p.q = nullptr;
         return TSP_OK;
     }
-    TSP_REQUIRE(ctx->p.n > 0, TSP_ESTATE, "upload particles before the quantity");
     int rc = upload_permuted(ctx, &ctx->p.q, q, ctx->p.n);
     if (rc) return rc;
     TSP_HIP(hipStreamSynchronize(ctx->stream));
@@ -368,6 +369,7 @@ int tsp_upload_rgb(tsp_context *ctx, const float *r, const float *g, const float
     TSP_REQUIRE(ctx && r && g && b, TSP_EINVAL, "NULL argument");
     TSP_REQUIRE(ctx->p.n > 0, TSP_ESTATE, "upload particles before rgb");
     TSP_HIP(hipSetDevice(ctx->device));
+    ctx->forget_render_undo();
     int rc;
     if ((rc = upload_permuted(ctx, &ctx->p.r, r, ctx->p.n))) return rc;
     if ((rc = upload_permuted(ctx, &ctx->p.g, g, ctx->p.n))) return rc;
@@ -380,8 +382,10 @@ int tsp_upload_rgb(tsp_context *ctx, const float *r, const float *g, const float
 int tsp_upload_velocities(tsp_context *ctx, const float *vx, const float *vy, const float *vz) {
     TSP_REQUIRE(ctx, TSP_EINVAL, "NULL context");
     TSP_REQUIRE((vx && vy && vz) || (!vx && !vy && !vz), TSP_EINVAL, "vx, vy and vz must be given together or not at all");
-    TSP_HIP(hipSetDevice(ctx->device));
     Particles &p = ctx->p;
+    TSP_REQUIRE(!vx || p.n > 0, TSP_ESTATE, "upload particles before the velocities");
+    TSP_HIP(hipSetDevice(ctx->device));
+    ctx->forget_render_undo();
     if (p.wrgb_source == W_KINEMATIC) p.wrgb_source = W_NONE;     // (the weights were formed from the velocities that go)
     if (!vx) {
         float **arrs[] = {&p.vx, &p.vy, &p.vz};
@@ -391,7 +395,6 @@ int tsp_upload_velocities(tsp_context *ctx, const float *vx, const float *vy, co
         }
         return TSP_OK;
     }
-    TSP_REQUIRE(p.n > 0, TSP_ESTATE, "upload particles before the velocities");
     int rc;
     if ((rc = upload_permuted(ctx, &p.vx, vx, p.n))) return rc;
     if ((rc = upload_permuted(ctx, &p.vy, vy, p.n))) return rc;
@@ -442,6 +445,7 @@ int tsp_upload_band_magnitudes(tsp_context *ctx, int n_bands, const double *mags
     TSP_REQUIRE(n_bands >= 1 && n_bands <= 64, TSP_EINVAL, "n_bands %d out of range", n_bands);
     TSP_REQUIRE(ctx->p.n > 0, TSP_ESTATE, "upload particles before the band magnitudes");
     TSP_HIP(hipSetDevice(ctx->device));
+    ctx->forget_render_undo();
     const int64_t n = ctx->p.n;
     DeviceScratch d_mags, d_w;
     TSP_SCRATCH_ALLOC(ctx, SITE("band_magnitudes"), d_mags, (size_t)n_bands * n * sizeof(double));
