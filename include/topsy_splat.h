@@ -103,7 +103,8 @@ const char *tsp_last_error(void);
  * 118: new entry point tsp_render_undo; tsp_group_render draws a block on every member or on none (it used to leave the block in
  * the accumulators of the members that had succeeded); no struct changed, nothing else changed.
  * 119: kinematic frames: the bases TSP_PRESENT_MOMENT_MEAN / TSP_PRESENT_MOMENT_SIGMA of tsp_present and tsp_present_yuv420 (values
- * that returned TSP_EINVAL before) and the new entry point tsp_moment_sort; no struct changed, nothing else changed. */
+ * that returned TSP_EINVAL before) and the new entry point tsp_moment_sort; no struct changed, nothing else changed.
+ * 120: new entry point tsp_sph_velocity_gradient (velocity divergence and curl by SPH gather sums); nothing else changed. */
 int tsp_version(void);
 int tsp_stats_size(void);
 
@@ -302,6 +303,41 @@ int tsp_smoothing_lengths(tsp_context *ctx, int64_t n, const float *x, const flo
  * returns TSP_ENOMEM and writes nothing. */
 int tsp_sph_sum(tsp_context *ctx, int64_t n, const float *x, const float *y, const float *z, const float *h,
                 const float *a, float period, float *out);
+
+/* Divergence and curl of the velocity at the particles by SPH gather sums: what pynbody derives as 'v_div' and 'v_curl' (the
+ * norm of the curl is its 'vorticity').  Host arrays in and out, caller's order; uses ctx's device and stream only: resident
+ * particles, image, accumulator and tsp_stats unchanged.  Float32 unless said otherwise, with these operations in this order (no
+ * fused multiply-adds):
+ *   - Particle i is valid iff x[i], y[i], z[i] are finite.  A query i is answerable iff it is valid and h[i] is finite and > 0.
+ *     The four outputs of a query that is not answerable are NaN.  Invalid particles are nobody's neighbour.  mass, rho, vx, vy,
+ *     vz are used as given (a NaN or an infinity propagates into every sum it takes part in).
+ *   - For an answerable i, over every valid j:
+ *         dx, dy, dz, d2 exactly as tsp_smoothing_lengths defines them (x[j] - x[i], nearest image when period > 0);
+ *         u = sqrtf(d2) / h[i];  the term exists iff d2 > 0 and u < 2 (the particle itself and exact duplicates contribute
+ *         nothing);
+ *         t = 2 - u;  f = u < 1 ? 3.0f - 2.25f * u : (0.75f * (t * t)) / u      (-w'(u) / u of the M4 spline w of tsp_sph_sum);
+ *         c = mass[j] * f;  dvx = vx[j] - vx[i] (dvy, dvz alike);
+ *         term_div = c * ((dvx * dx + dvy * dy) + dvz * dz);
+ *         term_cx = c * (dy * dvz - dz * dvy);  term_cy = c * (dz * dvx - dx * dvz);  term_cz = c * (dx * dvy - dy * dvx);
+ *         four float64 sums, S += (double)term.
+ *     hd = (double)h[i];  den = M_PI * (((hd * hd) * (hd * hd)) * hd) * (double)rho[i];  each output is (float)(S / den).
+ *   - The order of the sums is free but fixed (no atomics in them): the same call on the same input and device returns the same
+ *     bits.  Two orders differ by the float64 rounding of the sums only: with T terms and A = sum |term| / |den|, by at most
+ *     2 T 2^-53 A before the rounding to float32.
+ * This is the usual difference-form estimate, pynbody's convention:
+ *     div v_i = (1 / rho_i) sum_j m_j (v_j - v_i) . grad_i W(r_ij, h_i),   curl v_i = (1 / rho_i) sum_j m_j grad_i W x (v_j - v_i),
+ * with rho from tsp_sph_sum(a = mass) on the same h.  It is exactly zero for a uniform velocity field.  It is not exact for a
+ * linear one, and it is biased low on disordered particles, because rho_i contains the self term and the sums do not: for
+ * v = A x it returns about 0.77 of trace(A) and of the antisymmetric part on Poisson points with 32 neighbours, 0.981 on a cubic
+ * lattice with h = 1.2 spacings.  (A matrix-corrected, linear-exact estimator is a different sum.)
+ * 1 <= n < 2^31, period = 0 (open box) or finite and > 0, no NULL array (the outputs included); anything else returns
+ * TSP_EINVAL and writes nothing.  The cost is proportional to the candidates scanned, as for tsp_sph_sum.  Device memory is
+ * allocated for the call only (about 88 bytes per particle: the index and h as for tsp_sph_sum, 20 for the five fields, 16 for
+ * the (mass, velocity) records in Morton order; the results reuse what is free by then); a failed allocation returns TSP_ENOMEM and
+ * writes nothing. */
+int tsp_sph_velocity_gradient(tsp_context *ctx, int64_t n, const float *x, const float *y, const float *z, const float *h,
+                              const float *mass, const float *rho, const float *vx, const float *vy, const float *vz,
+                              float period, float *div_out, float *curl_x_out, float *curl_y_out, float *curl_z_out);
 
 /* The shrinking-sphere centre of a snapshot (Power et al. 2003): what pynbody.analysis.halo.center computes by default and the
  * reference asks for when it centres a snapshot at load (PynbodyDataLoader._perform_centering, src/topsy/loader.py:201-217, with

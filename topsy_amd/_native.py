@@ -18,8 +18,8 @@ SAMPLE_BILINEAR_MIP0, SAMPLE_BILINEAR_MIP = 0x10, 0x20      # diagnostic samplin
 UNIQUE_ID_BYTES = 128
 ABI_VERSION = 112            # the oldest tsp_version() whose structs this binding matches; entry points added since
                              # (113: tsp_shrink_sphere_center, 114: tsp_fof_groups, 115: tsp_sphere_moments,
-                             # 116: tsp_radial_profile, 117: the kinematic maps, 119: tsp_moment_sort) are required by name in
-                             # load_library()
+                             # 116: tsp_radial_profile, 117: the kinematic maps, 119: tsp_moment_sort,
+                             # 120: tsp_sph_velocity_gradient) are required by name in load_library()
 PRESENT_SCALAR, PRESENT_BIVARIATE, PRESENT_RGB, PRESENT_RGB_HDR, PRESENT_MOMENT_MEAN, PRESENT_MOMENT_SIGMA = 0, 1, 2, 3, 4, 5
 LAYER_QUAD, LAYER_LINES = 0, 1
 
@@ -162,6 +162,7 @@ SIGNATURES = {
     "tsp_tile_periodic": (ctypes.c_int, [_ctx, ctypes.c_int, _fp, _fp]),
     "tsp_smoothing_lengths": (ctypes.c_int, [_ctx, ctypes.c_int64, _fp, _fp, _fp, ctypes.c_int, ctypes.c_float, _fp]),
     "tsp_sph_sum": (ctypes.c_int, [_ctx, ctypes.c_int64, _fp, _fp, _fp, _fp, _fp, ctypes.c_float, _fp]),
+    "tsp_sph_velocity_gradient": (ctypes.c_int, [_ctx, ctypes.c_int64] + [_fp] * 9 + [ctypes.c_float] + [_fp] * 4),
     "tsp_shrink_sphere_center": (ctypes.c_int, [_ctx, ctypes.c_int64, _fp, _fp, _fp, _fp, ctypes.c_float, ctypes.c_double,
                                                 ctypes.c_double, ctypes.c_int64, ctypes.c_int, ctypes.POINTER(ctypes.c_double),
                                                 ctypes.POINTER(CenterInfo)]),
@@ -484,6 +485,21 @@ class Context:
         _check(self._lib.tsp_sph_sum(self._h, n, _ptr(x), _ptr(y), _ptr(z), _ptr(h), _ptr(a), float(np.float32(period or 0.0)),
                                      _ptr(out)))
         return out
+
+    def sph_velocity_gradient(self, x, y, z, h, mass, rho, vx, vy, vz, period=None):
+        """Divergence and curl of the velocity at caller-ordered float32 particles by SPH gather sums
+        (tsp_sph_velocity_gradient): (1 / rho_i) sum_j m_j (v_j - v_i) . grad_i W(r_ij, h_i) and the like cross product, with the
+        M4 spline of support 2 h[i] -- pynbody's 'v_div' and 'v_curl'.  Returns (div (n,), curl (n, 3)) float32; NaN where a
+        coordinate is not finite or h is not finite and > 0.  period: the side of a periodic box (None or 0: open).  Uses this
+        context's device only; what is resident stays."""
+        n = len(x)
+        arrs = [_f32(a, n, name) for a, name in ((x, "x"), (y, "y"), (z, "z"), (h, "h"), (mass, "mass"), (rho, "rho"), (vx, "vx"),
+                                                 (vy, "vy"), (vz, "vz"))]
+        div = np.empty(n, dtype=np.float32)
+        planes = np.empty((3, n), dtype=np.float32)
+        _check(self._lib.tsp_sph_velocity_gradient(self._h, n, *[_ptr(a) for a in arrs], float(np.float32(period or 0.0)),
+                                                   _ptr(div), _ptr(planes[0]), _ptr(planes[1]), _ptr(planes[2])))
+        return div, np.ascontiguousarray(planes.T)
 
     def shrink_sphere_center(self, x, y, z, mass, mass_cut_factor=0.0, r_start=0.0, shrink_factor=0.7, min_particles=100,
                              max_iterations=256):

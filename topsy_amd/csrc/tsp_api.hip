@@ -221,7 +221,7 @@ using namespace tsp;
 extern "C" {
 
 const char *tsp_last_error(void) { return g_err; }
-int tsp_version(void) { return 119; }     // 119: tsp_moment_sort, TSP_PRESENT_MOMENT_MEAN / _SIGMA (the kinematic maps as the base of tsp_present / tsp_present_yuv420); 118: tsp_render_undo, tsp_group_render all-or-nothing across the members; 117: kinematic maps (tsp_upload_velocities, tsp_set_line_of_sight, TSP_MODE_KINEMATIC, tsp_velocity_moments, tsp_colormap_moment); 116: tsp_radial_profile; 115: tsp_sphere_moments; 114: tsp_fof_groups; 113: tsp_shrink_sphere_center; 112: tsp_present_surface, tsp_present_surface_yuv420; 111: tsp_content_neg_inf; 110: tsp_sph_sum; 109: tsp_present_yuv420; 108: tsp_present; 107: surface rendering; 106: tsp_smoothing_lengths; 101: tsp_stats gained ms_mega, n_mega (16 bytes); 102: the per-kernel fragment counts (32 bytes); 103: n_chunk_culled (8 bytes); 104: matrix-core / kernel-I options removed; 105: kernel M's options removed (kernel G draws the mid footprints)
+int tsp_version(void) { return 120; }     // 120: tsp_sph_velocity_gradient; 119: tsp_moment_sort, TSP_PRESENT_MOMENT_MEAN / _SIGMA (the kinematic maps as the base of tsp_present / tsp_present_yuv420); 118: tsp_render_undo, tsp_group_render all-or-nothing across the members; 117: kinematic maps (tsp_upload_velocities, tsp_set_line_of_sight, TSP_MODE_KINEMATIC, tsp_velocity_moments, tsp_colormap_moment); 116: tsp_radial_profile; 115: tsp_sphere_moments; 114: tsp_fof_groups; 113: tsp_shrink_sphere_center; 112: tsp_present_surface, tsp_present_surface_yuv420; 111: tsp_content_neg_inf; 110: tsp_sph_sum; 109: tsp_present_yuv420; 108: tsp_present; 107: surface rendering; 106: tsp_smoothing_lengths; 101: tsp_stats gained ms_mega, n_mega (16 bytes); 102: the per-kernel fragment counts (32 bytes); 103: n_chunk_culled (8 bytes); 104: matrix-core / kernel-I options removed; 105: kernel M's options removed (kernel G draws the mid footprints)
 int tsp_stats_size(void) { return (int)sizeof(tsp_stats); }
 
 int tsp_device_count(void) {
@@ -938,7 +938,23 @@ int tsp_sph_sum(tsp_context *ctx, int64_t n, const float *x, const float *y, con
     TSP_REQUIRE(period == 0.0f || (std::isfinite(period) && period > 0.0f), TSP_EINVAL,
                 "period must be 0 (open box) or finite and > 0, not %g", (double)period);
     TSP_HIP(hipSetDevice(ctx->device));
-    return sph_sum(ctx, n, x, y, z, h, a, period == 0.0f ? 0.0f : period, out);
+    const float *fields[1] = {a};
+    float *outs[1] = {out};
+    return sph_sum(ctx, n, x, y, z, h, SPH_GATHER_SUM, fields, 1, period == 0.0f ? 0.0f : period, outs, 1);
+}
+
+int tsp_sph_velocity_gradient(tsp_context *ctx, int64_t n, const float *x, const float *y, const float *z, const float *h,
+                              const float *mass, const float *rho, const float *vx, const float *vy, const float *vz, float period,
+                              float *div_out, float *curl_x_out, float *curl_y_out, float *curl_z_out) {
+    TSP_REQUIRE(ctx && x && y && z && h && mass && rho && vx && vy && vz && div_out && curl_x_out && curl_y_out && curl_z_out,
+                TSP_EINVAL, "NULL argument");
+    TSP_REQUIRE(n >= 1 && n < (1ll << 31), TSP_EINVAL, "n = %lld outside [1, 2^31)", (long long)n);
+    TSP_REQUIRE(period == 0.0f || (std::isfinite(period) && period > 0.0f), TSP_EINVAL,
+                "period must be 0 (open box) or finite and > 0, not %g", (double)period);
+    TSP_HIP(hipSetDevice(ctx->device));
+    const float *fields[5] = {mass, rho, vx, vy, vz};
+    float *outs[4] = {div_out, curl_x_out, curl_y_out, curl_z_out};
+    return sph_sum(ctx, n, x, y, z, h, SPH_GATHER_VELOCITY_GRADIENT, fields, 5, period == 0.0f ? 0.0f : period, outs, 4);
 }
 
 int tsp_shrink_sphere_center(tsp_context *ctx, int64_t n, const float *x, const float *y, const float *z, const float *mass,

@@ -292,8 +292,12 @@ int content_sort(tsp_context *ctx, int kind, float scale, int64_t *n_finite, int
 int ensure_array(float **p, int64_t n);
 int smoothing_lengths(tsp_context *ctx, int64_t n, const float *x, const float *y, const float *z, int k, float period,
                       float *h_out);   // tsp_smooth.hip: per-call DeviceScratch only, no context state
-int sph_sum(tsp_context *ctx, int64_t n, const float *x, const float *y, const float *z, const float *h, const float *a,
-            float period, float *out);       // tsp_smooth.hip: the gather-form SPH sum on the same index; per-call DeviceScratch only
+// tsp_smooth.hip: the gather-form SPH sums on the same index (tsp_sph_sum, tsp_sph_velocity_gradient); per-call DeviceScratch only.
+// SPH_GATHER_SUM: fields = {a}, outs = {out}.  SPH_GATHER_VELOCITY_GRADIENT: fields = {mass, rho, vx, vy, vz}, outs = {div,
+// curl_x, curl_y, curl_z}.
+enum { SPH_GATHER_SUM = 0, SPH_GATHER_VELOCITY_GRADIENT = 1 };
+int sph_sum(tsp_context *ctx, int64_t n, const float *x, const float *y, const float *z, const float *h, int mode,
+            const float *const *fields, int n_fields, float period, float *const *outs, int n_outs);
 // tsp_fof.hip: friends-of-friends groups over the index of tsp_morton.h; per-call DeviceScratch only, no context state
 int fof_groups(tsp_context *ctx, int64_t n, const float *x, const float *y, const float *z, float linking_length, float period,
                int64_t min_members, int32_t *group_out, tsp_fof_info *info_out);

@@ -1,5 +1,5 @@
 // tsp_morton.h -- the Morton index over caller-ordered host positions and the exact float32 fixed-radius range query over it:
-// what tsp_smooth.hip (tsp_smoothing_lengths, tsp_sph_sum) and tsp_fof.hip (tsp_fof_groups) share.
+// what tsp_smooth.hip (tsp_smoothing_lengths, tsp_sph_sum, tsp_sph_velocity_gradient) and tsp_fof.hip (tsp_fof_groups) share.
 //
 // The index (build_morton_index, tsp_smooth.hip): bounding box of the finite positions; 63-bit Morton keys of the positions
 // quantised to 2^21 steps per axis (a periodic box: the positions wrapped into [0, L), for binning only -- distances always
@@ -71,6 +71,18 @@ static __device__ __forceinline__ float min_image(float d, float period) {
 }
 static __device__ __forceinline__ float dist2(float qx, float qy, float qz, float px, float py, float pz, float period) {
     float dx = px - qx, dy = py - qy, dz = pz - qz;
+    if (period > 0.0f) {
+        dx = min_image(dx, period);
+        dy = min_image(dy, period);
+        dz = min_image(dz, period);
+    }
+    return (dx * dx + dy * dy) + dz * dz;
+}
+// The displacement itself, p - q at the nearest image, for the sums that need its direction (tsp_sph_velocity_gradient); returns
+// d2 formed from it by the operations of dist2 in dist2's order, so the bits are dist2's.
+static __device__ __forceinline__ float displacement(float qx, float qy, float qz, float px, float py, float pz, float period,
+                                                     float &dx, float &dy, float &dz) {
+    dx = px - qx, dy = py - qy, dz = pz - qz;
     if (period > 0.0f) {
         dx = min_image(dx, period);
         dy = min_image(dy, period);

@@ -24,6 +24,8 @@
 //
 // tsp_sph_sum, the gather-form SPH sum (with a = mass: the density pynbody derives as 'rho'), is a range query of radius 2 h[i]
 // over the same index (step 1 is shared: build_morton_index); its kernel is described at sph_sum_kernel below.
+// tsp_sph_velocity_gradient, the divergence and curl of the velocity (pynbody's 'v_div' and 'v_curl'), is the same range query
+// with four sums per query (sph_velocity_gradient_kernel); one host routine, sph_sum(), serves both calls.
 #include <hipcub/hipcub.hpp>
 
 #include <math.h>
@@ -265,6 +267,129 @@ __global__ __launch_bounds__(256) void sph_sum_kernel(const float *__restrict__ 
     }
 }
 
+// ---- tsp_sph_velocity_gradient: divergence and curl of the velocity by the same gather ------------------------------------------
+// gather of the per-query h and rho and of the per-candidate payload (mass, vx, vy, vz: one 16-byte load) into Morton order
+__global__ __launch_bounds__(256) void sph_gather_velocity_kernel(const float *__restrict__ h, const float *__restrict__ mass,
+                                                                  const float *__restrict__ rho, const float *__restrict__ vx,
+                                                                  const float *__restrict__ vy, const float *__restrict__ vz,
+                                                                  const uint32_t *__restrict__ idx, int64_t nv,
+                                                                  float *__restrict__ sh, float *__restrict__ srho,
+                                                                  float4 *__restrict__ smv) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nv; i += (int64_t)gridDim.x * blockDim.x) {
+        const uint32_t j = idx[i];
+        sh[i] = h[j];
+        srho[i] = rho[j];
+        smv[i] = make_float4(mass[j], vx[j], vy[j], vz[j]);
+    }
+}
+
+// The contract's four terms for a candidate at displacement (dx, dy, dz), squared distance d2: float32, these operations in this
+// order; no term when d2 == 0 (the particle itself, an exact duplicate) or u >= 2.  mv = (mass, vx, vy, vz) of the candidate.
+__device__ __forceinline__ void velocity_gradient_term(float dx, float dy, float dz, float d2, float4 mv, float hq, float qvx,
+                                                       float qvy, float qvz, double (&S)[4], unsigned &terms) {
+    const float u = __fdiv_rn(sqrtf(d2), hq);
+    if (d2 > 0.0f && u < 2.0f) {
+        const float t = 2.0f - u;
+        const float f = u < 1.0f ? 3.0f - 2.25f * u : __fdiv_rn(0.75f * (t * t), u);
+        const float c = mv.x * f;
+        const float dvx = mv.y - qvx, dvy = mv.z - qvy, dvz = mv.w - qvz;
+        S[0] += (double)(c * ((dvx * dx + dvy * dy) + dvz * dz));
+        S[1] += (double)(c * (dy * dvz - dz * dvy));
+        S[2] += (double)(c * (dz * dvx - dx * dvz));
+        S[3] += (double)(c * (dx * dvy - dy * dvx));
+        ++terms;
+    }
+}
+
+// The range query of sph_sum_kernel (step A: a lane per query finds its runs, into LDS; step B: a wave per query scans them 64
+// candidates at a time) with four float64 partial sums per lane, each added over the wave by the same fixed butterfly.  A candidate
+// is three position loads and one 16-byte load; the query's own velocity is its own payload entry.
+// Block size 256 as there: the two run tables are 16 KiB of LDS, of which ten blocks fit in a CU's 160 KiB, more than the eight
+// blocks of four waves that its 32 wave slots take -- LDS does not limit the occupancy.  Registers do: the four double partials,
+// the wider candidate and the query's velocity bring the kernel to 80 VGPRs, six waves per SIMD (sph_sum_kernel: 57, eight), with
+// no spill.  A block of 128 would halve the tables and change neither figure.
+__global__ __launch_bounds__(256) void sph_velocity_gradient_kernel(const float *__restrict__ sx, const float *__restrict__ sy,
+                                                                    const float *__restrict__ sz, const float *__restrict__ sh,
+                                                                    const float *__restrict__ srho, const float4 *__restrict__ smv,
+                                                                    const uint64_t *__restrict__ keys, int64_t nv, Grid g,
+                                                                    float *__restrict__ div_sorted, float *__restrict__ cx_sorted,
+                                                                    float *__restrict__ cy_sorted, float *__restrict__ cz_sorted,
+                                                                    unsigned long long *counters) {
+    __shared__ uint32_t run_b[256][8], run_e[256][8];
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int lane = threadIdx.x & 63, wave0 = threadIdx.x & ~63;
+    const float L = g.period;
+    unsigned long long scanned = 0, steps = 0;
+    unsigned terms = 0;
+    float hq = 0.0f, qx = 0.0f, qy = 0.0f, qz = 0.0f, reach2 = 0.0f, qvx = 0.0f, qvy = 0.0f, qvz = 0.0f;
+    bool answerable = false;
+    for (int r = 0; r < 8; ++r) run_b[threadIdx.x][r] = run_e[threadIdx.x][r] = 0;
+    if (i < nv) {
+        hq = sh[i];
+        answerable = __builtin_isfinite(hq) && hq > 0.0f;
+    }
+    if (answerable) {
+        qx = sx[i], qy = sy[i], qz = sz[i];
+        const float4 own = smv[i];
+        qvx = own.y, qvy = own.z, qvz = own.w;
+        // every term has sqrtf(d2) / hq < 2, so d2 <= reach2 (see sph_sum_kernel)
+        const float reach = (2.0f * hq) * CULL_SLACK;
+        const float R = reach + g.eps;
+        reach2 = reach * reach >= 1e-30f ? reach * reach : __builtin_inff();
+        const double cull2 = ((double)reach * (double)reach) * (double)CULL_SLACK;
+        scanned = for_each_run(g, keys, nv, qx, qy, qz, R, cull2, [&](int combo, int64_t b, int64_t e) {
+            run_b[threadIdx.x][combo] = (uint32_t)b;      // (nv < 2^31)
+            run_e[threadIdx.x][combo] = (uint32_t)e;
+        });
+    }
+    __syncthreads();
+
+    double S[4] = {0.0, 0.0, 0.0, 0.0};
+    const unsigned long long todo = __ballot(answerable);
+    for (int l = 0; l < 64; ++l) {
+        if (!((todo >> l) & 1)) continue;                   // (uniform over the wave)
+        const float lx = __shfl(qx, l), ly = __shfl(qy, l), lz = __shfl(qz, l), lh = __shfl(hq, l), lreach2 = __shfl(reach2, l);
+        const float lvx = __shfl(qvx, l), lvy = __shfl(qvy, l), lvz = __shfl(qvz, l);
+        double part[4] = {0.0, 0.0, 0.0, 0.0};
+        for (int r = 0; r < 8; ++r) {
+            const int64_t b = run_b[wave0 + l][r], e = run_e[wave0 + l][r];
+            for (int64_t j = b + lane; j < e; j += 64) {
+                float dx, dy, dz;
+                const float d2 = displacement(lx, ly, lz, sx[j], sy[j], sz[j], L, dx, dy, dz);
+                if (d2 <= lreach2) velocity_gradient_term(dx, dy, dz, d2, smv[j], lh, lvx, lvy, lvz, part, terms);
+            }
+            steps += (unsigned long long)((e - b + 63) >> 6);
+        }
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            for (int off = 32; off; off >>= 1) part[c] += __shfl_xor(part[c], off);
+            if (lane == l) S[c] = part[c];
+        }
+    }
+    if (i < nv) {
+        float out[4];
+        const double hd = (double)hq;
+        const double den = M_PI * (((hd * hd) * (hd * hd)) * hd) * (double)(answerable ? srho[i] : 0.0f);
+#pragma unroll
+        for (int c = 0; c < 4; ++c) out[c] = answerable ? (float)(S[c] / den) : __builtin_nanf("");
+        div_sorted[i] = out[0];
+        cx_sorted[i] = out[1];
+        cy_sorted[i] = out[2];
+        cz_sorted[i] = out[3];
+    }
+
+    unsigned long long nterms = terms;
+    for (int off = 32; off; off >>= 1) {
+        scanned += __shfl_xor(scanned, off);
+        nterms += __shfl_xor(nterms, off);
+    }
+    if (lane == 0 && scanned) {
+        atomicAdd(&counters[0], scanned);
+        atomicAdd(&counters[1], nterms);
+        atomicAdd(&counters[2], steps);
+    }
+}
+
 }  // namespace
 
 // Step 1 of every entry point over the index (tsp_morton.h).
@@ -393,46 +518,85 @@ int smoothing_lengths(tsp_context *ctx, int64_t n, const float *x, const float *
     return TSP_OK;
 }
 
-int sph_sum(tsp_context *ctx, int64_t n, const float *x, const float *y, const float *z, const float *h, const float *a,
-            float period, float *out) {
+// The host side of both gather calls over the index.  mode SPH_GATHER_SUM: fields = {a}, outs = {out} (tsp_sph_sum);
+// SPH_GATHER_VELOCITY_GRADIENT: fields = {mass, rho, vx, vy, vz}, outs = {div, curl_x, curl_y, curl_z}.
+// Device memory beyond the index: the raw h ("sph_sum_h", n floats) and one buffer ("sph_sum_a") partitioned by offsets --
+//   sum:      [a: n]                                                                        (4 bytes per particle)
+//   gradient: [mass, rho, vx, vy, vz: 5 n, padded to 16 bytes][(mass, vx, vy, vz) sorted: 4 nv]   (36 bytes per particle)
+// -- and the buffers of the index that are free once the positions are gathered: the raw y and z hold the sorted h and the sorted
+// second per-query field (a | rho).  The sorted results go where nothing is read any more (sum: the unsorted index buffer;
+// gradient: the first four raw planes, dead once they are gathered), the results in the caller's order into the raw x (sum) or the
+// raw x, the raw h, the unsorted index buffer and the fifth raw plane (gradient).  The stream orders every reuse.
+int sph_sum(tsp_context *ctx, int64_t n, const float *x, const float *y, const float *z, const float *h, int mode,
+            const float *const *fields, int n_fields, float period, float *const *outs, int n_outs) {
+    const bool gradient = mode == SPH_GATHER_VELOCITY_GRADIENT;
+    const char *who = gradient ? "tsp_sph_velocity_gradient" : "tsp_sph_sum";
+    TSP_REQUIRE(n_fields == (gradient ? 5 : 1) && n_outs == (gradient ? 4 : 1), TSP_EINVAL, "%s: %d fields and %d outputs", who,
+                n_fields, n_outs);
     hipStream_t st = ctx->stream;
     const size_t fbytes = (size_t)n * sizeof(float);
     MortonIndex ix;
-    const int rc = build_morton_index(ctx, "tsp_sph_sum", n, x, y, z, period, 0, ix);
+    const int rc = build_morton_index(ctx, who, n, x, y, z, period, 0, ix);
     if (rc != TSP_OK) return rc;
     const int64_t nv = ix.nv;
 
-    // h and a into Morton order; the raw y and z buffers are free once the positions are gathered
+    // h and the fields into Morton order; the raw y and z buffers are free once the positions are gathered
     DeviceScratch dh, da;
+    const size_t raw_floats = ((size_t)n_fields * (size_t)n + 3) & ~(size_t)3;     // (the float4 payload starts 16-byte aligned)
+    const size_t a_floats = gradient ? raw_floats + 4 * (size_t)nv : (size_t)n;
     TSP_SCRATCH_ALLOC(ctx, SITE("sph_sum_h"), dh, fbytes);
-    TSP_SCRATCH_ALLOC(ctx, SITE("sph_sum_a"), da, fbytes);
+    TSP_SCRATCH_ALLOC(ctx, SITE("sph_sum_a"), da, a_floats * sizeof(float));
     TSP_HIP(hipMemcpyAsync(dh.p, h, fbytes, hipMemcpyHostToDevice, st));
-    TSP_HIP(hipMemcpyAsync(da.p, a, fbytes, hipMemcpyHostToDevice, st));
+    float *raw[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    for (int f = 0; f < n_fields; ++f) {
+        raw[f] = da.as<float>() + (size_t)f * (size_t)n;
+        TSP_HIP(hipMemcpyAsync(raw[f], fields[f], fbytes, hipMemcpyHostToDevice, st));
+    }
     float *sh = ix.dy.as<float>(), *sa = ix.dz.as<float>();
-    hipLaunchKernelGGL(sph_gather_kernel, dim3(ix.grid), dim3(256), 0, st, dh.as<float>(), da.as<float>(), ix.vals2.as<uint32_t>(), nv,
-                       sh, sa);
-    TSP_HIP(hipGetLastError());
-
-    // queries in Morton order; the sorted result reuses the unsorted index buffer
-    float *out_sorted = ix.vals.as<float>();
-    if (nv > 0) {
-        hipLaunchKernelGGL(sph_sum_kernel, dim3((unsigned)((nv + 255) / 256)), dim3(256), 0, st, ix.sx.as<float>(), ix.sy.as<float>(),
-                           ix.sz.as<float>(), sh, sa, ix.keys2.as<uint64_t>(), nv, ix.g, out_sorted, ix.d_count + 1);
+    const float *sorted[4] = {nullptr, nullptr, nullptr, nullptr};     // the results in Morton order
+    float *unsorted[4] = {nullptr, nullptr, nullptr, nullptr};         // and in the caller's order
+    const dim3 query_grid((unsigned)((nv + 255) / 256));
+    if (!gradient) {
+        hipLaunchKernelGGL(sph_gather_kernel, dim3(ix.grid), dim3(256), 0, st, dh.as<float>(), raw[0], ix.vals2.as<uint32_t>(), nv, sh,
+                           sa);
+        TSP_HIP(hipGetLastError());
+        // queries in Morton order; the sorted result reuses the unsorted index buffer
+        float *out_sorted = ix.vals.as<float>();
+        if (nv > 0) {
+            hipLaunchKernelGGL(sph_sum_kernel, query_grid, dim3(256), 0, st, ix.sx.as<float>(), ix.sy.as<float>(), ix.sz.as<float>(), sh,
+                               sa, ix.keys2.as<uint64_t>(), nv, ix.g, out_sorted, ix.d_count + 1);
+            TSP_HIP(hipGetLastError());
+        }
+        sorted[0] = out_sorted;
+        unsorted[0] = ix.dx.as<float>();
+    } else {
+        float4 *smv = reinterpret_cast<float4 *>(da.as<float>() + raw_floats);
+        hipLaunchKernelGGL(sph_gather_velocity_kernel, dim3(ix.grid), dim3(256), 0, st, dh.as<float>(), raw[0], raw[1], raw[2], raw[3],
+                           raw[4], ix.vals2.as<uint32_t>(), nv, sh, sa, smv);
+        TSP_HIP(hipGetLastError());
+        if (nv > 0) {
+            hipLaunchKernelGGL(sph_velocity_gradient_kernel, query_grid, dim3(256), 0, st, ix.sx.as<float>(), ix.sy.as<float>(),
+                               ix.sz.as<float>(), sh, sa, smv, ix.keys2.as<uint64_t>(), nv, ix.g, raw[0], raw[1], raw[2], raw[3],
+                               ix.d_count + 1);
+            TSP_HIP(hipGetLastError());
+        }
+        for (int c = 0; c < 4; ++c) sorted[c] = raw[c];
+        unsorted[0] = ix.dx.as<float>(), unsorted[1] = dh.as<float>(), unsorted[2] = ix.vals.as<float>(), unsorted[3] = raw[4];
+    }
+    // back to the caller's order; invalid particles get NaN
+    for (int c = 0; c < n_outs; ++c) {
+        hipLaunchKernelGGL(smooth_scatter_kernel, dim3(ix.grid), dim3(256), 0, st, sorted[c], ix.vals2.as<uint32_t>(), n, nv, unsorted[c]);
         TSP_HIP(hipGetLastError());
     }
-    // back to the caller's order (the raw x buffer is free now); invalid particles get NaN
-    hipLaunchKernelGGL(smooth_scatter_kernel, dim3(ix.grid), dim3(256), 0, st, out_sorted, ix.vals2.as<uint32_t>(), n, nv,
-                       ix.dx.as<float>());
-    TSP_HIP(hipGetLastError());
     unsigned long long counts[3] = {0, 0, 0};
     TSP_HIP(hipMemcpyAsync(counts, ix.d_count + 1, sizeof(counts), hipMemcpyDeviceToHost, st));
     TSP_HIP(hipStreamSynchronize(st));
-    TSP_HIP(hipMemcpy(out, ix.dx.p, fbytes, hipMemcpyDeviceToHost));
+    for (int c = 0; c < n_outs; ++c) TSP_HIP(hipMemcpy(outs[c], unsorted[c], fbytes, hipMemcpyDeviceToHost));
     // measurement aid: TOPSY_SMOOTH_STATS=1 reports the candidates scanned and the terms summed per query, and the share of
     // the lanes' scan steps that had a candidate (the last step of a run is rarely full)
     const char *env = getenv("TOPSY_SMOOTH_STATS");
     if (env && env[0] == '1')
-        fprintf(stderr, "tsp_sph_sum: n=%lld valid=%lld candidates=%llu per_query=%.2f terms=%llu per_query=%.2f lane_use=%.3f\n",
+        fprintf(stderr, "%s: n=%lld valid=%lld candidates=%llu per_query=%.2f terms=%llu per_query=%.2f lane_use=%.3f\n", who,
                 (long long)n, (long long)nv, counts[0], nv ? (double)counts[0] / (double)nv : 0.0, counts[1],
                 nv ? (double)counts[1] / (double)nv : 0.0, counts[2] ? (double)counts[0] / (64.0 * (double)counts[2]) : 0.0);
     return TSP_OK;

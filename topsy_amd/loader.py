@@ -686,6 +686,9 @@ def compute_virial_radius(ctx, pos, mass, center, rho_threshold, r_max, refineme
     return find_virial_radius(shell_masses, rho_threshold, r_max, refinements)
 
 
+VELOCITY_QUANTITIES = ("v_div", "vorticity")     # what an ArrayDataLoader with vel= derives from the velocities
+
+
 class ArrayDataLoader(AbstractDataLoader):
     """Particles given as numpy arrays (e.g. pulled from a pynbody snapshot by the caller:
     snap['pos'], snap['smooth'], snap['mass'], ...; reference PynbodyDataInMemory, loader.py:79-154).
@@ -698,6 +701,12 @@ class ArrayDataLoader(AbstractDataLoader):
     loader.py:123-127): quantities["rho"] when the caller supplied one, else the gather-form SPH density of the particles,
     computed on the GPU at the first get_named_quantity("rho") -- by the visualizer's context once ParticleBuffers has set it
     (set_density_context), else by a context of its own -- and cached; set_density() restores it from the caller's cache.
+
+    With vel, 'v_div' and 'vorticity' are quantities as well, after 'rho' (pynbody derives v_div, v_curl and vorticity the same
+    way, on the host): the difference-form SPH divergence of the velocity and the float32 norm of its curl
+    (tsp_sph_velocity_gradient), computed on first use on the same context as 'rho' -- after the smoothing lengths and 'rho'
+    where those are missing -- and cached; get_velocity_gradient() returns (div, curl), set_velocity_gradient() restores them
+    from the caller's cache.  A name the caller supplied in quantities= is returned as given.  Unanswerable particles carry NaN.
 
     center: where the view opens (the reference centres the snapshot at load, loader.py:201-217).  "none": the origin;
     "all": the shrinking-sphere centre of every particle; "zoom": that of the lightest mass species (mass < 1.01 * mass.min());
@@ -767,6 +776,8 @@ class ArrayDataLoader(AbstractDataLoader):
         self._period = periodicity_scale
         self._rho = None                 # the computed density ('rho' when the caller supplied none), in this loader's order
         self._density_context = None
+        self._velocity_gradient = None   # the computed (div (n,), curl (n, 3)) of vel, in this loader's order
+        self._vorticity = None           # the norm of that curl
         if self.needs_smoothing:
             if self._pos.ndim != 2 or self._pos.shape[1] != 3:
                 raise ValueError(f"pos must have shape (n, 3), not {self._pos.shape}")
@@ -824,11 +835,17 @@ class ArrayDataLoader(AbstractDataLoader):
     def get_named_quantity(self, name):
         if name == "rho" and name not in self._quantities:
             return self._density()
+        if name in VELOCITY_QUANTITIES and name not in self._quantities and self._vel is not None:
+            return self._derived_velocity_quantity(name)
         return self._quantities[name]
 
     def get_quantity_names(self):
         names = list(self._quantities)
-        return names if "rho" in self._quantities else names + ["rho"]
+        if "rho" not in self._quantities:
+            names.append("rho")
+        if self._vel is not None:
+            names += [name for name in VELOCITY_QUANTITIES if name not in self._quantities]
+        return names
 
     def set_density_context(self, context):
         """The context that computes 'rho' on first use (ParticleBuffers hands over its own; None: one made for the call)."""
@@ -844,26 +861,67 @@ class ArrayDataLoader(AbstractDataLoader):
             raise ValueError("the caller supplied quantities['rho']; it is used as given")
         self._rho = rho
 
-    def _density(self):
+    def _density(self, ctx=None):
+        """The computed density; ctx: the context of a caller that already holds one (_with_context)."""
         if self._rho is None:
             period = self._period or 0.0
             if self._pos.ndim != 2 or self._pos.shape[1] != 3:
                 raise ValueError(f"pos must have shape (n, 3), not {self._pos.shape}")
             check_smoothing_arguments(self.n_smooth, self._period)
-            ctx = self._density_context
-            own = ctx is None
-            if own:
-                from . import _native
-                ctx = _native.Context(1, 2, self._device if isinstance(self._device, int) else 0)
-            try:
+
+            def work(ctx):
                 x, y, z = self._pos[:, 0], self._pos[:, 1], self._pos[:, 2]
                 if self._smooth is None:
                     self.set_smooth(ctx.smoothing_lengths(x, y, z, self.n_smooth, period))
                 self._rho = ctx.sph_sum(x, y, z, self._smooth, self._mass, period)
-            finally:
-                if own:
-                    ctx.close()
+            if ctx is None:
+                self._with_context(work)
+            else:
+                work(ctx)
         return self._rho
+
+    def get_velocity_gradient(self):
+        """(div (n,), curl (n, 3)) float32 of the velocities in this loader's particle order: the SPH estimates of
+        tsp_sph_velocity_gradient, computed on the GPU on first use -- after the smoothing lengths and 'rho' where those are
+        missing (a supplied quantities["rho"] is the rho that is used) -- and cached."""
+        if self._vel is None:
+            raise KeyError("no velocities were supplied (vel=): there is no velocity gradient")
+        if self._velocity_gradient is None:
+            period = self._period or 0.0
+
+            def work(ctx):
+                rho = self._quantities["rho"] if "rho" in self._quantities else self._density(ctx)
+                x, y, z = self._pos[:, 0], self._pos[:, 1], self._pos[:, 2]
+                v = self._vel
+                if self._smooth is None:        # (a density restored by set_density, smoothing lengths not yet computed)
+                    check_smoothing_arguments(self.n_smooth, self._period)
+                    self.set_smooth(ctx.smoothing_lengths(x, y, z, self.n_smooth, period))
+                return ctx.sph_velocity_gradient(x, y, z, self._smooth, self._mass, rho, v[:, 0], v[:, 1], v[:, 2], period)
+            self._velocity_gradient = self._with_context(work)
+        return self._velocity_gradient
+
+    def set_velocity_gradient(self, div, curl):
+        """The velocity divergence (n,) and curl (n, 3) in this loader's particle order (e.g. from the caller's cache, next to
+        set_density): they are then not computed."""
+        div, curl = np.asarray(div, dtype=np.float32), np.asarray(curl, dtype=np.float32)
+        if div.shape != (len(self),):
+            raise ValueError(f"div must have shape ({len(self)},), not {div.shape}")
+        if curl.shape != (len(self), 3):
+            raise ValueError(f"curl must have shape ({len(self)}, 3), not {curl.shape}")
+        if self._vel is None:
+            raise ValueError("the loader has no velocities (vel=): 'v_div' and 'vorticity' are not among its quantities")
+        self._velocity_gradient = (div, curl)
+        self._vorticity = None
+
+    def _derived_velocity_quantity(self, name):
+        div, curl = self.get_velocity_gradient()
+        if name == "v_div":
+            return div
+        if self._vorticity is None:
+            cx, cy, cz = curl[:, 0], curl[:, 1], curl[:, 2]
+            with np.errstate(over="ignore", invalid="ignore"):
+                self._vorticity = np.sqrt((cx * cx + cy * cy) + cz * cz)      # float32, this order
+        return self._vorticity
 
     def _with_context(self, work):
         """work(ctx) on the visualizer's context once it was handed over (set_density_context), else on one made for the call."""

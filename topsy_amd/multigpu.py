@@ -213,6 +213,10 @@ class MultiGpuContext:
         """The SPH sum over the whole (caller-ordered) snapshot, on the first context like smoothing_lengths."""
         return self.contexts[0].sph_sum(x, y, z, h, a, period)
 
+    def sph_velocity_gradient(self, x, y, z, h, mass, rho, vx, vy, vz, period=None):
+        """The velocity divergence and curl over the whole (caller-ordered) snapshot, on the first context like sph_sum."""
+        return self.contexts[0].sph_velocity_gradient(x, y, z, h, mass, rho, vx, vy, vz, period)
+
     def shrink_sphere_center(self, x, y, z, mass, **kwargs):
         """The shrinking-sphere centre of the whole (caller-ordered) snapshot, on the first context like smoothing_lengths."""
         return self.contexts[0].shrink_sphere_center(x, y, z, mass, **kwargs)
