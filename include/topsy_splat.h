@@ -40,7 +40,9 @@ enum {
                           workspace, the post-pass staging and the scratch of the per-call entry points are allocated on
                           demand): on that return the caller's outputs are untouched, the context -- image, accumulator,
                           statistics, resident particles, their order and its layout -- is as the call found it,
-                          tsp_last_error names the allocation, and the context stays usable */
+                          tsp_last_error names the allocation, and the context stays usable.  The one exception are the
+                          calls that replace the whole snapshot, tsp_upload_particles and tsp_generate_synthetic: they
+                          leave no particles resident ("Failed uploads" below) */
 };
 
 /* Render modes: which per-particle channels feed the image (reference SPH subclasses). */
@@ -104,7 +106,9 @@ const char *tsp_last_error(void);
  * the accumulators of the members that had succeeded); no struct changed, nothing else changed.
  * 119: kinematic frames: the bases TSP_PRESENT_MOMENT_MEAN / TSP_PRESENT_MOMENT_SIGMA of tsp_present and tsp_present_yuv420 (values
  * that returned TSP_EINVAL before) and the new entry point tsp_moment_sort; no struct changed, nothing else changed.
- * 120: new entry point tsp_sph_velocity_gradient (velocity divergence and curl by SPH gather sums); nothing else changed. */
+ * 120: new entry point tsp_sph_velocity_gradient (velocity divergence and curl by SPH gather sums); nothing else changed.
+ * 121: a failed upload leaves no half-made state ("Failed uploads" below; it used to leave some arrays new, some old or
+ * missing); no entry point or struct changed. */
 int tsp_version(void);
 int tsp_stats_size(void);
 
@@ -125,7 +129,22 @@ int tsp_set_kernel_mips(tsp_context *ctx, const float *lut, int n0, int n_levels
 /* Particle upload, SoA float32, caller's (global) index order is preserved.
  * Replaces ParticleBuffers.get_pos_smooth_buffers / get_mass_and_quantity_buffers /
  * get_rgb_buffers (reference src/topsy/particle_buffers.py:84-118).
- * mass may be NULL for a context that will only render TSP_MODE_RGB. */
+ * mass may be NULL for a context that will only render TSP_MODE_RGB.
+ *
+ * Failed uploads.  Every device allocation of the uploads is made before the first copy, kernel or change of state.
+ *   1. Attribute uploads (tsp_upload_quantity, tsp_upload_rgb, tsp_upload_velocities, tsp_upload_band_magnitudes): a call that returns TSP_ENOMEM has changed nothing -- the
+ *      resident arrays (bit for bit), the cached vertex weights and what they were formed from, the validity of
+ *      tsp_render_undo, the image and the statistics are as before the call, and what the call allocated is freed.  Arrays
+ *      that are resident already are written in place, never freed and allocated again (n cannot change between two particle
+ *      uploads), so a repeated upload of an attribute allocates only the staging of the load-time permutation, if any.
+ *   2. Replace-all uploads (tsp_upload_particles, tsp_generate_synthetic) free the old snapshot FIRST -- keeping it would
+ *      double the peak memory of a 1e9-particle snapshot -- so a call that fails (TSP_ENOMEM or TSP_EHIP) leaves the context
+ *      holding no particles, exactly as after tsp_upload_particles(ctx, 0, ...): tsp_num_particles is 0, there is no
+ *      per-particle array, permutation, strata or cell grid; the image, the statistics, the LUTs and the options are
+ *      untouched.  Every attribute upload then returns TSP_ESTATE and tsp_render draws nothing.
+ *   3. tsp_render and tsp_render_surface return TSP_ESTATE for a context with n > 0 whose x, y, z or h array is missing,
+ *      next to their checks of the mass, rgb and velocity arrays: no half-made context reaches a kernel.
+ *   4. Groups: see "Several GPUs of one node behind ONE handle" at the end of this file. */
 int tsp_upload_particles(tsp_context *ctx, int64_t n, const float *x, const float *y, const float *z,
                          const float *h, const float *mass);
 /* q == NULL selects the density render (reference uploads q = 0 then, particle_buffers.py:96-99;
@@ -863,6 +882,12 @@ int tsp_set_reduced_image(tsp_context *ctx, const float *sum);
  * selected -- has nothing to take back and is left as it is, reduced state included (if it is context 0 and still presents a
  * reduced frame, that frame stands and is not summed again); and one on which the block replaced a surface image keeps the
  * block, because tsp_render_undo does not restore surface keys.
+ * Failed uploads ("Failed uploads" at tsp_upload_particles): a snapshot is resident on every member or on none -- when
+ * tsp_upload_particles or tsp_generate_synthetic fails on one member, tsp_group_upload_particles /
+ * tsp_group_generate_synthetic empty EVERY member, tsp_group_num_particles returns 0, and that member's code and message are
+ * returned; a tsp_group_render then draws nothing.  The group's attribute uploads (quantity, rgb, band magnitudes) are NOT
+ * transactional across the members: each member follows rule 1 on its own, so after a failure the failing member holds the
+ * old attribute and every other member the old or the new one -- upload the attribute again before rendering.
  * Calls on one group must be
  * serialised by the caller.  tsp_group_get_stats: counters summed over the shards, times of the slowest shard. */
 typedef struct tsp_group tsp_group;

@@ -1,17 +1,18 @@
-"""Source lint (no GPU): every device allocation that can run after tsp_create and the uploads goes through alloc_group(), whose
+"""Source lint (no GPU): every device allocation that can run after tsp_create goes through alloc_group(), whose
 failure leaves a group of buffers null with capacity 0, or -- per-call scratch -- through scratch_alloc() (TSP_SCRATCH_ALLOC), and
-every allocation site has a name of its own that the GPU tests (test_gpu_alloc_failure.py, test_gpu_scratch_alloc_failure.py) make
-fail."""
+every allocation site has a name of its own that the GPU tests (test_gpu_alloc_failure.py, test_gpu_scratch_alloc_failure.py,
+test_gpu_upload_alloc_failure.py) make fail."""
 import glob
 import os
 import re
 
 from test_gpu_alloc_failure import GENERIC_SITES, POSTPASS_SITES, RENDER_SITES
 from test_gpu_scratch_alloc_failure import SCRATCH_SITES
+from test_gpu_upload_alloc_failure import UPLOAD_SITES
 
 CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "topsy_amd", "csrc")
-# functions that may call hipMalloc themselves: the two helpers, context creation and the particle uploads
-RAW_ALLOWED = {"alloc_group", "scratch_alloc", "create_resources", "ensure_array", "upload_array", "upload_permuted", "generate_synthetic"}
+# functions that may call hipMalloc themselves: the two helpers and context creation
+RAW_ALLOWED = {"alloc_group", "scratch_alloc", "create_resources"}
 FUNC_DEF = re.compile(r"^(?!return\b|else\b|if\b|for\b|while\b|switch\b)[A-Za-z_][\w:<>,\s\*&]*?\b(\w+)\s*\([^;]*$")
 SITE = re.compile(r'\{\s*"(\w+)"\s*,\s*(?:\(void\s*\*\*\)\s*)?&|\bSITE\("(\w+)"\)')
 
@@ -38,7 +39,7 @@ def enclosing_functions(text):
 
 def test_raw_hipmalloc_only_in_the_helper_and_creation():
     bad = [f"{name}:{no} in {fn}" for name, text in sources() for no, fn in enclosing_functions(text) if fn not in RAW_ALLOWED]
-    assert not bad, "device allocations outside alloc_group() and the creation / upload functions: " + ", ".join(bad)
+    assert not bad, "device allocations outside alloc_group(), scratch_alloc() and context creation: " + ", ".join(bad)
 
 
 def test_the_lint_sees_the_helper():
@@ -61,6 +62,6 @@ def test_site_names_are_unique_and_covered():
     names = [a or b for _, text in sources() for a, b in SITE.findall(re.sub(r"//[^\n]*", "", text))]      # (comments aside)
     dup = sorted({n for n in names if names.count(n) > 1})
     assert not dup, f"allocation sites sharing a name: {dup}"
-    covered = set().union(*RENDER_SITES.values(), GENERIC_SITES, POSTPASS_SITES, *SCRATCH_SITES.values())
+    covered = set().union(*RENDER_SITES.values(), GENERIC_SITES, POSTPASS_SITES, *SCRATCH_SITES.values(), *UPLOAD_SITES.values())
     assert set(names) == covered, (f"sites no GPU test makes fail: {sorted(set(names) - covered)}; "
                                    f"sites the tests expect that the sources lack: {sorted(covered - set(names))}")

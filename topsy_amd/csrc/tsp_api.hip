@@ -23,15 +23,6 @@ void set_error(const char *fmt, ...) {
     va_end(ap);
 }
 
-int ensure_array(float **p, int64_t n) {
-    if (*p) {
-        TSP_HIP(hipFree(*p));
-        *p = nullptr;
-    }
-    if (n > 0) TSP_HIP(hipMalloc((void **)p, (size_t)n * sizeof(float)));
-    return TSP_OK;
-}
-
 int alloc_group(tsp_context *ctx, std::initializer_list<DeviceBuffer> bufs, std::initializer_list<Capacity> caps) {
     for (const Capacity &c : caps) c.set(0);
     hipError_t freed = hipSuccess;
@@ -109,12 +100,6 @@ int check_workspace(const tsp_context *ctx) {
     return TSP_OK;
 }
 
-static int upload_array(tsp_context *ctx, float **dst, const float *src, int64_t n) {
-    if (!*dst) TSP_HIP(hipMalloc((void **)dst, (size_t)n * sizeof(float)));
-    TSP_HIP(hipMemcpyAsync(*dst, src, (size_t)n * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
-    return TSP_OK;
-}
-
 __global__ void image_to_float_kernel(const double *__restrict__ src, float *__restrict__ dst, int64_t n) {
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
         dst[i] = (float)src[i];
@@ -139,17 +124,38 @@ __global__ void gather_kernel(const float *__restrict__ src, const uint32_t *__r
         dst[i] = src[perm[i]];
 }
 
-// upload in caller order, then apply the load-time permutation if one is active
-static int upload_permuted(tsp_context *ctx, float **dst, const float *src, int64_t n) {
-    if (!ctx->p.perm) return upload_array(ctx, dst, src, n);
-    float *tmp = nullptr;
-    TSP_HIP(hipMalloc((void **)&tmp, (size_t)n * sizeof(float)));
-    TSP_HIP(hipMemcpyAsync(tmp, src, (size_t)n * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
-    if (!*dst) TSP_HIP(hipMalloc((void **)dst, (size_t)n * sizeof(float)));
-    hipLaunchKernelGGL(gather_kernel, dim3(2048), dim3(256), 0, ctx->stream, tmp, ctx->p.perm, *dst, n);
-    TSP_HIP(hipGetLastError());
+// One attribute upload (tsp_upload_quantity / _rgb / _velocities): `count` caller-ordered host arrays src[] into the resident
+// arrays *dst[], through the load-time permutation if one is active.  Everything the call needs is allocated before the first
+// copy, kernel or change of state, so that a call that returns TSP_ENOMEM has changed nothing (include/topsy_splat.h): the
+// staging buffer of the permutation (one serves every array of the call) and, when the attribute is not resident yet, its
+// arrays as one group (`missing`; alloc_group frees what its pointers hold, so arrays that are resident are never handed to
+// it).  `changed` runs once the memory is there, before the first copy: what the context forgets because the attribute changes.
+template <typename F>
+static int upload_attributes(tsp_context *ctx, const char *staging_site, float **const *dst, const float *const *src, int count,
+                             bool resident, std::initializer_list<DeviceBuffer> missing, F changed) {
+    const int64_t n = ctx->p.n;
+    const size_t bytes = (size_t)n * sizeof(float);
+    DeviceScratch tmp;
+    if (ctx->p.perm) {
+        const int rc = scratch_alloc(ctx, staging_site, tmp, bytes);
+        if (rc) return rc;
+    }
+    if (!resident) {
+        const int rc = alloc_group(ctx, missing, {});
+        if (rc) return rc;
+    }
+    changed();
+    for (int k = 0; k < count; ++k) {
+        if (!ctx->p.perm) {
+            TSP_HIP(hipMemcpyAsync(*dst[k], src[k], bytes, hipMemcpyHostToDevice, ctx->stream));
+            continue;
+        }
+        TSP_HIP(hipMemcpyAsync(tmp.p, src[k], bytes, hipMemcpyHostToDevice, ctx->stream));
+        hipLaunchKernelGGL(gather_kernel, dim3(2048), dim3(256), 0, ctx->stream, tmp.as<float>(), ctx->p.perm, *dst[k], n);
+        TSP_HIP(hipGetLastError());
+        TSP_HIP(hipStreamSynchronize(ctx->stream));      // (tmp takes the next array)
+    }
     TSP_HIP(hipStreamSynchronize(ctx->stream));
-    TSP_HIP(hipFree(tmp));
     return TSP_OK;
 }
 
@@ -221,7 +227,7 @@ using namespace tsp;
 extern "C" {
 
 const char *tsp_last_error(void) { return g_err; }
-int tsp_version(void) { return 120; }     // 120: tsp_sph_velocity_gradient; 119: tsp_moment_sort, TSP_PRESENT_MOMENT_MEAN / _SIGMA (the kinematic maps as the base of tsp_present / tsp_present_yuv420); 118: tsp_render_undo, tsp_group_render all-or-nothing across the members; 117: kinematic maps (tsp_upload_velocities, tsp_set_line_of_sight, TSP_MODE_KINEMATIC, tsp_velocity_moments, tsp_colormap_moment); 116: tsp_radial_profile; 115: tsp_sphere_moments; 114: tsp_fof_groups; 113: tsp_shrink_sphere_center; 112: tsp_present_surface, tsp_present_surface_yuv420; 111: tsp_content_neg_inf; 110: tsp_sph_sum; 109: tsp_present_yuv420; 108: tsp_present; 107: surface rendering; 106: tsp_smoothing_lengths; 101: tsp_stats gained ms_mega, n_mega (16 bytes); 102: the per-kernel fragment counts (32 bytes); 103: n_chunk_culled (8 bytes); 104: matrix-core / kernel-I options removed; 105: kernel M's options removed (kernel G draws the mid footprints)
+int tsp_version(void) { return 121; }     // 121: a failed upload is atomic (attributes: nothing changed; particles / synthetic: no particles left; groups: every member emptied); 120: tsp_sph_velocity_gradient; 119: tsp_moment_sort, TSP_PRESENT_MOMENT_MEAN / _SIGMA (the kinematic maps as the base of tsp_present / tsp_present_yuv420); 118: tsp_render_undo, tsp_group_render all-or-nothing across the members; 117: kinematic maps (tsp_upload_velocities, tsp_set_line_of_sight, TSP_MODE_KINEMATIC, tsp_velocity_moments, tsp_colormap_moment); 116: tsp_radial_profile; 115: tsp_sphere_moments; 114: tsp_fof_groups; 113: tsp_shrink_sphere_center; 112: tsp_present_surface, tsp_present_surface_yuv420; 111: tsp_content_neg_inf; 110: tsp_sph_sum; 109: tsp_present_yuv420; 108: tsp_present; 107: surface rendering; 106: tsp_smoothing_lengths; 101: tsp_stats gained ms_mega, n_mega (16 bytes); 102: the per-kernel fragment counts (32 bytes); 103: n_chunk_culled (8 bytes); 104: matrix-core / kernel-I options removed; 105: kernel M's options removed (kernel G draws the mid footprints)
 int tsp_stats_size(void) { return (int)sizeof(tsp_stats); }
 
 int tsp_device_count(void) {
@@ -336,16 +342,29 @@ int tsp_upload_particles(tsp_context *ctx, int64_t n, const float *x, const floa
     TSP_REQUIRE(n >= 0 && n < ((int64_t)1 << 32), TSP_EINVAL, "particle count %lld out of range", (long long)n);
     TSP_REQUIRE(n == 0 || (x && y && z && h), TSP_EINVAL, "NULL position/smoothing array");
     TSP_HIP(hipSetDevice(ctx->device));
+    // The old snapshot goes first (keeping it would double the peak memory of a large one), so a call that fails leaves the
+    // context with no particles at all, as after n = 0: p.n is set only once every array exists and holds its data
     free_particles(ctx);
-    ctx->p.n = n;
     if (n == 0) return TSP_OK;
-    int rc;
-    if ((rc = upload_array(ctx, &ctx->p.x, x, n))) return rc;
-    if ((rc = upload_array(ctx, &ctx->p.y, y, n))) return rc;
-    if ((rc = upload_array(ctx, &ctx->p.z, z, n))) return rc;
-    if ((rc = upload_array(ctx, &ctx->p.h, h, n))) return rc;
-    if (mass && (rc = upload_array(ctx, &ctx->p.m, mass, n))) return rc;
-    TSP_HIP(hipStreamSynchronize(ctx->stream));
+    Particles &p = ctx->p;
+    const size_t bytes = (size_t)n * sizeof(float);
+    int rc = alloc_group(ctx, {{"particles_x", (void **)&p.x, bytes}, {"particles_y", (void **)&p.y, bytes},
+                               {"particles_z", (void **)&p.z, bytes}, {"particles_h", (void **)&p.h, bytes}}, {});
+    if (!rc && mass) rc = alloc_group(ctx, {{"particles_mass", (void **)&p.m, bytes}}, {});
+    if (!rc) {
+        rc = [&]() -> int {
+            float *const dst[] = {p.x, p.y, p.z, p.h, p.m};
+            const float *const src[] = {x, y, z, h, mass};
+            for (int k = 0; k < (mass ? 5 : 4); ++k) TSP_HIP(hipMemcpyAsync(dst[k], src[k], bytes, hipMemcpyHostToDevice, ctx->stream));
+            TSP_HIP(hipStreamSynchronize(ctx->stream));
+            return TSP_OK;
+        }();
+    }
+    if (rc) {
+        free_particles(ctx);         // (allocates nothing and leaves tsp_last_error alone)
+        return rc;
+    }
+    p.n = n;
     return TSP_OK;
 }
 
@@ -353,30 +372,32 @@ int tsp_upload_quantity(tsp_context *ctx, const float *q) {
     TSP_REQUIRE(ctx, TSP_EINVAL, "NULL context");
     TSP_REQUIRE(!q || ctx->p.n > 0, TSP_ESTATE, "upload particles before the quantity");
     TSP_HIP(hipSetDevice(ctx->device));
-    ctx->forget_render_undo();                           // (an upload ends the validity of tsp_render_undo: topsy_splat.h)
+    Particles &p = ctx->p;
     if (!q) {
-        if (ctx->p.q) TSP_HIP(hipFree(ctx->p.q));
-        ctx->p.q = nullptr;
+        ctx->forget_render_undo();                       // (an upload ends the validity of tsp_render_undo: topsy_splat.h)
+        if (p.q) TSP_HIP(hipFree(p.q));
+        p.q = nullptr;
         return TSP_OK;
     }
-    int rc = upload_permuted(ctx, &ctx->p.q, q, ctx->p.n);
-    if (rc) return rc;
-    TSP_HIP(hipStreamSynchronize(ctx->stream));
-    return TSP_OK;
+    float **const dst[] = {&p.q};
+    const float *const src[] = {q};
+    return upload_attributes(ctx, SITE("quantity_staging"), dst, src, 1, p.q != nullptr,
+                             {{"quantity_q", (void **)&p.q, (size_t)p.n * sizeof(float)}}, [&]() { ctx->forget_render_undo(); });
 }
 
 int tsp_upload_rgb(tsp_context *ctx, const float *r, const float *g, const float *b) {
     TSP_REQUIRE(ctx && r && g && b, TSP_EINVAL, "NULL argument");
     TSP_REQUIRE(ctx->p.n > 0, TSP_ESTATE, "upload particles before rgb");
     TSP_HIP(hipSetDevice(ctx->device));
-    ctx->forget_render_undo();
-    int rc;
-    if ((rc = upload_permuted(ctx, &ctx->p.r, r, ctx->p.n))) return rc;
-    if ((rc = upload_permuted(ctx, &ctx->p.g, g, ctx->p.n))) return rc;
-    if ((rc = upload_permuted(ctx, &ctx->p.b, b, ctx->p.n))) return rc;
-    ctx->p.wrgb_source = W_NONE;
-    TSP_HIP(hipStreamSynchronize(ctx->stream));
-    return TSP_OK;
+    Particles &p = ctx->p;
+    const size_t bytes = (size_t)p.n * sizeof(float);
+    float **const dst[] = {&p.r, &p.g, &p.b};
+    const float *const src[] = {r, g, b};
+    return upload_attributes(ctx, SITE("rgb_staging"), dst, src, 3, p.r && p.g && p.b,
+                             {{"rgb_r", (void **)&p.r, bytes}, {"rgb_g", (void **)&p.g, bytes}, {"rgb_b", (void **)&p.b, bytes}}, [&]() {
+                                 ctx->forget_render_undo();
+                                 p.wrgb_source = W_NONE;      // (the cached weights were formed from the colours that go)
+                             });
 }
 
 int tsp_upload_velocities(tsp_context *ctx, const float *vx, const float *vy, const float *vz) {
@@ -385,9 +406,12 @@ int tsp_upload_velocities(tsp_context *ctx, const float *vx, const float *vy, co
     Particles &p = ctx->p;
     TSP_REQUIRE(!vx || p.n > 0, TSP_ESTATE, "upload particles before the velocities");
     TSP_HIP(hipSetDevice(ctx->device));
-    ctx->forget_render_undo();
-    if (p.wrgb_source == W_KINEMATIC) p.wrgb_source = W_NONE;     // (the weights were formed from the velocities that go)
+    const auto changed = [&]() {
+        ctx->forget_render_undo();
+        if (p.wrgb_source == W_KINEMATIC) p.wrgb_source = W_NONE;     // (the weights were formed from the velocities that go)
+    };
     if (!vx) {
+        changed();
         float **arrs[] = {&p.vx, &p.vy, &p.vz};
         for (float **a : arrs) {
             if (*a) TSP_HIP(hipFree(*a));
@@ -395,12 +419,12 @@ int tsp_upload_velocities(tsp_context *ctx, const float *vx, const float *vy, co
         }
         return TSP_OK;
     }
-    int rc;
-    if ((rc = upload_permuted(ctx, &p.vx, vx, p.n))) return rc;
-    if ((rc = upload_permuted(ctx, &p.vy, vy, p.n))) return rc;
-    if ((rc = upload_permuted(ctx, &p.vz, vz, p.n))) return rc;
-    TSP_HIP(hipStreamSynchronize(ctx->stream));
-    return TSP_OK;
+    const size_t bytes = (size_t)p.n * sizeof(float);
+    float **const dst[] = {&p.vx, &p.vy, &p.vz};
+    const float *const src[] = {vx, vy, vz};
+    return upload_attributes(ctx, SITE("velocities_staging"), dst, src, 3, p.vx && p.vy && p.vz,
+                             {{"velocities_x", (void **)&p.vx, bytes}, {"velocities_y", (void **)&p.vy, bytes},
+                              {"velocities_z", (void **)&p.vz, bytes}}, changed);
 }
 
 int tsp_set_line_of_sight(tsp_context *ctx, const float axis[3], const float v_ref[3]) {
@@ -445,19 +469,24 @@ int tsp_upload_band_magnitudes(tsp_context *ctx, int n_bands, const double *mags
     TSP_REQUIRE(n_bands >= 1 && n_bands <= 64, TSP_EINVAL, "n_bands %d out of range", n_bands);
     TSP_REQUIRE(ctx->p.n > 0, TSP_ESTATE, "upload particles before the band magnitudes");
     TSP_HIP(hipSetDevice(ctx->device));
-    ctx->forget_render_undo();
-    const int64_t n = ctx->p.n;
+    Particles &p = ctx->p;
+    const int64_t n = p.n;
+    // every allocation first, as in upload_attributes: resident colour arrays are written in place (n cannot have changed)
     DeviceScratch d_mags, d_w;
     TSP_SCRATCH_ALLOC(ctx, SITE("band_magnitudes"), d_mags, (size_t)n_bands * n * sizeof(double));
     TSP_SCRATCH_ALLOC(ctx, SITE("band_weights"), d_w, (size_t)3 * n_bands * sizeof(double));
+    if (!(p.r && p.g && p.b)) {
+        const size_t bytes = (size_t)n * sizeof(float);
+        const int rc = alloc_group(ctx, {{"band_r", (void **)&p.r, bytes}, {"band_g", (void **)&p.g, bytes}, {"band_b", (void **)&p.b, bytes}}, {});
+        if (rc) return rc;
+    }
+    ctx->forget_render_undo();
+    p.wrgb_source = W_NONE;
     TSP_HIP(hipMemcpyAsync(d_mags.p, mags, (size_t)n_bands * n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
     TSP_HIP(hipMemcpyAsync(d_w.p, weights, (size_t)3 * n_bands * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    int rc;
-    if ((rc = ensure_array(&ctx->p.r, n)) || (rc = ensure_array(&ctx->p.g, n)) || (rc = ensure_array(&ctx->p.b, n))) return rc;
     const unsigned grid = (unsigned)std::min<int64_t>((n + 255) / 256, (int64_t)ctx->cu_count * 16);
     hipLaunchKernelGGL(band_contraction_kernel, dim3(grid), dim3(256), 0, ctx->stream, d_mags.as<double>(), d_w.as<double>(), n_bands, n,
-                       ctx->p.perm, ctx->p.r, ctx->p.g, ctx->p.b);
-    ctx->p.wrgb_source = W_NONE;
+                       p.perm, p.r, p.g, p.b);
     TSP_HIP(hipGetLastError());
     TSP_HIP(hipStreamSynchronize(ctx->stream));
     return TSP_OK;
@@ -471,7 +500,9 @@ int tsp_generate_synthetic(tsp_context *ctx, int64_t n_total, int64_t first, int
     TSP_REQUIRE(count < ((int64_t)1 << 32), TSP_EINVAL, "shard too large");
     TSP_HIP(hipSetDevice(ctx->device));
     free_particles(ctx);
-    return generate_synthetic(ctx, n_total, first, count, seed, h_cap, with_quantity, with_rgb);
+    const int rc = generate_synthetic(ctx, n_total, first, count, seed, h_cap, with_quantity, with_rgb);
+    if (rc) free_particles(ctx);     // as tsp_upload_particles: a failed call leaves no particles (tsp_last_error stays)
+    return rc;
 }
 
 int tsp_get_strata_offsets(tsp_context *ctx, int64_t *offsets_out, int capacity) {
@@ -611,6 +642,8 @@ static int render_block(tsp_context *ctx, const float *M, float scale_factor, co
     TSP_REQUIRE(mode == TSP_MODE_WEIGHTED || mode == TSP_MODE_DEPTH || mode == TSP_MODE_RGB || mode == TSP_MODE_KINEMATIC, TSP_EINVAL,
                 "bad mode %d", mode);
     const bool kinematic = mode == TSP_MODE_KINEMATIC;
+    // (no upload leaves n > 0 without these four: the check keeps a half-made context from ever reaching a kernel)
+    TSP_REQUIRE(ctx->p.n == 0 || (ctx->p.x && ctx->p.y && ctx->p.z && ctx->p.h), TSP_ESTATE, "position / smoothing-length arrays not resident");
     if (kinematic) {
         TSP_REQUIRE(ctx->Ccap == 4, TSP_EINVAL, "TSP_MODE_KINEMATIC needs a 4-channel context");
         TSP_REQUIRE(!(flags & (TSP_PIPE_GENERIC | TSP_SAMPLE_BILINEAR_MIP0 | TSP_SAMPLE_BILINEAR_MIP)), TSP_EINVAL,
@@ -1121,6 +1154,7 @@ int tsp_render_surface(tsp_context *ctx, const float *M, float scale_factor, flo
                        const int64_t *lens, int n_ranges, int clear, double *gpu_ms_out) {
     TSP_REQUIRE(ctx && M, TSP_EINVAL, "NULL argument");
     TSP_REQUIRE(ctx->p.n == 0 || ctx->p.m, TSP_EINVAL, "the surface pass needs the mass array (density cut)");
+    TSP_REQUIRE(ctx->p.n == 0 || (ctx->p.x && ctx->p.y && ctx->p.z && ctx->p.h), TSP_ESTATE, "position / smoothing-length arrays not resident");
     TSP_REQUIRE(ctx->p.n < ((int64_t)1 << 32), TSP_EINVAL, "the surface keys hold indices below 2^32");
     TSP_REQUIRE(n_ranges >= 0 && (n_ranges == 0 || (starts && lens) || (!starts && !lens)), TSP_EINVAL, "bad ranges");
     TSP_REQUIRE(ctx->have_sphere_mips, TSP_ESTATE, "tsp_set_sphere_mips must be called before tsp_render_surface");

@@ -86,18 +86,19 @@ static uint64_t gcd64(uint64_t a, uint64_t b) {
 
 int generate_synthetic(tsp_context *ctx, int64_t n_total, int64_t first, int64_t count, uint64_t seed, float h_cap,
                        int with_quantity, int with_rgb) {
+    // the caller (tsp_generate_synthetic) has freed the old snapshot and frees whatever exists again when this fails; p.n is
+    // set only once every array exists
     Particles &p = ctx->p;
-    p.n = count;
     ctx->ws.bounds_valid = false;
     if (count == 0) return TSP_OK;
-    float **need[] = {&p.x, &p.y, &p.z, &p.h, &p.m};
-    for (float **a : need) TSP_HIP(hipMalloc((void **)a, (size_t)count * sizeof(float)));
-    if (with_quantity) TSP_HIP(hipMalloc((void **)&p.q, (size_t)count * sizeof(float)));
-    if (with_rgb) {
-        TSP_HIP(hipMalloc((void **)&p.r, (size_t)count * sizeof(float)));
-        TSP_HIP(hipMalloc((void **)&p.g, (size_t)count * sizeof(float)));
-        TSP_HIP(hipMalloc((void **)&p.b, (size_t)count * sizeof(float)));
-    }
+    const size_t bytes = (size_t)count * sizeof(float);
+    int rc = alloc_group(ctx, {{"synthetic_x", (void **)&p.x, bytes}, {"synthetic_y", (void **)&p.y, bytes}, {"synthetic_z", (void **)&p.z, bytes},
+                               {"synthetic_h", (void **)&p.h, bytes}, {"synthetic_mass", (void **)&p.m, bytes}}, {});
+    if (!rc && with_quantity) rc = alloc_group(ctx, {{"synthetic_q", (void **)&p.q, bytes}}, {});
+    if (!rc && with_rgb)
+        rc = alloc_group(ctx, {{"synthetic_r", (void **)&p.r, bytes}, {"synthetic_g", (void **)&p.g, bytes}, {"synthetic_b", (void **)&p.b, bytes}}, {});
+    if (rc) return rc;
+    p.n = count;
     SynthParams sp;
     sp.n_total = n_total; sp.first = first; sp.count = count; sp.seed = seed; sp.h_cap = h_cap;
     sp.c0 = (int64_t)((double)n_total * 0.5);   // int(N * w), loader.py:281

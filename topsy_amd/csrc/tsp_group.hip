@@ -56,6 +56,17 @@ void set_bounds(tsp_group *grp, int64_t n) {
     for (int g = 0; g <= G; ++g) grp->bounds[g] = (n * g) / G;
 }
 
+// A snapshot is resident on every member or on none: when a member's upload (or generation) has failed, it holds no particles
+// (tsp_upload_particles) while the others hold their shards of the new snapshot, which a render would draw without any error.
+// Every member is emptied and the group counts 0 particles; the failing member's code and message stay.
+int empty_after_failure(tsp_group *grp, int rc) {
+    const std::string why = tsp_last_error();
+    for (tsp_context *c : grp->ctx) (void)tsp_upload_particles(c, 0, nullptr, nullptr, nullptr, nullptr, nullptr);
+    set_bounds(grp, 0);
+    set_error("%s", why.c_str());
+    return rc;
+}
+
 }  // namespace
 
 extern "C" {
@@ -132,10 +143,11 @@ int tsp_group_upload_particles(tsp_group *grp, int64_t n, const float *x, const 
     TSP_REQUIRE(grp && x && y && z && h, TSP_EINVAL, "NULL argument");
     TSP_REQUIRE(n >= 0, TSP_EINVAL, "negative particle count");
     set_bounds(grp, n);
-    return for_each_context(grp, [&](int g) {
+    const int rc = for_each_context(grp, [&](int g) {
         const int64_t a = grp->bounds[g], len = grp->bounds[g + 1] - a;
         return tsp_upload_particles(grp->ctx[g], len, x + a, y + a, z + a, h + a, mass ? mass + a : nullptr);
     });
+    return rc ? empty_after_failure(grp, rc) : TSP_OK;
 }
 
 int tsp_group_upload_quantity(tsp_group *grp, const float *q) {
@@ -160,10 +172,11 @@ int tsp_group_generate_synthetic(tsp_group *grp, int64_t n_total, int64_t first,
     TSP_REQUIRE(grp, TSP_EINVAL, "NULL group");
     TSP_REQUIRE(count >= 0, TSP_EINVAL, "negative particle count");
     set_bounds(grp, count);
-    return for_each_context(grp, [&](int g) {
+    const int rc = for_each_context(grp, [&](int g) {
         const int64_t a = grp->bounds[g], len = grp->bounds[g + 1] - a;
         return tsp_generate_synthetic(grp->ctx[g], n_total, first + a, len, seed, h_cap, with_quantity, with_rgb);
     });
+    return rc ? empty_after_failure(grp, rc) : TSP_OK;
 }
 
 int tsp_group_reorder_spatial(tsp_group *grp, int n_strata, uint64_t seed) {

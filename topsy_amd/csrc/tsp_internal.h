@@ -231,8 +231,8 @@ int scratch_alloc(tsp_context *ctx, const char *site, DeviceScratch &buf, size_t
         if (rc_ != TSP_OK) return rc_;                                               \
     } while (0)
 
-// Every device buffer that can be (re)allocated after tsp_create and the uploads -- the render workspace, the colormap and
-// post-pass staging -- goes through alloc_group().  A group is the buffers that are only ever used together, with the capacity
+// Every device buffer that can be (re)allocated after tsp_create -- the resident particle arrays, the render workspace, the
+// colormap and post-pass staging -- goes through alloc_group().  A group is the buffers that are only ever used together, with the capacity
 // fields that describe them: the group is freed and its capacities zeroed first, then each buffer is allocated, and only once all
 // of them exist are the capacities recorded.  A failed allocation (or the injected one of option debug_fail_alloc) leaves every
 // pointer of the group null and its capacities 0, so the next call allocates again instead of trusting a stale size; it returns
@@ -289,7 +289,6 @@ int launch_image_convert(tsp_context *ctx, bool to_float);
 int tile_periodic(tsp_context *ctx, int n, const float *h_offsets, const float *h_weights);
 int moment_sort(tsp_context *ctx, int which, int absolute, int64_t *n_finite);   // the same sort of a kinematic image's moment map
 int content_sort(tsp_context *ctx, int kind, float scale, int64_t *n_finite, int64_t *n_nonpositive);   // image64 -> image (true) or image -> image64 (false)
-int ensure_array(float **p, int64_t n);
 int smoothing_lengths(tsp_context *ctx, int64_t n, const float *x, const float *y, const float *z, int k, float period,
                       float *h_out);   // tsp_smooth.hip: per-call DeviceScratch only, no context state
 // tsp_smooth.hip: the gather-form SPH sums on the same index (tsp_sph_sum, tsp_sph_velocity_gradient); per-call DeviceScratch only.

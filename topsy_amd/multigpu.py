@@ -80,6 +80,8 @@ class MultiGpuContext:
 
     def _map(self, fn):
         futures = [self._pool.submit(fn, g, c) for g, c in enumerate(self.contexts)]
+        for f in futures:
+            f.exception()       # every member has finished before the first failure is raised: none is still at work on its context
         return [f.result() for f in futures]
 
     def _shard(self, g):
@@ -183,7 +185,24 @@ class MultiGpuContext:
         else:
             self._bounds = distributed.shard_bounds(n, self.n_gpus)
         arrays = [np.asarray(v) if v is not None else None for v in (x, y, z, h, mass)]
-        self._map(lambda g, c: c.upload_particles(*[self._take(v, g) for v in arrays]))
+        self._all_or_none(lambda g, c: c.upload_particles(*[self._take(v, g) for v in arrays]))
+
+    def _all_or_none(self, fn):
+        """A snapshot is resident on every member or on none (as tsp_group_upload_particles): when the upload or generation `fn`
+        fails on one member -- which then holds no particles -- the others would draw their shards of the new snapshot without
+        any error, so every member is emptied, the context counts 0 particles, and the member's exception is raised again."""
+        futures = [self._pool.submit(fn, g, c) for g, c in enumerate(self.contexts)]
+        errors = [f.exception() for f in futures]
+        failed = [e for e in errors if e is not None]
+        if not failed:
+            return
+        empty = np.empty(0, dtype=np.float32)
+        for c in self.contexts:
+            c.upload_particles(empty, empty, empty, empty)
+        self._n_uploaded = 0
+        self._cyclic = self._cyclic_ranges = False
+        self._bounds = np.zeros(self.n_gpus + 1, dtype=np.int64)
+        raise failed[0]
 
     def _upload_sliced(self, method, arrays, axis=0):
         # an empty shard (fewer particles or interleave blocks than members) holds nothing to attach the values to: the
@@ -243,7 +262,7 @@ class MultiGpuContext:
         def gen(g, c):
             a, ln = self._shard(g)
             c.generate_synthetic(n_total, first + a, ln, seed, h_cap, with_quantity, with_rgb)
-        self._map(gen)
+        self._all_or_none(gen)
 
     def reorder_spatial(self, n_strata=1, seed=1337, want_permutation=False):
         """Load-time ordering, shard by shard: every shard is cut into ceil(n_strata / G) strata, so the snapshot as a

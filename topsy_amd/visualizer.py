@@ -12,7 +12,7 @@ import logging
 
 import numpy as np
 
-from . import colormap, config, loader, overlays, particle_buffers, periodic_sph, sph
+from . import _native, colormap, config, loader, overlays, particle_buffers, periodic_sph, sph
 from .drawreason import DrawReason
 from .frames import FrameInterface
 
@@ -201,6 +201,17 @@ class VisualizerBase(FrameInterface):
                 self.data_loader.get_named_quantity(value)
             except Exception as e:
                 raise ValueError(f"Unable to get quantity named '{value}'") from e
+        old = self.particle_buffers.quantity_name
+        try:
+            self._switch_quantity(value)
+        except _native.BackendError:
+            # the upload failed and left the resident quantity as it was (a failed attribute upload changes nothing,
+            # include/topsy_splat.h): go on drawing that one
+            logger.error(f"Failed to switch to quantity '{value}'; reverting to '{old}'")
+            self._switch_quantity(old)
+            raise
+
+    def _switch_quantity(self, value):
         self.particle_buffers.quantity_name = value
         self.invalidate(DrawReason.CHANGE)
         self._colormap.update_parameters({"vmin": None, "vmax": None, "log": None})
