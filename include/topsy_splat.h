@@ -108,7 +108,9 @@ const char *tsp_last_error(void);
  * that returned TSP_EINVAL before) and the new entry point tsp_moment_sort; no struct changed, nothing else changed.
  * 120: new entry point tsp_sph_velocity_gradient (velocity divergence and curl by SPH gather sums); nothing else changed.
  * 121: a failed upload leaves no half-made state ("Failed uploads" below; it used to leave some arrays new, some old or
- * missing); no entry point or struct changed. */
+ * missing); no entry point or struct changed.
+ * 122: new entry point tsp_sph_sample_lattice and the struct tsp_lattice (SPH sums at the points of a lattice: 3-D grids, slices
+ * and rays); nothing else changed. */
 int tsp_version(void);
 int tsp_stats_size(void);
 
@@ -357,6 +359,44 @@ int tsp_sph_sum(tsp_context *ctx, int64_t n, const float *x, const float *y, con
 int tsp_sph_velocity_gradient(tsp_context *ctx, int64_t n, const float *x, const float *y, const float *z, const float *h,
                               const float *mass, const float *rho, const float *vx, const float *vy, const float *vz,
                               float period, float *div_out, float *curl_x_out, float *curl_y_out, float *curl_z_out);
+
+/* SPH sums at the points of a lattice: "what is the density, or the temperature, at this point in space?" on a regular 3-D grid
+ * (pynbody's to_3d_grid), a slice or a ray.  Host arrays in and out; uses ctx's device and stream only: resident particles, image,
+ * accumulator and tsp_stats unchanged.  The estimator is gather-form with the smoothing length taken at the sample point (yt's
+ * "gather" smoothing).  Float32 unless said otherwise, with these operations in this order (no fused multiply-adds):
+ *   - The lattice.  nq = nu * nv * nw points; point (i, j, k), 0 <= i < nu, 0 <= j < nv, 0 <= k < nw, has on every axis the
+ *     coordinate ((origin + (double)i * du) + (double)j * dv) + (double)k * dw in float64, rounded once to float32.  The
+ *     outputs are C-ordered [k][j][i], i fastest.  The point is used as it is: in a periodic box it may lie outside [0, period),
+ *     the wrap happens inside the distances only.
+ *   - Particle j is valid iff x[j], y[j], z[j] are finite; invalid particles are nobody's neighbour and contribute nothing.
+ *   - For a lattice point r, over every valid j: d2_j exactly as tsp_smoothing_lengths defines it, with dx = x[j] - r.x (nearest
+ *     image when period > 0).  h(r) = 0.5f * sqrtf(the n_neighbours-th smallest d2_j): the rule of tsp_smoothing_lengths, except
+ *     that no particle is the query itself (one that coincides with r counts like any other).  h_out[r] = h(r) as computed
+ *     (h_out may be NULL).
+ *   - For each of the n_fields fields a_f (1 <= n_fields <= 4), over every valid j:
+ *         u = sqrtf(d2_j) / h(r);  the term exists iff u < 2 (the n_neighbours-th neighbour itself, at u == 2, contributes nothing);
+ *         u2 = u * u;  w = u < 1 ? (1 - 1.5f * u2) + 0.75f * (u2 * u) : 0.25f * ((t * t) * t) with t = 2 - u   (tsp_sph_sum's w);
+ *         term = a_f[j] * w;  S_f += (double)term  (float64 sum, any order);
+ *     outs[f][r] = (float)(S_f / (M_PI * (double)((h * h) * h))) with h = h(r).
+ *     Where h(r) is not finite or is 0 (n_neighbours particles sit exactly on the point) every field at that point is NaN.  a_f[j]
+ *     is used as given: a NaN or an infinity propagates into the points whose sums it takes part in, and only those.
+ *     With a = mass this is the density at r; with a_0 = mass * q and a_1 = mass, outs[0] / outs[1] is the kernel-weighted mean
+ *     of q at r, and no per-particle rho is needed.
+ *   - The order of the sums is free but fixed (no atomics in them): the same call on the same input and device returns the same
+ *     bits; for a_f >= 0 any two orders agree to within one float32 ulp of the output.
+ * TSP_EINVAL, and nothing written: a NULL argument (h_out aside); n_fields outside [1, 4]; n, n_neighbours or period that
+ * tsp_smoothing_lengths refuses; fewer than n_neighbours valid particles; nu, nv or nw below 1 or nq >= 2^31; a lattice number
+ * that is not finite, or a lattice point that rounds to a float32 that is not finite.  The cost is that of a k-NN search and a
+ * range sum per lattice point.  Device memory is allocated for the call only (the index of tsp_smoothing_lengths, 4 n_fields
+ * bytes per particle twice, and 4 (1 + n_fields) bytes per lattice point); a failed allocation returns TSP_ENOMEM and writes
+ * nothing. */
+typedef struct {
+    double origin[3], du[3], dv[3], dw[3];
+    int32_t nu, nv, nw;
+} tsp_lattice;
+int tsp_sph_sample_lattice(tsp_context *ctx, int64_t n, const float *x, const float *y, const float *z, int n_fields,
+                           const float *const *fields, int n_neighbours, float period, const tsp_lattice *lattice,
+                           float *h_out /* nq floats, may be NULL */, float *const *outs /* n_fields pointers to nq floats */);
 
 /* The shrinking-sphere centre of a snapshot (Power et al. 2003): what pynbody.analysis.halo.center computes by default and the
  * reference asks for when it centres a snapshot at load (PynbodyDataLoader._perform_centering, src/topsy/loader.py:201-217, with

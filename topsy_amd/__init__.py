@@ -183,6 +183,52 @@ def sph_velocity_gradient(pos, mass, vel, smooth=None, rho=None, n_smooth=config
         ctx.close()
 
 
+def sph_grid(pos, mass, values=None, shape=(64, 64, 64), center=(0, 0, 0), size=None, rotation=None,
+             n_smooth=config.SMOOTH_NEIGHBOURS, periodicity_scale=None, device_id=0):
+    """SPH fields of an (n, 3) position array sampled on a regular 3-D grid on GPU `device_id` (C: tsp_sph_sample_lattice;
+    pynbody's to_3d_grid): shape = (nu, nv, nw) samples at the cell centres of a box of side `size` (required: one length or
+    three) centred on `center`, whose axes u, v, w are the rows of `rotation` (None: the identity).  The estimator is gather-form
+    with the smoothing length taken at the sample point: smooth = half the distance from the point to its n_smooth-th nearest
+    particle, rho = sum_j mass_j W(|r - r_j|, smooth) with the M4 cubic spline of support 2 smooth.  Returns a dict of float32
+    arrays indexed [k][j][i], shape (nw, nv, nu): "rho", "smooth" and, with `values`, "mean" = sum m q W / sum m W, the
+    kernel-weighted mean of values at the point (NaN where rho is 0 or NaN) -- and "points": the three float64 vectors (u, v, w) of
+    the samples' offsets from `center` along the axes, sample (i, j, k) lying at center + u[i] rotation[0] + v[j] rotation[1] +
+    w[k] rotation[2].  periodicity_scale: the side of a periodic box (None: open); the box may straddle its faces."""
+    from . import lattice
+    return lattice.sph_grid(pos, mass, values, shape=shape, center=center, size=size, rotation=rotation, n_smooth=n_smooth,
+                            periodicity_scale=periodicity_scale, device_id=device_id)
+
+
+def sph_slice(pos, mass, values=None, resolution=256, center=(0, 0, 0), size=None, rotation=None,
+              n_smooth=config.SMOOTH_NEIGHBOURS, periodicity_scale=None, device_id=0):
+    """SPH fields on the plane through `center` spanned by the first two rows of `rotation` (None: the x-y plane): sph_grid with
+    shape = (resolution, resolution, 1).  size (required): the side of the square, or (side along u, side along v).  Returns the
+    dict of sph_grid with (resolution, resolution) arrays indexed [j][i] and "points" = (u, v)."""
+    from . import lattice
+    n = lattice._count("resolution", resolution)
+    if size is not None and np.ndim(size) != 0:
+        try:
+            size = tuple(size)
+        except TypeError:
+            size = ()
+        if len(size) != 2:
+            raise ValueError(f"size must be a finite number > 0 or two of them, not {size!r}")
+        size = (size[0], size[1], 1.0)
+    out = sph_grid(pos, mass, values, shape=(n, n, 1), center=center, size=size, rotation=rotation, n_smooth=n_smooth,
+                   periodicity_scale=periodicity_scale, device_id=device_id)
+    return {name: a[:2] if name == "points" else a[0] for name, a in out.items()}
+
+
+def sph_ray(pos, mass, values=None, start=None, end=None, n_samples=256, n_smooth=config.SMOOTH_NEIGHBOURS,
+            periodicity_scale=None, device_id=0):
+    """SPH fields along the straight line from `start` to `end` (both required, both sampled; n_samples = 1 samples start):
+    tsp_sph_sample_lattice on a lattice of shape (n_samples, 1, 1).  Returns the dict of sph_grid with (n_samples,) arrays and
+    "points" = the (n_samples, 3) float64 coordinates of the samples."""
+    from . import lattice
+    return lattice.sph_ray(pos, mass, values, start=start, end=end, n_samples=n_samples, n_smooth=n_smooth,
+                           periodicity_scale=periodicity_scale, device_id=device_id)
+
+
 def shrink_sphere_center(pos, mass, select="all", r_start=None, shrink_factor=0.7, min_particles=100, device_id=0):
     """Shrinking-sphere centre (Power et al. 2003; pynbody.analysis.halo.center's default) of an (n, 3) position array on GPU
     `device_id` (C: tsp_shrink_sphere_center): starting from the centre of mass and a sphere of radius r_start (None: half the

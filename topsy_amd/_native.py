@@ -19,7 +19,8 @@ UNIQUE_ID_BYTES = 128
 ABI_VERSION = 112            # the oldest tsp_version() whose structs this binding matches; entry points added since
                              # (113: tsp_shrink_sphere_center, 114: tsp_fof_groups, 115: tsp_sphere_moments,
                              # 116: tsp_radial_profile, 117: the kinematic maps, 119: tsp_moment_sort,
-                             # 120: tsp_sph_velocity_gradient) are required by name in load_library()
+                             # 120: tsp_sph_velocity_gradient, 122: tsp_sph_sample_lattice) are required by name in
+                             # load_library()
 PRESENT_SCALAR, PRESENT_BIVARIATE, PRESENT_RGB, PRESENT_RGB_HDR, PRESENT_MOMENT_MEAN, PRESENT_MOMENT_SIGMA = 0, 1, 2, 3, 4, 5
 LAYER_QUAD, LAYER_LINES = 0, 1
 
@@ -89,6 +90,13 @@ class ProfileInfo(ctypes.Structure):
                 ("mass_inner", ctypes.c_double)]
 
 
+class Lattice(ctypes.Structure):
+    """struct tsp_lattice: point (i, j, k) is origin + i du + j dv + k dw."""
+    _fields_ = [("origin", ctypes.c_double * 3), ("du", ctypes.c_double * 3), ("dv", ctypes.c_double * 3),
+                ("dw", ctypes.c_double * 3), ("nu", ctypes.c_int32), ("nv", ctypes.c_int32), ("nw", ctypes.c_int32)]
+
+
+LATTICE_MAX_FIELDS = 4       # fields per tsp_sph_sample_lattice call
 PROFILE_SUMS = 11            # doubles per bin of tsp_radial_profile's sums_out: mass, ms, mc (3), mc2 (3), mj (3)
 
 
@@ -163,6 +171,8 @@ SIGNATURES = {
     "tsp_smoothing_lengths": (ctypes.c_int, [_ctx, ctypes.c_int64, _fp, _fp, _fp, ctypes.c_int, ctypes.c_float, _fp]),
     "tsp_sph_sum": (ctypes.c_int, [_ctx, ctypes.c_int64, _fp, _fp, _fp, _fp, _fp, ctypes.c_float, _fp]),
     "tsp_sph_velocity_gradient": (ctypes.c_int, [_ctx, ctypes.c_int64] + [_fp] * 9 + [ctypes.c_float] + [_fp] * 4),
+    "tsp_sph_sample_lattice": (ctypes.c_int, [_ctx, ctypes.c_int64, _fp, _fp, _fp, ctypes.c_int, ctypes.POINTER(_fp), ctypes.c_int,
+                                              ctypes.c_float, ctypes.POINTER(Lattice), _fp, ctypes.POINTER(_fp)]),
     "tsp_shrink_sphere_center": (ctypes.c_int, [_ctx, ctypes.c_int64, _fp, _fp, _fp, _fp, ctypes.c_float, ctypes.c_double,
                                                 ctypes.c_double, ctypes.c_int64, ctypes.c_int, ctypes.POINTER(ctypes.c_double),
                                                 ctypes.POINTER(CenterInfo)]),
@@ -248,6 +258,29 @@ def load_library():
                                  f"this binding needs version >= {ABI_VERSION} and {ctypes.sizeof(Stats)} bytes: rebuild the library")
     _lib = lib
     return lib
+
+
+def lattice_struct(origin, du, dv, dw, shape):
+    """The tsp_lattice of shape = (nu, nv, nw) points origin + i du + j dv + k dw.  Raises ValueError for a shape that is not
+    three integers >= 1 with fewer than 2^31 points in all, or vectors that are not three finite numbers."""
+    try:
+        dims = [int(v) for v in shape]
+        exact = all(not isinstance(v, bool) and int(v) == v for v in shape)
+    except (TypeError, ValueError):
+        dims, exact = [], False
+    if len(dims) != 3 or not exact or min(dims) < 1 or dims[0] * dims[1] * dims[2] >= 2 ** 31:
+        raise ValueError(f"shape must be three integers >= 1 with fewer than 2^31 points in all, not {shape!r}")
+    lat = Lattice()
+    for name, v in (("origin", origin), ("du", du), ("dv", dv), ("dw", dw)):
+        try:
+            a = np.asarray(v, dtype=np.float64)
+        except (TypeError, ValueError):
+            raise ValueError(f"{name} must be three finite numbers, not {v!r}") from None
+        if a.shape != (3,) or not np.isfinite(a).all():
+            raise ValueError(f"{name} must be three finite numbers, not {v!r}")
+        getattr(lat, name)[:] = a.tolist()
+    lat.nu, lat.nv, lat.nw = dims
+    return lat
 
 
 def _check(rc):
@@ -500,6 +533,29 @@ class Context:
         _check(self._lib.tsp_sph_velocity_gradient(self._h, n, *[_ptr(a) for a in arrs], float(np.float32(period or 0.0)),
                                                    _ptr(div), _ptr(planes[0]), _ptr(planes[1]), _ptr(planes[2])))
         return div, np.ascontiguousarray(planes.T)
+
+    def sph_sample_lattice(self, x, y, z, fields, k=32, period=None, origin=(0, 0, 0), du=(1, 0, 0), dv=(0, 1, 0), dw=(0, 0, 1),
+                           shape=(1, 1, 1)):
+        """SPH sums of 1 to 4 caller-ordered float32 per-particle `fields` at the points origin + i du + j dv + k dw of a
+        lattice of shape = (nu, nv, nw) points (tsp_sph_sample_lattice): at every point the smoothing length h is half the
+        distance to the k-th nearest particle and field f is sum_j fields[f][j] W(|r - r_j|, h) with the M4 spline of support
+        2 h; fields = [mass] gives the density, [mass * q, mass] the two sums whose ratio is the kernel-weighted mean of q.
+        Returns (h (nw, nv, nu), outs (len(fields), nw, nv, nu)) float32; the fields are NaN where h is 0 or not finite.
+        period: the side of a periodic box (None or 0: open).  Uses this context's device only; what is resident stays."""
+        n = len(x)
+        x, y, z = _f32(x, n, "x"), _f32(y, n, "y"), _f32(z, n, "z")
+        fields = [_f32(a, n, f"fields[{f}]") for f, a in enumerate(fields)]
+        if not 1 <= len(fields) <= LATTICE_MAX_FIELDS:
+            raise ValueError(f"1 to {LATTICE_MAX_FIELDS} fields per call, not {len(fields)}")
+        lat = lattice_struct(origin, du, dv, dw, shape)
+        nu, nv, nw = lat.nu, lat.nv, lat.nw
+        h = np.empty((nw, nv, nu), dtype=np.float32)
+        outs = np.empty((len(fields), nw, nv, nu), dtype=np.float32)
+        field_ptrs = (_fp * len(fields))(*[_ptr(a) for a in fields])
+        out_ptrs = (_fp * len(fields))(*[_ptr(outs[f]) for f in range(len(fields))])
+        _check(self._lib.tsp_sph_sample_lattice(self._h, n, _ptr(x), _ptr(y), _ptr(z), len(fields), field_ptrs, int(k),
+                                                float(np.float32(period or 0.0)), ctypes.byref(lat), _ptr(h), out_ptrs))
+        return h, outs
 
     def shrink_sphere_center(self, x, y, z, mass, mass_cut_factor=0.0, r_start=0.0, shrink_factor=0.7, min_particles=100,
                              max_iterations=256):

@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "tsp_internal.h"
+#include "tsp_morton.h"
 
 namespace tsp {
 
@@ -227,7 +228,7 @@ using namespace tsp;
 extern "C" {
 
 const char *tsp_last_error(void) { return g_err; }
-int tsp_version(void) { return 121; }     // 121: a failed upload is atomic (attributes: nothing changed; particles / synthetic: no particles left; groups: every member emptied); 120: tsp_sph_velocity_gradient; 119: tsp_moment_sort, TSP_PRESENT_MOMENT_MEAN / _SIGMA (the kinematic maps as the base of tsp_present / tsp_present_yuv420); 118: tsp_render_undo, tsp_group_render all-or-nothing across the members; 117: kinematic maps (tsp_upload_velocities, tsp_set_line_of_sight, TSP_MODE_KINEMATIC, tsp_velocity_moments, tsp_colormap_moment); 116: tsp_radial_profile; 115: tsp_sphere_moments; 114: tsp_fof_groups; 113: tsp_shrink_sphere_center; 112: tsp_present_surface, tsp_present_surface_yuv420; 111: tsp_content_neg_inf; 110: tsp_sph_sum; 109: tsp_present_yuv420; 108: tsp_present; 107: surface rendering; 106: tsp_smoothing_lengths; 101: tsp_stats gained ms_mega, n_mega (16 bytes); 102: the per-kernel fragment counts (32 bytes); 103: n_chunk_culled (8 bytes); 104: matrix-core / kernel-I options removed; 105: kernel M's options removed (kernel G draws the mid footprints)
+int tsp_version(void) { return 122; }     // 122: tsp_sph_sample_lattice and the struct tsp_lattice (SPH sums at the points of a lattice); 121: a failed upload is atomic (attributes: nothing changed; particles / synthetic: no particles left; groups: every member emptied); 120: tsp_sph_velocity_gradient; 119: tsp_moment_sort, TSP_PRESENT_MOMENT_MEAN / _SIGMA (the kinematic maps as the base of tsp_present / tsp_present_yuv420); 118: tsp_render_undo, tsp_group_render all-or-nothing across the members; 117: kinematic maps (tsp_upload_velocities, tsp_set_line_of_sight, TSP_MODE_KINEMATIC, tsp_velocity_moments, tsp_colormap_moment); 116: tsp_radial_profile; 115: tsp_sphere_moments; 114: tsp_fof_groups; 113: tsp_shrink_sphere_center; 112: tsp_present_surface, tsp_present_surface_yuv420; 111: tsp_content_neg_inf; 110: tsp_sph_sum; 109: tsp_present_yuv420; 108: tsp_present; 107: surface rendering; 106: tsp_smoothing_lengths; 101: tsp_stats gained ms_mega, n_mega (16 bytes); 102: the per-kernel fragment counts (32 bytes); 103: n_chunk_culled (8 bytes); 104: matrix-core / kernel-I options removed; 105: kernel M's options removed (kernel G draws the mid footprints)
 int tsp_stats_size(void) { return (int)sizeof(tsp_stats); }
 
 int tsp_device_count(void) {
@@ -952,14 +953,20 @@ int tsp_colormap_rgb_host(tsp_context *ctx, const float *img, int H, int W, int 
     return unstage_host_image(ctx, hs, out_rgba8, o8, out_rgba_f32, of);
 }
 
-int tsp_smoothing_lengths(tsp_context *ctx, int64_t n, const float *x, const float *y, const float *z, int n_neighbours,
-                          float period, float *h_out) {
-    TSP_REQUIRE(ctx && x && y && z && h_out, TSP_EINVAL, "NULL argument");
+// what a k-nearest-neighbour search accepts (tsp_smoothing_lengths, tsp_sph_sample_lattice)
+static int check_neighbour_search(int64_t n, int n_neighbours, float period) {
     TSP_REQUIRE(n >= 1 && n < (1ll << 31), TSP_EINVAL, "n = %lld outside [1, 2^31)", (long long)n);
     TSP_REQUIRE(n_neighbours >= 2 && n_neighbours <= 64, TSP_EINVAL, "n_neighbours = %d outside [2, 64]", n_neighbours);
     TSP_REQUIRE(period == 0.0f || (std::isfinite(period) && period > 0.0f), TSP_EINVAL,
                 "period must be 0 (open box) or finite and > 0, not %g", (double)period);
     TSP_REQUIRE(n >= n_neighbours, TSP_EINVAL, "%lld particles, n_neighbours = %d", (long long)n, n_neighbours);
+    return TSP_OK;
+}
+
+int tsp_smoothing_lengths(tsp_context *ctx, int64_t n, const float *x, const float *y, const float *z, int n_neighbours,
+                          float period, float *h_out) {
+    TSP_REQUIRE(ctx && x && y && z && h_out, TSP_EINVAL, "NULL argument");
+    if (const int rc = check_neighbour_search(n, n_neighbours, period)) return rc;
     TSP_HIP(hipSetDevice(ctx->device));
     return smoothing_lengths(ctx, n, x, y, z, n_neighbours, period == 0.0f ? 0.0f : period, h_out);
 }
@@ -988,6 +995,31 @@ int tsp_sph_velocity_gradient(tsp_context *ctx, int64_t n, const float *x, const
     const float *fields[5] = {mass, rho, vx, vy, vz};
     float *outs[4] = {div_out, curl_x_out, curl_y_out, curl_z_out};
     return sph_sum(ctx, n, x, y, z, h, SPH_GATHER_VELOCITY_GRADIENT, fields, 5, period == 0.0f ? 0.0f : period, outs, 4);
+}
+
+int tsp_sph_sample_lattice(tsp_context *ctx, int64_t n, const float *x, const float *y, const float *z, int n_fields,
+                           const float *const *fields, int n_neighbours, float period, const tsp_lattice *lattice, float *h_out,
+                           float *const *outs) {
+    TSP_REQUIRE(ctx && x && y && z && fields && lattice && outs, TSP_EINVAL, "NULL argument");
+    TSP_REQUIRE(n_fields >= 1 && n_fields <= 4, TSP_EINVAL, "n_fields = %d outside [1, 4]", n_fields);
+    for (int f = 0; f < n_fields; ++f) TSP_REQUIRE(fields[f] && outs[f], TSP_EINVAL, "NULL field or output %d", f);
+    if (const int rc = check_neighbour_search(n, n_neighbours, period)) return rc;
+    const tsp_lattice &lat = *lattice;
+    TSP_REQUIRE(lat.nu >= 1 && lat.nv >= 1 && lat.nw >= 1, TSP_EINVAL, "lattice of %d x %d x %d points", lat.nu, lat.nv, lat.nw);
+    TSP_REQUIRE((int64_t)lat.nu * lat.nv < (1ll << 31) && (int64_t)lat.nu * lat.nv * lat.nw < (1ll << 31), TSP_EINVAL,
+                "lattice of %d x %d x %d points: 2^31 or more", lat.nu, lat.nv, lat.nw);
+    for (int a = 0; a < 3; ++a)
+        TSP_REQUIRE(std::isfinite(lat.origin[a]) && std::isfinite(lat.du[a]) && std::isfinite(lat.dv[a]) && std::isfinite(lat.dw[a]),
+                    TSP_EINVAL, "the lattice has a non-finite number on axis %d", a);
+    // every coordinate is affine in (i, j, k), and so is every partial sum of the rule: the extremes are at the corners
+    for (int corner = 0; corner < 8; ++corner) {
+        float p[3];
+        lattice_point(lat, corner & 1 ? lat.nu - 1 : 0, corner & 2 ? lat.nv - 1 : 0, corner & 4 ? lat.nw - 1 : 0, p[0], p[1], p[2]);
+        TSP_REQUIRE(std::isfinite(p[0]) && std::isfinite(p[1]) && std::isfinite(p[2]), TSP_EINVAL,
+                    "a corner of the lattice, (%g, %g, %g), is not a finite float32", (double)p[0], (double)p[1], (double)p[2]);
+    }
+    TSP_HIP(hipSetDevice(ctx->device));
+    return sph_sample_lattice(ctx, n, x, y, z, n_fields, fields, n_neighbours, period == 0.0f ? 0.0f : period, lattice, h_out, outs);
 }
 
 int tsp_shrink_sphere_center(tsp_context *ctx, int64_t n, const float *x, const float *y, const float *z, const float *mass,

@@ -297,6 +297,11 @@ int smoothing_lengths(tsp_context *ctx, int64_t n, const float *x, const float *
 enum { SPH_GATHER_SUM = 0, SPH_GATHER_VELOCITY_GRADIENT = 1 };
 int sph_sum(tsp_context *ctx, int64_t n, const float *x, const float *y, const float *z, const float *h, int mode,
             const float *const *fields, int n_fields, float period, float *const *outs, int n_outs);
+// tsp_smooth.hip: the SPH sums of n_fields per-particle fields at the points of a lattice, with h taken at the point from its k
+// nearest particles (tsp_sph_sample_lattice); per-call DeviceScratch only, through the sites of sph_sum().
+int sph_sample_lattice(tsp_context *ctx, int64_t n, const float *x, const float *y, const float *z, int n_fields,
+                       const float *const *fields, int k, float period, const tsp_lattice *lattice, float *h_out,
+                       float *const *outs);
 // tsp_fof.hip: friends-of-friends groups over the index of tsp_morton.h; per-call DeviceScratch only, no context state
 int fof_groups(tsp_context *ctx, int64_t n, const float *x, const float *y, const float *z, float linking_length, float period,
                int64_t min_members, int32_t *group_out, tsp_fof_info *info_out);

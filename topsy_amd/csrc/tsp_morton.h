@@ -91,6 +91,15 @@ static __device__ __forceinline__ float displacement(float qx, float qy, float q
     return (dx * dx + dy * dy) + dz * dz;
 }
 
+// The contract's lattice point (tsp_sph_sample_lattice): ((origin + i du) + j dv) + k dw per axis in float64, these operations in
+// this order, unfused, rounded once to float32.  The host forms the corners by the same code when it checks the lattice.
+static __host__ __device__ __forceinline__ void lattice_point(const tsp_lattice &lat, int i, int j, int k, float &x, float &y, float &z) {
+    float p[3];
+    for (int a = 0; a < 3; ++a)
+        p[a] = (float)(((lat.origin[a] + (double)i * lat.du[a]) + (double)j * lat.dv[a]) + (double)k * lat.dw[a]);
+    x = p[0], y = p[1], z = p[2];
+}
+
 // first index in [lo, hi) whose key is >= key (hi when none)
 static __device__ __forceinline__ int64_t key_lower_bound(const uint64_t *__restrict__ keys, int64_t lo, int64_t hi, uint64_t key) {
     while (lo < hi) {

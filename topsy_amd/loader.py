@@ -1034,6 +1034,24 @@ class ArrayDataLoader(AbstractDataLoader):
         pos, mass, vel = check_moments_arrays(self._pos, self._mass, self._vel)
         return self._with_context(lambda ctx: compute_profile(ctx, pos, mass, vel, kwargs, G))
 
+    def sample_lattice(self, lattice_spec, quantity=None):
+        """{"rho", "smooth"[, "mean"]} of topsy_amd.lattice.sample on the lattice `lattice_spec` (dict: origin, du, dv, dw, shape),
+        found on the GPU (tsp_sph_sample_lattice) from the host arrays in the loader's periodic box; quantity: the name of the
+        loader quantity whose kernel-weighted mean is "mean" (KeyError if there is none of that name)."""
+        from . import lattice
+        if self._pos.ndim != 2 or self._pos.shape[1] != 3 or self._mass.shape != (len(self._pos),):
+            raise ValueError(f"a lattice needs pos of shape (n, 3) and one mass per particle, not {self._pos.shape} and "
+                             f"{self._mass.shape}")
+        n_smooth, period = check_smoothing_arguments(self.n_smooth, self._period)
+        if quantity is not None and quantity not in self.get_quantity_names():
+            raise KeyError(f"no quantity named {quantity!r}: the loader has {self.get_quantity_names()}")
+        n_finite = int(np.isfinite(self._pos).all(axis=1).sum())
+        if n_finite < n_smooth:
+            raise ValueError(f"{n_finite} particles have finite coordinates; n_smooth = {n_smooth} needs at least as many")
+        values = None if quantity is None else np.asarray(self.get_named_quantity(quantity), dtype=np.float32)
+        pos, mass = np.asarray(self._pos, dtype=np.float32), np.asarray(self._mass, dtype=np.float32)
+        return self._with_context(lambda ctx: lattice.sample(ctx, pos, mass, values, n_smooth, period, lattice_spec))
+
     def virial_radius(self, rho_threshold, r_max, center=None, refinements=3):
         """The radius about `center` (None: the initial centre) inside which the mean density is rho_threshold, by the rule of
         topsy_amd.virial_radius, found on the GPU from the host arrays."""

@@ -236,6 +236,10 @@ class MultiGpuContext:
         """The velocity divergence and curl over the whole (caller-ordered) snapshot, on the first context like sph_sum."""
         return self.contexts[0].sph_velocity_gradient(x, y, z, h, mass, rho, vx, vy, vz, period)
 
+    def sph_sample_lattice(self, x, y, z, fields, k=32, period=None, **lattice):
+        """The SPH sums at the points of a lattice over the whole (caller-ordered) snapshot, on the first context like sph_sum."""
+        return self.contexts[0].sph_sample_lattice(x, y, z, fields, k, period, **lattice)
+
     def shrink_sphere_center(self, x, y, z, mass, **kwargs):
         """The shrinking-sphere centre of the whole (caller-ordered) snapshot, on the first context like smoothing_lengths."""
         return self.contexts[0].shrink_sphere_center(x, y, z, mass, **kwargs)

@@ -347,6 +347,19 @@ class VisualizerBase(FrameInterface):
             frame = np.asarray(self.rotation_matrix, dtype=np.float64)
         return ld.profile(r_max, center=center, frame=frame, **kwargs)
 
+    def get_slice_image(self, quantity=None, resolution=None):
+        """The SPH field on the view's centre plane (depth 0 in view coordinates), float32 (R, R) at R = resolution (None: the
+        render resolution): the density for quantity=None, else the kernel-weighted mean of that loader quantity, evaluated at
+        the pixel centres with the smoothing length taken at the point (topsy_amd.sph_grid's estimator).  Pixel (row, col) is the
+        point centre_on_pixel(row, col) would centre on at zero depth.  The sums are found on the GPU from the loader's host
+        arrays (tsp_sph_sample_lattice); the rendered frame stays as it is."""
+        from . import lattice
+        ld = self._array_loader("a slice")
+        res = lattice._count("resolution", self._render_resolution if resolution is None else resolution)
+        spec = lattice.slice_lattice(self.rotation_matrix, self.position_offset, self.scale, res)
+        out = ld.sample_lattice(spec, quantity)
+        return out["rho" if quantity is None else "mean"][0]
+
     def scale_to_virial(self, rho_threshold, r_max, factor=1.0):
         """Set scale to `factor` times the virial radius (topsy_amd.virial_radius: mean enclosed density rho_threshold, searched
         out to r_max) of what the view is centred on, -position_offset: after centre_on_halo(N) the view then frames halo N.
