@@ -110,7 +110,9 @@ const char *tsp_last_error(void);
  * 121: a failed upload leaves no half-made state ("Failed uploads" below; it used to leave some arrays new, some old or
  * missing); no entry point or struct changed.
  * 122: new entry point tsp_sph_sample_lattice and the struct tsp_lattice (SPH sums at the points of a lattice: 3-D grids, slices
- * and rays); nothing else changed. */
+ * and rays); nothing else changed.
+ * 123: new entry point tsp_gravity_direct and the struct tsp_gravity_info (softened direct-sum gravity: the potential and the
+ * accelerations at targets, for 'phi' and a disc's rotation curve); nothing else changed. */
 int tsp_version(void);
 int tsp_stats_size(void);
 
@@ -566,6 +568,57 @@ int tsp_radial_profile(tsp_context *ctx, int64_t n, const float *x, const float 
                        const float *vx, const float *vy, const float *vz,      /* all three or none (NULL) */
                        const tsp_profile_spec *spec, int64_t *count_out /* n_bins */, double *sums_out /* n_bins * 11 */,
                        tsp_profile_info *info_out);
+
+/* Softened direct-sum gravity: the potential and the acceleration at every target from every source -- pynbody's gravity.calc
+ * direct sum, from which a snapshot's 'phi' and a disc profile's midplane rotation curve and potential are taken.  Host arrays in,
+ * caller's order; uses ctx's device and stream only, in every context state: resident particles, image, accumulator and tsp_stats
+ * unchanged.  G = 1 (the caller multiplies).
+ *   - Sums.  With d = t_i - s_j per component and r2 = d . d + eps_j^2 (Plummer softening with the source's length):
+ *         pot_i = - sum_j m_j r2^(-1/2),        acc_i = - sum_j m_j r2^(-3/2) d.
+ *     eps = NULL: every source has the softening length eps_all (the same bits as an array holding that value).
+ *   - Sources.  Source j takes part iff sx[j], sy[j], sz[j], mass[j] and its softening length are finite; n_valid_sources counts
+ *     those.  A source with mass 0 takes part (and adds zeros).
+ *   - Pairs.  A pair with r2 == 0 (distance 0 and eps_j = 0) contributes nothing; so does one with r2 below 2^-126, and one whose
+ *     r2 overflows float32.  Coincident distinct particles with eps > 0 are ordinary pairs.
+ *   - Targets.  tx, ty, tz all NULL: the targets are the sources (n_tgt must equal n_src), and the pair i == j by index contributes
+ *     nothing.  A target with a non-finite coordinate gets NaN in every output and is not counted in n_valid_targets; with NULL
+ *     targets that is decided by the coordinates alone (a source left out for its mass is still a target).
+ *   - Outputs.  pot_out[i], acc_out[3 i + (0, 1, 2)] = (ax, ay, az); either may be NULL, not both: what both forms of the call
+ *     return is equal bit for bit.
+ *   - Arithmetic.  Pair terms in float32: d by one subtraction each, eps_j^2 by one multiplication,
+ *     r2 = fma(dx, dx, fma(dy, dy, fma(dz, dz, eps_j^2))), inv = the hardware reciprocal square root of r2 (1 ulp), the potential term
+ *     p = m_j * inv, the acceleration terms fma(w, d, .) with w = p * (inv * inv).  Per target, runs of 16 consecutive sources
+ *     (indices 16 k .. 16 k + 15) are added in float32 in index order, the runs in float64 in index order within a contiguous
+ *     range of source tiles, and the ranges in index order.
+ *   - Error bound.  Against the float64 evaluation of the formulae on the float32 inputs, per output component,
+ *         |got - want| <= TSP_GRAVITY_ERROR_K * 2^-24 * sum_j |term_ij|,      TSP_GRAVITY_ERROR_K = 64.
+ *     The account, u = 2^-24: each d within u; eps^2 within u; r2 within 2u + 3u; inv within 2.5u + 2u (1 ulp <= 2u): 5u; p within
+ *     6u; inv * inv within 11u, w within 18u, an acceleration term within 19u; a float32 run of 16 terms adds 15u; the float64
+ *     additions add less than n_src * 2^-53 <= 4u.  25u for the potential, 38u for an acceleration component.  It holds for pairs
+ *     with 2^-80 <= r2 <= 2^80 whose m_j r2^(-3/2) is 0 or lies in float32's normal range [2^-126, 2^127], and for coordinates
+ *     whose differences do not overflow float32; outside that range the float32 terms may flush, overflow or (a difference that is
+ *     infinite) turn a target's acceleration into NaN.
+ *   - Determinism.  No floating-point atomics; the order of every sum is a function of n_src, n_tgt and the device (the sources
+ *     are cut into tiles of TSP_GRAVITY_SOURCE_TILE, the targets into launches of 2^18 and workgroups of up to
+ *     TSP_GRAVITY_TARGETS_PER_WORKGROUP, the tiles into ranges by the launch's target count and the device's CU count): the same
+ *     call returns the same bits, and a target's values do not depend on the other targets of a launch with the same number of
+ *     target workgroups.
+ * 1 <= n_src, n_tgt < 2^31; no NULL among sx, sy, sz, mass; eps_all finite and >= 0 when eps is NULL (ignored otherwise); the
+ * targets all three NULL (then n_tgt == n_src) or none NULL; at least one of pot_out and acc_out; at least one valid source;
+ * anything else returns TSP_EINVAL and writes nothing.  info_out is optional.  Not provided: periodic images (no Ewald sum), and
+ * a tree -- the cost is n_src * n_tgt pairs, whatever the geometry (measured rates: DESIGN.md).  Device memory is allocated for the
+ * call only (20 bytes per source, 44 per target, at most 32 MB of partial sums on 256 CUs); a failed allocation returns TSP_ENOMEM
+ * and writes nothing. */
+#define TSP_GRAVITY_SOURCE_TILE 512                 /* sources per tile of the pair kernel */
+#define TSP_GRAVITY_TARGETS_PER_WORKGROUP 1024      /* targets of a workgroup at most (fewer than 513 targets: 256 or 512) */
+#define TSP_GRAVITY_ERROR_K 64
+typedef struct { int64_t n_valid_sources, n_valid_targets; } tsp_gravity_info;
+int tsp_gravity_direct(tsp_context *ctx,
+        int64_t n_src, const float *sx, const float *sy, const float *sz, const float *mass,
+        const float *eps /* n_src softening lengths, or NULL: eps_all for every source */, float eps_all,
+        int64_t n_tgt, const float *tx, const float *ty, const float *tz /* all three NULL: the targets are the sources */,
+        double *pot_out /* n_tgt, or NULL */, double *acc_out /* n_tgt * 3, (ax, ay, az) per target, or NULL */,
+        tsp_gravity_info *info_out /* optional */);
 
 /* Kinematic maps: the mass-weighted mean line-of-sight velocity and its dispersion per pixel, from resident velocities (what
  * pynbody's image(qty="vz", av_z=True) draws after analysis.angmom.sideon; the reference has no such mode).  The rgb kernels

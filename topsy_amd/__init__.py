@@ -26,7 +26,7 @@ def test(nparticle=config.TEST_DATA_NUM_PARTICLES_DEFAULT, **kwargs):
 
 
 def from_arrays(pos, smooth, mass, quantities=None, rgb=None, with_cells=False, n_smooth=None, periodicity_scale=None,
-                center="none", halos=None, vel=None, orient="none", orient_radius=None, orient_method=None, **kwargs):
+                center="none", halos=None, vel=None, orient="none", orient_radius=None, orient_method=None, eps=None, **kwargs):
     """Visualizer over caller-supplied numpy arrays (e.g. taken from a pynbody snapshot).
 
     smooth=None computes the smoothing lengths on the GPU from the n_smooth (default config.SMOOTH_NEIGHBOURS) nearest
@@ -59,14 +59,21 @@ def from_arrays(pos, smooth, mass, quantities=None, rgb=None, with_cells=False, 
 
     vis.profile(r_max, ...) is the radial profile (radial_profile) of what the view shows -- about the view's centre, in the
     view's frame: after orient("faceon"), geometry="disc" gives the rotation curve -- and vis.scale_to_virial(rho_threshold,
-    r_max) sets the view's scale to the virial radius (virial_radius) of what it is centred on."""
+    r_max) sets the view's scale to the virial radius (virial_radius) of what it is centred on.
+
+    eps: the gravitational softening, one length or one per particle.  With it 'phi' is a quantity too, listed after the
+    other derived names (vis.quantity_name = "phi"): the potential of every particle from all the others with G = 1, a direct
+    sum on the GPU on first use (gravity_direct; n^2 pairs, refused above config.GRAVITY_DIRECT_MAX_PAIRS) and cached on the
+    loader -- and vis.rotation_curve(radii) is the disc's rotation curve and midplane potential (rotation_curve) about the view's
+    centre in the view's frame."""
     from . import visualizer, loader
     return visualizer.Visualizer(data_loader_class=loader.ArrayDataLoader,
                                  data_loader_kwargs={"pos": pos, "smooth": smooth, "mass": mass,
                                                      "quantities": quantities, "rgb": rgb, "with_cells": with_cells,
                                                      "n_smooth": n_smooth, "periodicity_scale": periodicity_scale,
                                                      "center": center, "halos": halos, "vel": vel, "orient": orient,
-                                                     "orient_radius": orient_radius, "orient_method": orient_method},
+                                                     "orient_radius": orient_radius, "orient_method": orient_method,
+                                                     "eps": eps},
                                  **kwargs)
 
 
@@ -312,6 +319,49 @@ def radial_profile(pos, mass, vel=None, center=(0, 0, 0), r_max=None, r_min=0.0,
         ctx.close()
 
 
+def gravity_direct(pos, mass, eps, targets=None, G=1.0, device_id=0):
+    """The gravitational potential and acceleration of the particles of an (n, 3) position array at `targets` (k, 3), or at the
+    particles themselves (None: a particle does not act on itself), by a direct sum on GPU `device_id` (C: tsp_gravity_direct):
+    pot_i = -G sum_j mass_j / sqrt(|t_i - r_j|^2 + eps_j^2), acc_i = -G sum_j mass_j (t_i - r_j) / (|t_i - r_j|^2 + eps_j^2)^(3/2)
+    -- Plummer softening with the source's length, pynbody's direct sum (snap['phi']).  eps: one softening length >= 0 or one
+    per particle.  Pair terms are float32, the sums float64; the rounding stays within 64 * 2^-24 of the sum of the terms'
+    magnitudes.  A particle with a non-finite coordinate, mass or eps exerts nothing; a target with a non-finite coordinate gets
+    NaN; a pair at distance 0 with eps 0 contributes nothing.  The cost is n * k pairs: no tree, no periodic images.
+    Returns (pot float64 (k,), acc float64 (k, 3))."""
+    from . import _native, gravity
+    pos, mass, eps = gravity.check_arrays(pos, mass, eps)
+    G = gravity.check_G(G)
+    t = None if targets is None else gravity.check_targets(targets)
+    ctx = _native.Context(1, 2, device_id)
+    try:
+        pot, acc, _ = gravity.compute_gravity(ctx, np.asarray(pos, dtype=np.float32), mass, eps, t)
+    finally:
+        ctx.close()
+    return G * pot, G * acc
+
+
+def rotation_curve(pos, mass, eps, radii, center=(0, 0, 0), frame=None, G=1.0, device_id=0):
+    """The midplane rotation curve and potential of the particles of an (n, 3) position array, from direct sums of the softened
+    forces at probe points (C: tsp_gravity_direct) on GPU `device_id`: what pynbody's disc profile takes v_circ and pot from
+    (gravity.calc.midplane_rot_curve / midplane_potential).  pynbody's source was not at hand when this was written, so the
+    rule stated here is the contract.  With the rows (e1, e2, e3) of `frame` (None: the identity; the matrix of
+    topsy_amd.orientation(..., orient="faceon") puts the disc's axis in e3), every radius R of `radii` gets four probes,
+    center + R e1, center - R e1, center + R e2, center - R e2; v_circ(R) is the mean over the four of
+    sqrt(max(0, -a . (p - center))) with a the acceleration at the probe p, pot(R) the mean of the four potentials.  center is
+    subtracted from pos in float64 before the sums are formed in float32, so that probes and nearby sources keep their digits.
+    eps, G and the treatment of non-finite particles: as gravity_direct.  Unlike Profile.v_circ = sqrt(G M(<r) / r), which is
+    exact for a spherical mass distribution only, this is right for a disc.  The cost is 4 len(radii) * n pairs.
+    Returns a RotationCurve (topsy_amd/gravity.py): .radii, .v_circ, .pot (n_radii,), .acc (n_radii, 4, 3)."""
+    from . import _native, gravity
+    pos, mass, eps = gravity.check_arrays(pos, mass, eps)
+    radii, c, frame, G = gravity.check_radii(radii), gravity.check_center(center), gravity.check_frame(frame), gravity.check_G(G)
+    ctx = _native.Context(1, 2, device_id)
+    try:
+        return gravity.compute_rotation_curve(ctx, pos, mass, eps, radii, c, frame, G)
+    finally:
+        ctx.close()
+
+
 def virial_radius(pos, mass, center, rho_threshold, r_max, refinements=3, device_id=0):
     """The radius about `center` inside which the mean density is rho_threshold (pynbody.analysis.halo.virial_radius for arrays;
     rho_threshold is e.g. 200 times the critical density in the caller's units), on GPU `device_id` (C: tsp_radial_profile).
@@ -384,7 +434,10 @@ def velocity_maps(pos, smooth, mass, vel, rotation=None, center=(0, 0, 0), scale
 
 def __getattr__(name):
     """topsy_amd.VisualizationRecorder (movie recording and export, topsy_amd/recorder), topsy_amd.FofCatalogue and
-    topsy_amd.Profile (topsy_amd/loader.py), imported on first use."""
+    topsy_amd.Profile (topsy_amd/loader.py), topsy_amd.RotationCurve (topsy_amd/gravity.py), imported on first use."""
+    if name == "RotationCurve":
+        from .gravity import RotationCurve
+        return RotationCurve
     if name == "FofCatalogue":
         from .loader import FofCatalogue
         return FofCatalogue

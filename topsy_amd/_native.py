@@ -19,8 +19,8 @@ UNIQUE_ID_BYTES = 128
 ABI_VERSION = 112            # the oldest tsp_version() whose structs this binding matches; entry points added since
                              # (113: tsp_shrink_sphere_center, 114: tsp_fof_groups, 115: tsp_sphere_moments,
                              # 116: tsp_radial_profile, 117: the kinematic maps, 119: tsp_moment_sort,
-                             # 120: tsp_sph_velocity_gradient, 122: tsp_sph_sample_lattice) are required by name in
-                             # load_library()
+                             # 120: tsp_sph_velocity_gradient, 122: tsp_sph_sample_lattice, 123: tsp_gravity_direct) are
+                             # required by name in load_library()
 PRESENT_SCALAR, PRESENT_BIVARIATE, PRESENT_RGB, PRESENT_RGB_HDR, PRESENT_MOMENT_MEAN, PRESENT_MOMENT_SIGMA = 0, 1, 2, 3, 4, 5
 LAYER_QUAD, LAYER_LINES = 0, 1
 
@@ -96,6 +96,16 @@ class Lattice(ctypes.Structure):
                 ("dw", ctypes.c_double * 3), ("nu", ctypes.c_int32), ("nv", ctypes.c_int32), ("nw", ctypes.c_int32)]
 
 
+class GravityInfo(ctypes.Structure):
+    """struct tsp_gravity_info."""
+    _fields_ = [("n_valid_sources", ctypes.c_int64), ("n_valid_targets", ctypes.c_int64)]
+
+
+# tsp_gravity_direct (the header's TSP_GRAVITY_* constants): sources per tile of the pair kernel, targets of a workgroup at most,
+# and K of its error bound |got - want| <= K * 2^-24 * sum |term|
+GRAVITY_SOURCE_TILE = 512
+GRAVITY_TARGETS_PER_WORKGROUP = 1024
+GRAVITY_ERROR_K = 64
 LATTICE_MAX_FIELDS = 4       # fields per tsp_sph_sample_lattice call
 PROFILE_SUMS = 11            # doubles per bin of tsp_radial_profile's sums_out: mass, ms, mc (3), mc2 (3), mj (3)
 
@@ -182,6 +192,9 @@ SIGNATURES = {
                                           ctypes.c_double, ctypes.c_double, ctypes.POINTER(Moments)]),
     "tsp_radial_profile": (ctypes.c_int, [_ctx, ctypes.c_int64, _fp, _fp, _fp, _fp, _fp, _fp, _fp, ctypes.POINTER(ProfileSpec), _i64p,
                                           ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ProfileInfo)]),
+    "tsp_gravity_direct": (ctypes.c_int, [_ctx, ctypes.c_int64, _fp, _fp, _fp, _fp, _fp, ctypes.c_float, ctypes.c_int64, _fp, _fp, _fp,
+                                          ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double),
+                                          ctypes.POINTER(GravityInfo)]),
     "tsp_set_sphere_mips": (ctypes.c_int, [_ctx, _fp, ctypes.c_int, ctypes.c_int]),
     "tsp_density_order_stats": (ctypes.c_int, [_ctx, _i64p, ctypes.c_int, _fp]),
     "tsp_render_surface": (ctypes.c_int, [_ctx, _fp, ctypes.c_float, ctypes.c_float, _i64p, _i64p, ctypes.c_int, ctypes.c_int,
@@ -647,6 +660,36 @@ class Context:
                                             sums.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), ctypes.byref(info)))
         return {"count": count, "sums": sums, "n_valid": int(info.n_valid), "n_inner": int(info.n_inner),
                 "n_binned": int(info.n_binned), "mass_inner": float(info.mass_inner)}
+
+    def gravity_direct(self, sx, sy, sz, mass, eps, targets=None, want_pot=True, want_acc=True):
+        """The softened direct sum (tsp_gravity_direct, G = 1) of the float32 sources at `targets` = (tx, ty, tz), or at the
+        sources themselves (None: the pair of a particle with itself is left out).  eps: one softening length for every source or
+        an array of them.  Returns (pot float64 (n_tgt,) or None, acc float64 (n_tgt, 3) or None, dict(n_valid_sources,
+        n_valid_targets)); NaN at a target with a non-finite coordinate.  The cost is n_src * n_tgt pairs.  Uses this context's
+        device only; what is resident stays."""
+        n = len(sx)
+        sx, sy, sz, mass = _f32(sx, n, "sx"), _f32(sy, n, "sy"), _f32(sz, n, "sz"), _f32(mass, n, "mass")
+        if np.ndim(eps) == 0:
+            eps_array, eps_all = None, float(np.float32(eps))
+        else:
+            eps_array, eps_all = _f32(eps, n, "eps"), 0.0
+        if targets is None:
+            n_tgt, (tx, ty, tz) = n, (None, None, None)
+        else:
+            if len(targets) != 3:
+                raise ValueError("targets must be the three arrays (tx, ty, tz)")
+            n_tgt = len(targets[0])
+            tx, ty, tz = (_f32(t, n_tgt, name) for t, name in zip(targets, ("tx", "ty", "tz")))
+        if not (want_pot or want_acc):
+            raise ValueError("at least one of want_pot and want_acc must be set")
+        pot = np.empty(n_tgt, dtype=np.float64) if want_pot else None
+        acc = np.empty((n_tgt, 3), dtype=np.float64) if want_acc else None
+        info = GravityInfo()
+        dp = ctypes.POINTER(ctypes.c_double)
+        _check(self._lib.tsp_gravity_direct(self._h, n, _ptr(sx), _ptr(sy), _ptr(sz), _ptr(mass), _ptr(eps_array), eps_all, n_tgt,
+                                            _ptr(tx), _ptr(ty), _ptr(tz), None if pot is None else pot.ctypes.data_as(dp),
+                                            None if acc is None else acc.ctypes.data_as(dp), ctypes.byref(info)))
+        return pot, acc, {"n_valid_sources": int(info.n_valid_sources), "n_valid_targets": int(info.n_valid_targets)}
 
     # ---- surface (include/topsy_splat.h "Surface rendering") ---------------------------------
     def set_sphere_mips(self, mips, n0=64, n_levels=4):

@@ -41,4 +41,9 @@ SPATIAL_ORDER_MAX_STRATA = 400
 # consecutive particles dealt to the shards in turn; "auto" = interleaved when the loader brings its own cell layout (its
 # order is then spatially sorted and index ranges are spatial slabs of very different cost), contiguous otherwise.
 MULTI_GPU_SHARD_ASSIGNMENT = "auto"
+# The most pairs (sources x targets) a direct gravity sum that the library starts on its own account may take: the first use of
+# 'phi' of from_arrays(..., eps=...).  A direct sum costs every pair and nothing cuts it short, so above this
+# get_named_quantity("phi") raises instead of starting an hour-long call.  The value is about a minute of the measured rate of
+# the potential-only sum on one MI355X, 3.96e12 pairs a second: n = 1.5e7 particles.
+GRAVITY_DIRECT_MAX_PAIRS = 2.4e14
 MULTI_GPU_INTERLEAVE_BLOCK = 4096

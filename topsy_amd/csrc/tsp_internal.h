@@ -231,6 +231,10 @@ int scratch_alloc(tsp_context *ctx, const char *site, DeviceScratch &buf, size_t
         if (rc_ != TSP_OK) return rc_;                                               \
     } while (0)
 
+// The two scratch buffers that every gather call (tsp_smooth.hip) and the direct gravity sum (tsp_gravity.hip) take, in this
+// order: the one place that owns their sites (tsp_api.hip).  Each caller partitions them by offsets of its own.
+int gather_scratch(tsp_context *ctx, DeviceScratch &dh, size_t h_bytes, DeviceScratch &da, size_t a_bytes);
+
 // Every device buffer that can be (re)allocated after tsp_create -- the resident particle arrays, the render workspace, the
 // colormap and post-pass staging -- goes through alloc_group().  A group is the buffers that are only ever used together, with the capacity
 // fields that describe them: the group is freed and its capacities zeroed first, then each buffer is allocated, and only once all
@@ -318,6 +322,11 @@ int sphere_moments(tsp_context *ctx, int64_t n, const float *x, const float *y, 
 int radial_profile(tsp_context *ctx, int64_t n, const float *x, const float *y, const float *z, const float *mass, const float *vx,
                    const float *vy, const float *vz, const tsp_profile_spec *spec, int64_t *count_out, double *sums_out,
                    tsp_profile_info *info_out);
+// tsp_gravity.hip: the softened direct sum of potential and acceleration at the targets (tsp_gravity_direct; tx == nullptr: the
+// targets are the sources); per-call DeviceScratch only, through the sites of gather_scratch(); no context state
+int gravity_direct(tsp_context *ctx, int64_t n_src, const float *sx, const float *sy, const float *sz, const float *mass,
+                   const float *eps, float eps_all, int64_t n_tgt, const float *tx, const float *ty, const float *tz, double *pot_out,
+                   double *acc_out, tsp_gravity_info *info_out);
 // tsp_surface.hip: the occlusion pass + resolve (keys in image64, (q, depth) in image), the rho order statistics and the
 // filter + shading; per-call memory is DeviceScratch
 int render_surface(tsp_context *ctx, const Camera &cam, float cut, const int64_t *h_starts, const int64_t *h_lens,

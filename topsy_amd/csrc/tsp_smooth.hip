@@ -736,13 +736,6 @@ int smoothing_lengths(tsp_context *ctx, int64_t n, const float *x, const float *
     return TSP_OK;
 }
 
-// The two scratch buffers that every gather call takes beyond the index, in this order: the one place that owns their sites.
-static int gather_scratch(tsp_context *ctx, DeviceScratch &dh, size_t h_bytes, DeviceScratch &da, size_t a_bytes) {
-    TSP_SCRATCH_ALLOC(ctx, SITE("sph_sum_h"), dh, h_bytes);
-    TSP_SCRATCH_ALLOC(ctx, SITE("sph_sum_a"), da, a_bytes);
-    return TSP_OK;
-}
-
 // The host side of both gather calls over the index.  mode SPH_GATHER_SUM: fields = {a}, outs = {out} (tsp_sph_sum);
 // SPH_GATHER_VELOCITY_GRADIENT: fields = {mass, rho, vx, vy, vz}, outs = {div, curl_x, curl_y, curl_z}.
 // Device memory beyond the index: the raw h ("sph_sum_h", n floats) and one buffer ("sph_sum_a") partitioned by offsets --

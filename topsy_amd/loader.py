@@ -731,16 +731,28 @@ class ArrayDataLoader(AbstractDataLoader):
     or along the minor axis of the particles' second-moment tensor ("shape", the default without).  orient_radius is required:
     no single length suits every snapshot.  get_initial_rotation() computes the matrix on the GPU (tsp_sphere_moments) on first
     use, on the same context as 'rho', and caches it (orient_moments holds the moments); set_initial_rotation() restores it from
-    the caller's cache.  orientation() gives the matrix for any sphere.  Out of scope: periodic wrapping of the displacements."""
+    the caller's cache.  orientation() gives the matrix for any sphere.  Out of scope: periodic wrapping of the displacements.
+
+    eps: the gravitational softening, one length >= 0 or one per particle (permuted with the other arrays under with_cells).
+    With it 'phi' is a quantity, listed after the other derived names (every pynbody snapshot has one): the potential of every
+    particle from all the others, Plummer-softened with the source's length, G = 1 -- a direct sum on the GPU
+    (tsp_gravity_direct) on first use, on the same context as 'rho', cached as float32.  It costs n^2 pairs; above
+    config.GRAVITY_DIRECT_MAX_PAIRS the first use raises ValueError instead.  rotation_curve() is the midplane rotation curve
+    (topsy_amd.rotation_curve) from the same arrays.  Without eps nothing changes: names, order, errors."""
 
     # reference PynbodyDataInMemory.get_rgb_masses (loader.py:115-121): (band, weight) per rgb channel
     RGB_BANDS = (("I", 0.5), ("V", 1.0), ("U", 1.0))
 
     def __init__(self, device=None, pos=None, smooth=None, mass=None, quantities=None, rgb=None,
                  units="kpc", periodicity_scale=None, with_cells=False, band_magnitudes=None, n_smooth=None,
-                 center="none", halos=None, vel=None, orient="none", orient_radius=None, orient_method=None):
+                 center="none", halos=None, vel=None, orient="none", orient_radius=None, orient_method=None, eps=None):
         super().__init__(device)
         self._pos = np.asarray(pos, dtype=np.float32)
+        self._eps = None                 # the gravitational softening: a float, or float32 (n,) in this loader's order
+        self._phi = None                 # the computed potential ('phi' with eps=), in this loader's order
+        if eps is not None:
+            from . import gravity
+            self._eps = gravity.check_eps(eps, len(self._pos))
         self._vel = None if vel is None else np.asarray(vel, dtype=np.float32)
         if self._vel is not None and (self._pos.ndim != 2 or self._vel.shape != self._pos.shape or self._pos.shape[1] != 3):
             raise ValueError(f"vel must have shape (n, 3) like pos, not {self._vel.shape} (pos: {self._pos.shape})")
@@ -810,6 +822,8 @@ class ArrayDataLoader(AbstractDataLoader):
                 self._halos_option = self._halos_option[order]
             if self._vel is not None:
                 self._vel = self._vel[order]
+            if isinstance(self._eps, np.ndarray):
+                self._eps = self._eps[order]
 
     def __len__(self):
         return len(self._pos)
@@ -837,6 +851,8 @@ class ArrayDataLoader(AbstractDataLoader):
             return self._density()
         if name in VELOCITY_QUANTITIES and name not in self._quantities and self._vel is not None:
             return self._derived_velocity_quantity(name)
+        if name == "phi" and name not in self._quantities and self._eps is not None:
+            return self._potential()
         return self._quantities[name]
 
     def get_quantity_names(self):
@@ -845,7 +861,42 @@ class ArrayDataLoader(AbstractDataLoader):
             names.append("rho")
         if self._vel is not None:
             names += [name for name in VELOCITY_QUANTITIES if name not in self._quantities]
+        if self._eps is not None and "phi" not in self._quantities:
+            names.append("phi")
         return names
+
+    def get_softening(self):
+        """The gravitational softening of eps=: a float, float32 (n,) in this loader's order, or None."""
+        return self._eps
+
+    def _gravity_arrays(self):
+        if self._pos.ndim != 2 or self._pos.shape[1] != 3 or self._mass.shape != (len(self._pos),):
+            raise ValueError(f"gravity needs pos of shape (n, 3) and one mass per particle, not {self._pos.shape} and "
+                             f"{self._mass.shape}")
+        return self._pos, self._mass
+
+    def _potential(self):
+        """'phi': the potential of every particle from all the others (tsp_gravity_direct, G = 1), float32 like every quantity;
+        computed on first use on the context that computes 'rho', and cached."""
+        if self._phi is None:
+            from . import gravity
+            pos, mass = self._gravity_arrays()
+            gravity.check_pair_count(len(pos), len(pos), "'phi'")
+            pot = self._with_context(lambda ctx: gravity.compute_gravity(ctx, pos, mass, self._eps, None, want_acc=False))[0]
+            self._phi = pot.astype(np.float32)
+        return self._phi
+
+    def rotation_curve(self, radii, center=None, frame=None, eps=None, G=1.0):
+        """The RotationCurve (topsy_amd.rotation_curve) of the particles about `center` (None: the initial centre) in `frame`,
+        found on the GPU (tsp_gravity_direct) from the host arrays; eps=None: the loader's own softening (eps=)."""
+        from . import gravity
+        pos, mass = self._gravity_arrays()
+        eps = self._eps if eps is None else gravity.check_eps(eps, len(pos))
+        if eps is None:
+            raise ValueError("no softening length: pass eps= here or to from_arrays / ArrayDataLoader")
+        center = self.get_initial_center() if center is None else center
+        radii, c, frame, G = gravity.check_radii(radii), gravity.check_center(center), gravity.check_frame(frame), gravity.check_G(G)
+        return self._with_context(lambda ctx: gravity.compute_rotation_curve(ctx, pos, mass, eps, radii, c, frame, G))
 
     def set_density_context(self, context):
         """The context that computes 'rho' on first use (ParticleBuffers hands over its own; None: one made for the call)."""
