@@ -112,7 +112,9 @@ const char *tsp_last_error(void);
  * 122: new entry point tsp_sph_sample_lattice and the struct tsp_lattice (SPH sums at the points of a lattice: 3-D grids, slices
  * and rays); nothing else changed.
  * 123: new entry point tsp_gravity_direct and the struct tsp_gravity_info (softened direct-sum gravity: the potential and the
- * accelerations at targets, for 'phi' and a disc's rotation curve); nothing else changed. */
+ * accelerations at targets, for 'phi' and a disc's rotation curve); nothing else changed.
+ * 124: new entry point tsp_gravity_tree and the struct tsp_gravity_tree_info (the same sums by a Barnes-Hut tree over the
+ * Morton order, O(n log n)); nothing else changed. */
 int tsp_version(void);
 int tsp_stats_size(void);
 
@@ -619,6 +621,55 @@ int tsp_gravity_direct(tsp_context *ctx,
         int64_t n_tgt, const float *tx, const float *ty, const float *tz /* all three NULL: the targets are the sources */,
         double *pot_out /* n_tgt, or NULL */, double *acc_out /* n_tgt * 3, (ax, ay, az) per target, or NULL */,
         tsp_gravity_info *info_out /* optional */);
+
+/* Barnes-Hut tree gravity: the sums of tsp_gravity_direct in O(n log n), by a tree that is implicit in the Morton order of the
+ * sources (topsy_amd/csrc/tsp_gravity_tree.hip).  Host arrays in, caller's order; uses ctx's device and stream only, in every
+ * context state: resident particles, image, accumulator and tsp_stats unchanged.  G = 1.  What is said of tsp_gravity_direct holds
+ * here too -- the sums, the softening with the source's length, which sources, pairs and targets count, the self pair (left out by
+ * the caller's index when the targets are the sources), the outputs and their order, "nothing is written on failure" -- except:
+ *   - mass[j] < 0 returns TSP_EINVAL (a centre of mass needs masses >= 0; 0 is fine), and so does theta outside [0, 1] or not
+ *     finite.
+ *   - Tree.  The sources with finite coordinates are sorted along the 63-bit Morton curve of their bounding box (a source whose
+ *     mass or softening length is not finite stays in the order with mass 0 and is not counted valid).  A leaf is
+ *     TSP_GRAVITY_TREE_LEAF consecutive sorted particles, a node of level l + 1 is TSP_GRAVITY_TREE_FANOUT consecutive nodes of
+ *     level l; the last node of a level may be partial; the top level has one node.  A node carries its mass M, its centre of
+ *     mass c, the second moments Q_ab = sum m (x - c)_a (x - c)_b, the mass-weighted mean e2 of eps^2, and a radius b that is no
+ *     smaller than the distance from c to the farthest corner of the members' bounding box.  Sums in float64, stored in float32.
+ *   - Walk.  The targets are taken in groups of 64 (targets = sources: 64 consecutive particles of the Morton order; separate
+ *     targets: 64 consecutive targets in the caller's order -- pass neighbours next to each other, the group's box decides what is
+ *     opened).  With dmin the distance from the group's bounding box to c, a node with M > 0 is accepted iff
+ *         dmin * theta > b      and      dmin^2 + e2_min >= 8 (e2_max - e2_min)
+ *     (e2_min, e2_max over the members with mass; the second rule matters only where the softening varies inside the node, and
+ *     keeps the mean e2 from being used at distances where the spread of eps^2 would show).  An accepted node adds, with
+ *     d = t - c, r2 = d . d + e2, u = d r2^(-1/2), s = u . Q u, T = tr Q:
+ *         pot -= r2^(-1/2) (M + (1.5 s - 0.5 T) / r2),
+ *         acc -= ((M + (7.5 s - 1.5 T) / r2) u - 3 Q u / r2) / r2;
+ *     a node that is not accepted is opened: its children are tested, and a leaf's particles are summed as tsp_gravity_direct
+ *     sums pairs.  A node without mass adds nothing.  theta = 0 accepts nothing: the call is the direct sum with the sources in
+ *     Morton order.  A node that holds a target of the group is never accepted (b >= |c - t| >= dmin), so the self pair only
+ *     arises in a leaf.  A target's value may depend on which other targets share its group (they decide what is opened), not
+ *     on anything else: the same call returns the same bits (no floating-point atomics).
+ *   - Error.  Rounding, against the float64 evaluation of the same terms: TSP_GRAVITY_TREE_ERROR_K * 2^-24 * sum |term| per
+ *     output component; with theta = 0 that is a bound against the direct sum itself.  A node whose mass is one particle's
+ *     (every other member massless) gives that particle's pair term within 32 * 2^-24 relative.  The truncation (what the
+ *     octupole and higher moments of the accepted nodes would add) is not bounded by the library; DESIGN.md has measured values
+ *     (theta = 0.5: 99 % of the accelerations within 1e-2 relative in the scenes measured there).
+ *   - info_out (optional): n_nodes, n_levels (the leaves' level included), pairs_direct = target-particle terms evaluated,
+ *     pairs_node = target-node terms evaluated (integer counts over the valid targets).
+ * 1 <= n_src, n_tgt < 2^31; arguments otherwise as tsp_gravity_direct; at least one source must be valid.  Device memory for the
+ * call only (about 75 bytes per source, the neighbour index included, beside the sort's temporary storage; 44 bytes per separate
+ * target, 64 per particle when the targets are the sources), through the allocation sites of the neighbour index and the gather
+ * sums; a failed allocation returns TSP_ENOMEM and writes nothing. */
+#define TSP_GRAVITY_TREE_LEAF 32                    /* sorted particles per leaf */
+#define TSP_GRAVITY_TREE_FANOUT 8                   /* nodes of a level per node of the next */
+#define TSP_GRAVITY_TREE_ERROR_K 64
+typedef struct { int64_t n_valid_sources, n_valid_targets, n_nodes, n_levels, pairs_direct, pairs_node; } tsp_gravity_tree_info;
+int tsp_gravity_tree(tsp_context *ctx,
+        int64_t n_src, const float *sx, const float *sy, const float *sz, const float *mass,
+        const float *eps /* n_src softening lengths, or NULL: eps_all for every source */, float eps_all,
+        int64_t n_tgt, const float *tx, const float *ty, const float *tz /* all three NULL: the targets are the sources */,
+        float theta, double *pot_out /* n_tgt, or NULL */, double *acc_out /* n_tgt * 3, or NULL */,
+        tsp_gravity_tree_info *info_out /* optional */);
 
 /* Kinematic maps: the mass-weighted mean line-of-sight velocity and its dispersion per pixel, from resident velocities (what
  * pynbody's image(qty="vz", av_z=True) draws after analysis.angmom.sideon; the reference has no such mode).  The rgb kernels

@@ -1,6 +1,7 @@
 """Time tsp_gravity_direct (softened direct-sum gravity) in its two regimes.
 
     python tools/gpu_gravity_bench.py [--n 262144] [--targets 400] [--sources 1e7] [--repeats 3] [--clock-ghz 2.4]
+    python tools/gpu_gravity_bench.py --tree [--theta 0.5] [--n 1048576] [--repeats 3] [--direct-up-to 1048576]
 
 Cases, all on one context after a warm-up at 2^14: 'phi' of every particle (targets = sources, n = 2^18, the potential only: what
 from_arrays(eps=...) runs), the same with the accelerations, and a rotation curve's shape (400 targets against 1e7 sources, both
@@ -13,7 +14,13 @@ each) the inner loop's VALU instructions, counted in the disassembly of gravity_
 (hipcc --offload-arch=gfx950 --save-temps; the unchecked loop: 16 sources x 4 targets per iteration), at their issue cycles on
 one SIMD -- full-rate float32 2 cycles, v_rsq_f32 (quarter rate) 8, the float64 conversions and additions 4 -- over
 4 SIMDs x CUs at --clock-ghz.  Counts per pair: with accelerations 13.03 full-rate + 1 rsq + 0.5 float64 (930 VALU per 64
-pairs); the potential only 8.03 + 1 + 0.125 (586 per 64)."""
+pairs); the potential only 8.03 + 1 + 0.125 (586 per 64).
+
+--tree times tsp_gravity_tree instead, on the same Plummer sphere by the same method: targets = sources with accelerations at
+--n, the library's report of the walk kernel (kernel_ms), of the tree's build kernels (build_ms) and of the index (index_ms, host
+clock: upload, keys, sort), the particle and node terms per target, the walk's terms per second as a share of the direct kernel's
+measured pairs per second, and -- up to --direct-up-to particles -- the direct sum of the same particles next to it.
+"""
 import argparse
 import json
 import os
@@ -64,6 +71,43 @@ def timed(call):
     return dt, {k: float(v) for k, v in re.findall(r"(\w+)=([0-9.eE+-]+)(?=\s|$)", lines[-1])} if lines else {}
 
 
+def tree_main(args, _native):
+    n, eps = int(args.n), 0.01
+    ctx = _native.Context(16, 2)
+    w = plummer(2 ** 14, 1)
+    wm = np.full(len(w), 1.0 / len(w), dtype=np.float32)
+    ctx.gravity_tree(w[:, 0], w[:, 1], w[:, 2], wm, eps, theta=args.theta)                   # warm-up: code objects
+    ctx.gravity_direct(w[:, 0], w[:, 1], w[:, 2], wm, eps)
+    p = plummer(n, 2)
+    x, y, z = (np.ascontiguousarray(p[:, k]) for k in range(3))
+    m = np.full(n, 1.0 / n, dtype=np.float32)
+    result = {"n": n, "theta": args.theta}
+    times, report, info = [], {}, {}
+    for _ in range(args.repeats):
+        holder = []
+        dt, report = timed(lambda: holder.append(ctx.gravity_tree(x, y, z, m, eps, theta=args.theta)[2]))
+        times.append(dt)
+        info = holder[0]
+    terms = info["pairs_direct"] + info["pairs_node"]
+    kernel_s = 1e-3 * report.get("kernel_ms", float("nan"))
+    result["tree"] = {"wall_s": times, "kernel_ms": report.get("kernel_ms"), "build_ms": report.get("build_ms"),
+                      "index_ms": report.get("index_ms"), "pairs_direct_per_target": info["pairs_direct"] / n,
+                      "pairs_node_per_target": info["pairs_node"] / n, "n_nodes": info["n_nodes"], "n_levels": info["n_levels"],
+                      "terms_per_s": terms / kernel_s, "share_of_direct_rate": terms / kernel_s / args.direct_pairs_per_s,
+                      "equivalent_direct_pairs_per_s": float(n) * n / kernel_s}
+    if n <= args.direct_up_to:
+        times, report = [], {}
+        for _ in range(args.repeats):
+            dt, report = timed(lambda: ctx.gravity_direct(x, y, z, m, eps))
+            times.append(dt)
+        kernel_s = 1e-3 * report.get("kernel_ms", float("nan"))
+        result["direct"] = {"wall_s": times, "kernel_ms": report.get("kernel_ms"), "pairs_per_s": float(n) * n / kernel_s}
+    else:
+        result["direct_extrapolated"] = {"kernel_ms": 1e3 * float(n) * n / args.direct_pairs_per_s, "pairs_per_s": args.direct_pairs_per_s}
+    ctx.close()
+    print(json.dumps(result), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=float, default=2 ** 18)
@@ -72,8 +116,14 @@ def main():
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--clock-ghz", type=float, default=2.4)
     ap.add_argument("--cu-count", type=int, default=256)
+    ap.add_argument("--tree", action="store_true", help="time tsp_gravity_tree (targets = sources, with accelerations) at --n")
+    ap.add_argument("--theta", type=float, default=0.5)
+    ap.add_argument("--direct-up-to", type=float, default=2 ** 20, help="--tree: also time the direct sum up to this n")
+    ap.add_argument("--direct-pairs-per-s", type=float, default=2.66e12, help="--tree: the direct kernel's measured rate with accelerations")
     args = ap.parse_args()
     from topsy_amd import _native
+    if args.tree:
+        return tree_main(args, _native)
     n, n_src, n_tgt = int(args.n), int(args.sources), args.targets
     eps = 0.01
     ctx = _native.Context(16, 2)

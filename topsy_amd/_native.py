@@ -19,8 +19,8 @@ UNIQUE_ID_BYTES = 128
 ABI_VERSION = 112            # the oldest tsp_version() whose structs this binding matches; entry points added since
                              # (113: tsp_shrink_sphere_center, 114: tsp_fof_groups, 115: tsp_sphere_moments,
                              # 116: tsp_radial_profile, 117: the kinematic maps, 119: tsp_moment_sort,
-                             # 120: tsp_sph_velocity_gradient, 122: tsp_sph_sample_lattice, 123: tsp_gravity_direct) are
-                             # required by name in load_library()
+                             # 120: tsp_sph_velocity_gradient, 122: tsp_sph_sample_lattice, 123: tsp_gravity_direct,
+                             # 124: tsp_gravity_tree) are required by name in load_library()
 PRESENT_SCALAR, PRESENT_BIVARIATE, PRESENT_RGB, PRESENT_RGB_HDR, PRESENT_MOMENT_MEAN, PRESENT_MOMENT_SIGMA = 0, 1, 2, 3, 4, 5
 LAYER_QUAD, LAYER_LINES = 0, 1
 
@@ -106,6 +106,19 @@ class GravityInfo(ctypes.Structure):
 GRAVITY_SOURCE_TILE = 512
 GRAVITY_TARGETS_PER_WORKGROUP = 1024
 GRAVITY_ERROR_K = 64
+
+
+class GravityTreeInfo(ctypes.Structure):
+    """struct tsp_gravity_tree_info."""
+    _fields_ = [(name, ctypes.c_int64) for name in ("n_valid_sources", "n_valid_targets", "n_nodes", "n_levels", "pairs_direct",
+                                                    "pairs_node")]
+
+
+# tsp_gravity_tree (the header's TSP_GRAVITY_TREE_* constants): sorted particles per leaf, nodes of a level per node of the next,
+# and K of its rounding bound
+GRAVITY_TREE_LEAF = 32
+GRAVITY_TREE_FANOUT = 8
+GRAVITY_TREE_ERROR_K = 64
 LATTICE_MAX_FIELDS = 4       # fields per tsp_sph_sample_lattice call
 PROFILE_SUMS = 11            # doubles per bin of tsp_radial_profile's sums_out: mass, ms, mc (3), mc2 (3), mj (3)
 
@@ -195,6 +208,9 @@ SIGNATURES = {
     "tsp_gravity_direct": (ctypes.c_int, [_ctx, ctypes.c_int64, _fp, _fp, _fp, _fp, _fp, ctypes.c_float, ctypes.c_int64, _fp, _fp, _fp,
                                           ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double),
                                           ctypes.POINTER(GravityInfo)]),
+    "tsp_gravity_tree": (ctypes.c_int, [_ctx, ctypes.c_int64, _fp, _fp, _fp, _fp, _fp, ctypes.c_float, ctypes.c_int64, _fp, _fp, _fp,
+                                        ctypes.c_float, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double),
+                                        ctypes.POINTER(GravityTreeInfo)]),
     "tsp_set_sphere_mips": (ctypes.c_int, [_ctx, _fp, ctypes.c_int, ctypes.c_int]),
     "tsp_density_order_stats": (ctypes.c_int, [_ctx, _i64p, ctypes.c_int, _fp]),
     "tsp_render_surface": (ctypes.c_int, [_ctx, _fp, ctypes.c_float, ctypes.c_float, _i64p, _i64p, ctypes.c_int, ctypes.c_int,
@@ -667,6 +683,17 @@ class Context:
         an array of them.  Returns (pot float64 (n_tgt,) or None, acc float64 (n_tgt, 3) or None, dict(n_valid_sources,
         n_valid_targets)); NaN at a target with a non-finite coordinate.  The cost is n_src * n_tgt pairs.  Uses this context's
         device only; what is resident stays."""
+        return self._gravity(False, sx, sy, sz, mass, eps, targets, 0.0, want_pot, want_acc)
+
+    def gravity_tree(self, sx, sy, sz, mass, eps, targets=None, theta=0.5, want_pot=True, want_acc=True):
+        """The same sums by the Barnes-Hut tree over the Morton order of the sources (tsp_gravity_tree, G = 1): arguments and
+        results as gravity_direct, with the opening angle theta in [0, 1] (0: nothing is accepted, the direct sum in Morton
+        order) and masses >= 0.  The dict holds n_valid_sources, n_valid_targets, n_nodes, n_levels, pairs_direct and pairs_node
+        (target-particle and target-node terms evaluated).  Separate targets are walked in groups of 64 in the order given:
+        neighbours next to each other prune best."""
+        return self._gravity(True, sx, sy, sz, mass, eps, targets, float(theta), want_pot, want_acc)
+
+    def _gravity(self, tree, sx, sy, sz, mass, eps, targets, theta, want_pot, want_acc):
         n = len(sx)
         sx, sy, sz, mass = _f32(sx, n, "sx"), _f32(sy, n, "sy"), _f32(sz, n, "sz"), _f32(mass, n, "mass")
         if np.ndim(eps) == 0:
@@ -684,12 +711,15 @@ class Context:
             raise ValueError("at least one of want_pot and want_acc must be set")
         pot = np.empty(n_tgt, dtype=np.float64) if want_pot else None
         acc = np.empty((n_tgt, 3), dtype=np.float64) if want_acc else None
-        info = GravityInfo()
+        info = GravityTreeInfo() if tree else GravityInfo()
         dp = ctypes.POINTER(ctypes.c_double)
-        _check(self._lib.tsp_gravity_direct(self._h, n, _ptr(sx), _ptr(sy), _ptr(sz), _ptr(mass), _ptr(eps_array), eps_all, n_tgt,
-                                            _ptr(tx), _ptr(ty), _ptr(tz), None if pot is None else pot.ctypes.data_as(dp),
-                                            None if acc is None else acc.ctypes.data_as(dp), ctypes.byref(info)))
-        return pot, acc, {"n_valid_sources": int(info.n_valid_sources), "n_valid_targets": int(info.n_valid_targets)}
+        sources = (self._h, n, _ptr(sx), _ptr(sy), _ptr(sz), _ptr(mass), _ptr(eps_array), eps_all, n_tgt, _ptr(tx), _ptr(ty), _ptr(tz))
+        outputs = (None if pot is None else pot.ctypes.data_as(dp), None if acc is None else acc.ctypes.data_as(dp), ctypes.byref(info))
+        if tree:
+            _check(self._lib.tsp_gravity_tree(*sources, theta, *outputs))
+        else:
+            _check(self._lib.tsp_gravity_direct(*sources, *outputs))
+        return pot, acc, {name: int(getattr(info, name)) for name, _ in info._fields_}
 
     # ---- surface (include/topsy_splat.h "Surface rendering") ---------------------------------
     def set_sphere_mips(self, mips, n0=64, n_levels=4):

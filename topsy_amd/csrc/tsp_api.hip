@@ -234,7 +234,7 @@ using namespace tsp;
 extern "C" {
 
 const char *tsp_last_error(void) { return g_err; }
-int tsp_version(void) { return 123; }     // 123: tsp_gravity_direct and the struct tsp_gravity_info (softened direct-sum gravity: potential, accelerations); 122: tsp_sph_sample_lattice and the struct tsp_lattice (SPH sums at the points of a lattice); 121: a failed upload is atomic (attributes: nothing changed; particles / synthetic: no particles left; groups: every member emptied); 120: tsp_sph_velocity_gradient; 119: tsp_moment_sort, TSP_PRESENT_MOMENT_MEAN / _SIGMA (the kinematic maps as the base of tsp_present / tsp_present_yuv420); 118: tsp_render_undo, tsp_group_render all-or-nothing across the members; 117: kinematic maps (tsp_upload_velocities, tsp_set_line_of_sight, TSP_MODE_KINEMATIC, tsp_velocity_moments, tsp_colormap_moment); 116: tsp_radial_profile; 115: tsp_sphere_moments; 114: tsp_fof_groups; 113: tsp_shrink_sphere_center; 112: tsp_present_surface, tsp_present_surface_yuv420; 111: tsp_content_neg_inf; 110: tsp_sph_sum; 109: tsp_present_yuv420; 108: tsp_present; 107: surface rendering; 106: tsp_smoothing_lengths; 101: tsp_stats gained ms_mega, n_mega (16 bytes); 102: the per-kernel fragment counts (32 bytes); 103: n_chunk_culled (8 bytes); 104: matrix-core / kernel-I options removed; 105: kernel M's options removed (kernel G draws the mid footprints)
+int tsp_version(void) { return 124; }     // 124: tsp_gravity_tree and the struct tsp_gravity_tree_info (Barnes-Hut tree gravity over the Morton order); 123: tsp_gravity_direct and the struct tsp_gravity_info (softened direct-sum gravity: potential, accelerations); 122: tsp_sph_sample_lattice and the struct tsp_lattice (SPH sums at the points of a lattice); 121: a failed upload is atomic (attributes: nothing changed; particles / synthetic: no particles left; groups: every member emptied); 120: tsp_sph_velocity_gradient; 119: tsp_moment_sort, TSP_PRESENT_MOMENT_MEAN / _SIGMA (the kinematic maps as the base of tsp_present / tsp_present_yuv420); 118: tsp_render_undo, tsp_group_render all-or-nothing across the members; 117: kinematic maps (tsp_upload_velocities, tsp_set_line_of_sight, TSP_MODE_KINEMATIC, tsp_velocity_moments, tsp_colormap_moment); 116: tsp_radial_profile; 115: tsp_sphere_moments; 114: tsp_fof_groups; 113: tsp_shrink_sphere_center; 112: tsp_present_surface, tsp_present_surface_yuv420; 111: tsp_content_neg_inf; 110: tsp_sph_sum; 109: tsp_present_yuv420; 108: tsp_present; 107: surface rendering; 106: tsp_smoothing_lengths; 101: tsp_stats gained ms_mega, n_mega (16 bytes); 102: the per-kernel fragment counts (32 bytes); 103: n_chunk_culled (8 bytes); 104: matrix-core / kernel-I options removed; 105: kernel M's options removed (kernel G draws the mid footprints)
 int tsp_stats_size(void) { return (int)sizeof(tsp_stats); }
 
 int tsp_device_count(void) {
@@ -1123,6 +1123,25 @@ int tsp_gravity_direct(tsp_context *ctx, int64_t n_src, const float *sx, const f
     if (!eps) TSP_REQUIRE(std::isfinite(eps_all) && eps_all >= 0.0f, TSP_EINVAL, "eps_all must be finite and >= 0, not %g", (double)eps_all);
     TSP_HIP(hipSetDevice(ctx->device));
     return gravity_direct(ctx, n_src, sx, sy, sz, mass, eps, eps_all, n_tgt, tx, ty, tz, pot_out, acc_out, info_out);
+}
+
+int tsp_gravity_tree(tsp_context *ctx, int64_t n_src, const float *sx, const float *sy, const float *sz, const float *mass,
+                     const float *eps, float eps_all, int64_t n_tgt, const float *tx, const float *ty, const float *tz, float theta,
+                     double *pot_out, double *acc_out, tsp_gravity_tree_info *info_out) {
+    TSP_REQUIRE(ctx && sx && sy && sz && mass, TSP_EINVAL, "NULL argument");
+    TSP_REQUIRE((tx && ty && tz) || (!tx && !ty && !tz), TSP_EINVAL, "tx, ty and tz must be given together or not at all");
+    TSP_REQUIRE(pot_out || acc_out, TSP_EINVAL, "neither pot_out nor acc_out is given");
+    TSP_REQUIRE(n_src >= 1 && n_src < (1ll << 31), TSP_EINVAL, "n_src = %lld outside [1, 2^31)", (long long)n_src);
+    TSP_REQUIRE(n_tgt >= 1 && n_tgt < (1ll << 31), TSP_EINVAL, "n_tgt = %lld outside [1, 2^31)", (long long)n_tgt);
+    TSP_REQUIRE(tx || n_tgt == n_src, TSP_EINVAL, "without targets n_tgt must be n_src = %lld, not %lld", (long long)n_src,
+                (long long)n_tgt);
+    if (!eps) TSP_REQUIRE(std::isfinite(eps_all) && eps_all >= 0.0f, TSP_EINVAL, "eps_all must be finite and >= 0, not %g", (double)eps_all);
+    TSP_REQUIRE(std::isfinite(theta) && theta >= 0.0f && theta <= 1.0f, TSP_EINVAL, "theta = %g outside [0, 1]", (double)theta);
+    for (int64_t j = 0; j < n_src; ++j)      // (NaN passes: that source is left out)
+        TSP_REQUIRE(!(mass[j] < 0.0f), TSP_EINVAL, "mass[%lld] = %g is negative: a centre of mass needs masses >= 0", (long long)j,
+                    (double)mass[j]);
+    TSP_HIP(hipSetDevice(ctx->device));
+    return gravity_tree(ctx, n_src, sx, sy, sz, mass, eps, eps_all, n_tgt, tx, ty, tz, theta, pot_out, acc_out, info_out);
 }
 
 int tsp_present(tsp_context *ctx, int width, int height, const tsp_present_base *base, const tsp_present_layer *layers,

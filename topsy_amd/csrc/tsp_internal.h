@@ -327,6 +327,11 @@ int radial_profile(tsp_context *ctx, int64_t n, const float *x, const float *y, 
 int gravity_direct(tsp_context *ctx, int64_t n_src, const float *sx, const float *sy, const float *sz, const float *mass,
                    const float *eps, float eps_all, int64_t n_tgt, const float *tx, const float *ty, const float *tz, double *pot_out,
                    double *acc_out, tsp_gravity_info *info_out);
+// tsp_gravity_tree.hip: the same sums by a Barnes-Hut tree over the Morton order of the sources (tsp_gravity_tree); per-call
+// DeviceScratch only, through the sites of build_morton_index() and gather_scratch(); no context state
+int gravity_tree(tsp_context *ctx, int64_t n_src, const float *sx, const float *sy, const float *sz, const float *mass,
+                 const float *eps, float eps_all, int64_t n_tgt, const float *tx, const float *ty, const float *tz, float theta,
+                 double *pot_out, double *acc_out, tsp_gravity_tree_info *info_out);
 // tsp_surface.hip: the occlusion pass + resolve (keys in image64, (q, depth) in image), the rho order statistics and the
 // filter + shading; per-call memory is DeviceScratch
 int render_surface(tsp_context *ctx, const Camera &cam, float cut, const int64_t *h_starts, const int64_t *h_lens,

@@ -1,4 +1,5 @@
-"""Direct-sum gravity for arrays: the host side of topsy_amd.gravity_direct and topsy_amd.rotation_curve (C: tsp_gravity_direct).
+"""Gravity for arrays: the host side of topsy_amd.gravity_direct, topsy_amd.gravity_tree and topsy_amd.rotation_curve (C:
+tsp_gravity_direct, tsp_gravity_tree).
 
 The GPU forms the softened sums with G = 1; this module checks the arguments, places the probes of a rotation curve, and
 multiplies by G.  Everything but the two compute_* functions runs without a GPU."""
@@ -49,6 +50,31 @@ def check_G(G):
     if not np.isfinite(g) or g <= 0:
         raise ValueError(f"G must be a finite number > 0, not {G!r}")
     return g
+
+
+def check_theta(theta):
+    """The tree's opening angle: a finite number in [0, 1] (0 accepts no node: the direct sum in Morton order)."""
+    try:
+        t = float(theta)
+    except (TypeError, ValueError):
+        t = np.nan
+    if not np.isfinite(t) or t < 0 or t > 1:
+        raise ValueError(f"theta must be a finite number in [0, 1], not {theta!r}")
+    return t
+
+
+def check_method(method, name="method"):
+    if method not in ("direct", "tree"):
+        raise ValueError(f"{name} must be 'direct' or 'tree', not {method!r}")
+    return method
+
+
+def check_tree_masses(mass):
+    """The tree needs masses >= 0 (a centre of mass); NaN passes (that particle exerts nothing)."""
+    with np.errstate(invalid="ignore"):
+        negative = np.nonzero(np.asarray(mass) < 0)[0]
+    if len(negative):
+        raise ValueError(f"the tree needs masses >= 0: mass[{negative[0]}] = {mass[negative[0]]!r} ({len(negative)} negative in all)")
 
 
 def check_targets(targets):
@@ -123,18 +149,21 @@ class RotationCurve:
         return len(self.radii)
 
 
-def compute_gravity(ctx, pos32, mass, eps, targets32, want_pot=True, want_acc=True):
+def compute_gravity(ctx, pos32, mass, eps, targets32, want_pot=True, want_acc=True, method="direct", theta=0.5):
     x, y, z = (np.ascontiguousarray(pos32[:, k]) for k in range(3))
     t = None if targets32 is None else [np.ascontiguousarray(targets32[:, k]) for k in range(3)]
     with np.errstate(invalid="ignore"):
         valid = np.isfinite(pos32).all(axis=1) & np.isfinite(mass) & (True if np.ndim(eps) == 0 else np.isfinite(eps))
     if not valid.any():
         raise ValueError("no particle has finite coordinates, a finite mass and a finite softening length")
+    if method == "tree":
+        check_tree_masses(mass)
+        return ctx.gravity_tree(x, y, z, mass, eps, targets=t, theta=theta, want_pot=want_pot, want_acc=want_acc)
     return ctx.gravity_direct(x, y, z, mass, eps, targets=t, want_pot=want_pot, want_acc=want_acc)
 
 
-def compute_rotation_curve(ctx, pos, mass, eps, radii, center, frame, G):
+def compute_rotation_curve(ctx, pos, mass, eps, radii, center, frame, G, method="direct", theta=0.5):
     """rotation_curve() on a context: arguments already checked."""
     probes = rotation_probes(radii, frame).reshape(-1, 3).astype(np.float32)
-    pot, acc, _ = compute_gravity(ctx, centred_positions(pos, center), mass, eps, probes)
+    pot, acc, _ = compute_gravity(ctx, centred_positions(pos, center), mass, eps, probes, method=method, theta=theta)
     return RotationCurve(radii, probes, pot, acc, G)

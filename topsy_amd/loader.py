@@ -738,15 +738,21 @@ class ArrayDataLoader(AbstractDataLoader):
     particle from all the others, Plummer-softened with the source's length, G = 1 -- a direct sum on the GPU
     (tsp_gravity_direct) on first use, on the same context as 'rho', cached as float32.  It costs n^2 pairs; above
     config.GRAVITY_DIRECT_MAX_PAIRS the first use raises ValueError instead.  rotation_curve() is the midplane rotation curve
-    (topsy_amd.rotation_curve) from the same arrays.  Without eps nothing changes: names, order, errors."""
+    (topsy_amd.rotation_curve) from the same arrays.  Without eps nothing changes: names, order, errors.
+    gravity="tree" computes 'phi' by the Barnes-Hut tree (tsp_gravity_tree, opening angle gravity_theta) instead: O(n log n), not
+    subject to config.GRAVITY_DIRECT_MAX_PAIRS, masses >= 0; the default "direct" leaves every name, order and error as it was."""
 
     # reference PynbodyDataInMemory.get_rgb_masses (loader.py:115-121): (band, weight) per rgb channel
     RGB_BANDS = (("I", 0.5), ("V", 1.0), ("U", 1.0))
 
     def __init__(self, device=None, pos=None, smooth=None, mass=None, quantities=None, rgb=None,
                  units="kpc", periodicity_scale=None, with_cells=False, band_magnitudes=None, n_smooth=None,
-                 center="none", halos=None, vel=None, orient="none", orient_radius=None, orient_method=None, eps=None):
+                 center="none", halos=None, vel=None, orient="none", orient_radius=None, orient_method=None, eps=None,
+                 gravity="direct", gravity_theta=0.5):
         super().__init__(device)
+        from . import gravity as gravity_checks
+        self._gravity_method = gravity_checks.check_method(gravity, "gravity")
+        self._gravity_theta = gravity_checks.check_theta(gravity_theta)
         self._pos = np.asarray(pos, dtype=np.float32)
         self._eps = None                 # the gravitational softening: a float, or float32 (n,) in this loader's order
         self._phi = None                 # the computed potential ('phi' with eps=), in this loader's order
@@ -881,14 +887,20 @@ class ArrayDataLoader(AbstractDataLoader):
         if self._phi is None:
             from . import gravity
             pos, mass = self._gravity_arrays()
-            gravity.check_pair_count(len(pos), len(pos), "'phi'")
-            pot = self._with_context(lambda ctx: gravity.compute_gravity(ctx, pos, mass, self._eps, None, want_acc=False))[0]
+            method, theta = self._gravity_method, self._gravity_theta
+            if method == "direct":
+                gravity.check_pair_count(len(pos), len(pos), "'phi'")
+            else:
+                gravity.check_tree_masses(mass)
+            pot = self._with_context(lambda ctx: gravity.compute_gravity(ctx, pos, mass, self._eps, None, want_acc=False,
+                                                                         method=method, theta=theta))[0]
             self._phi = pot.astype(np.float32)
         return self._phi
 
-    def rotation_curve(self, radii, center=None, frame=None, eps=None, G=1.0):
+    def rotation_curve(self, radii, center=None, frame=None, eps=None, G=1.0, method="direct", theta=0.5):
         """The RotationCurve (topsy_amd.rotation_curve) of the particles about `center` (None: the initial centre) in `frame`,
-        found on the GPU (tsp_gravity_direct) from the host arrays; eps=None: the loader's own softening (eps=)."""
+        found on the GPU (tsp_gravity_direct, or tsp_gravity_tree with method="tree") from the host arrays; eps=None: the loader's
+        own softening (eps=)."""
         from . import gravity
         pos, mass = self._gravity_arrays()
         eps = self._eps if eps is None else gravity.check_eps(eps, len(pos))
@@ -896,7 +908,10 @@ class ArrayDataLoader(AbstractDataLoader):
             raise ValueError("no softening length: pass eps= here or to from_arrays / ArrayDataLoader")
         center = self.get_initial_center() if center is None else center
         radii, c, frame, G = gravity.check_radii(radii), gravity.check_center(center), gravity.check_frame(frame), gravity.check_G(G)
-        return self._with_context(lambda ctx: gravity.compute_rotation_curve(ctx, pos, mass, eps, radii, c, frame, G))
+        method, theta = gravity.check_method(method), gravity.check_theta(theta)
+        if method == "tree":
+            gravity.check_tree_masses(mass)
+        return self._with_context(lambda ctx: gravity.compute_rotation_curve(ctx, pos, mass, eps, radii, c, frame, G, method, theta))
 
     def set_density_context(self, context):
         """The context that computes 'rho' on first use (ParticleBuffers hands over its own; None: one made for the call)."""

@@ -347,15 +347,17 @@ class VisualizerBase(FrameInterface):
             frame = np.asarray(self.rotation_matrix, dtype=np.float64)
         return ld.profile(r_max, center=center, frame=frame, **kwargs)
 
-    def rotation_curve(self, radii, eps=None, G=1.0):
+    def rotation_curve(self, radii, eps=None, G=1.0, method="direct", theta=0.5):
         """The RotationCurve (topsy_amd.rotation_curve: v_circ and the midplane potential from direct sums of the softened forces
         at four probes per radius) of what the view shows: about -position_offset, what the view is centred on, in the frame of
         rotation_matrix -- after orient("faceon", r) the probes lie in the disc's plane and the curve is the disc's, the one to
         compare profile(geometry="disc").v_phi with.  eps=None: the softening given to from_arrays(eps=...).  The sums are found
-        on the GPU from the loader's host arrays; 4 len(radii) * n pairs."""
+        on the GPU from the loader's host arrays; 4 len(radii) * n pairs, or by the tree (gravity_tree, opening angle theta) with
+        method="tree"."""
         ld = self._array_loader("a rotation curve")
         return ld.rotation_curve(radii, center=-np.asarray(self.position_offset, dtype=np.float64),
-                                 frame=np.asarray(self.rotation_matrix, dtype=np.float64), eps=eps, G=G)
+                                 frame=np.asarray(self.rotation_matrix, dtype=np.float64), eps=eps, G=G,
+                                 method=method, theta=theta)
 
     def get_slice_image(self, quantity=None, resolution=None):
         """The SPH field on the view's centre plane (depth 0 in view coordinates), float32 (R, R) at R = resolution (None: the
