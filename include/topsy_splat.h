@@ -975,7 +975,7 @@ int tsp_get_stats(tsp_context *ctx, tsp_stats *out);
 /* Options by name.  "count_fragments" (0/1): fragment counting (adds atomics; off by default).  "use_quantity" (0/1): render
  * density-only without dropping the resident quantity.  "chunk_cull" (1/0), "reorder_interleave" (1/0, read by the next
  * tsp_reorder_spatial).  The remaining names are tuning and measurement aids of the pipeline ("p_small_milli", "huge_split",
- * "huge_variant", "h2_walk", "huge_band_mib", "mid_item_records", "mid_item_scale_milli", "stream_blocks_per_cu", "stream_batch_chunks",
+ * "huge_variant", "h2_walk", "h2_chord", "huge_band_mib", "mid_item_records", "mid_item_scale_milli", "stream_blocks_per_cu", "stream_batch_chunks",
  * "overlap_mid_huge", "slice_records", "debug_*"; csrc/tsp_api.hip). */
 int tsp_set_option(tsp_context *ctx, const char *name, int64_t value);
 

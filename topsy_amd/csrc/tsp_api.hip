@@ -1375,6 +1375,12 @@ int tsp_set_option(tsp_context *ctx, const char *name, int64_t value) {
         ctx->h2_walk = (int)value;
         return TSP_OK;
     }
+    if (!strcmp(name, "h2_chord")) {
+        // kernel H2's row clip: 1 = a hit's rows outside the chord of the footprint's disc are not walked (default), 0 = the square's rows (A/B and parity)
+        TSP_REQUIRE(value == 0 || value == 1, TSP_EINVAL, "%s out of range", name);
+        ctx->h2_chord = (int)value;
+        return TSP_OK;
+    }
     if (!strcmp(name, "reorder_interleave")) {   // read by the next tsp_reorder_spatial
         TSP_REQUIRE(value >= 0 && value <= 2, TSP_EINVAL, "%s out of range", name);
         ctx->reorder_interleave = (int)value;      // 0: Morton order inside the blocks, 1: 64 x 8 transposition, 2: by descending h

@@ -96,7 +96,8 @@ namespace tsp {
     H2A_ROW(S, t0, 0, p) H2A_ROW(S, t1, 1, p) H2A_ROW(S, t2, 2, p) H2A_ROW(S, t3, 3, p)                        \
     "s_branch .Lh2end_%=\n"
 // out of line, group K of state S: the tested rows, then the next group (N: its label, `end` after the last);  the skip of an
-// uncovered group (the covered rows are contiguous: none below -> the next group, none above -> done)
+// uncovered group (the covered rows are contiguous: none below -> the next group, none above -> done; the row clip keeps them so,
+// the chord of a strip's column interval being one interval of rows: see the row pass of splat_huge2_kernel)
 #define H2A_SLOW(S, K, N, p, t0, t1, t2, t3)                                                                   \
     ".Lh2s" #S "_" #K "_%=:\n\t"                                                                               \
     H2A_TROW(S, t0, 0, p) H2A_TROW(S, t1, 1, p) H2A_TROW(S, t2, 2, p) H2A_TROW(S, t3, 3, p)                    \
@@ -214,7 +215,11 @@ __global__ __launch_bounds__(H2T, OCC) void splat_huge2_kernel(TileArgs a) {
     float2 *rt = rt_all + wv * 64;
     const float2 *rt_quad = rt + (lane & 3);               // this lane's slot in every row group
     const int sx = tx0 + 64 * W * (wv & 1), sy = ty0 + HR * (wv >> 1);
-    const float sx0 = (float)sx, sx1 = (float)(sx + 64 * W), sy0 = (float)sy, sy1 = (float)(sy + HR);
+    // (the strip's edges as floats, pinned in scalar registers: converted on the vector ALU they were wave-uniform values in VGPRs, and
+    // three of them were spilled and re-read from scratch for every 64 records)
+    // (as asm: the compiler knows the value is uniform, folds the builtin away and keeps the converted value in a VGPR)
+    auto uniform_f = [](int v) -> float { float s; asm("v_readfirstlane_b32 %0, %1" : "=s"(s) : "v"((float)v)); return s; };
+    const float sx0 = uniform_f(sx), sx1 = uniform_f(sx + 64 * W), sy0 = uniform_f(sy), sy1 = uniform_f(sy + HR);
     float pxc[W];
 #pragma unroll
     for (int w = 0; w < W; ++w) pxc[w] = (sx + 64 * w + lane < R) ? (float)(sx + 64 * w + lane) + 0.5f : __builtin_inff();
@@ -288,7 +293,10 @@ __global__ __launch_bounds__(H2T, OCC) void splat_huge2_kernel(TileArgs a) {
         if (hits == 0ull) continue;
         since_fold += __popcll(hits);
         const float g_invP = 1.0f / g.z;
-        const float g_w1 = (MODE == TSP_MODE_RGB) ? gw1 : g.w * gw1;
+        // the row clip's limit for this record on this strip (tsp_pipeline.h chord_limit), once per batch: a pixel row at d from the
+        // centre in y with d d >= g_lim has its chord of the disc outside the strip's columns
+        const float g_lim = chord_limit(g.x, g.z, sx0, sx1, a.chord_k2);
+        const float g_w1 =(MODE == TSP_MODE_RGB) ? gw1 : g.w * gw1;
         // The rows of NH = 64 / HR hits are evaluated in ONE pass: lane j works out pixel row j % HR for hit j / HR (with HR = 32 the
         // upper half of the wave used to repeat the lower half's work); the hits' parameters reach their lanes through ds_bpermute
         // (the LDS crossbar, not the vector ALU) instead of a v_readlane each per hit.  Columns and the row walk follow hit by hit.
@@ -311,8 +319,16 @@ __global__ __launch_bounds__(H2T, OCC) void splat_huge2_kernel(TileArgs a) {
                 const float pcy_l = __int_as_float(__builtin_amdgcn_ds_bpermute(bp, __float_as_int(g.y)));
                 const float half_l = __int_as_float(__builtin_amdgcn_ds_bpermute(bp, __float_as_int(g_half)));
                 const float invP_l = __int_as_float(__builtin_amdgcn_ds_bpermute(bp, __float_as_int(g_invP)));
+                const float lim_l = __int_as_float(__builtin_amdgcn_ds_bpermute(bp, __float_as_int(g_lim)));
                 const float d = pyc_own - pcy_l;
-                const float cv = (__builtin_fabsf(d) < half_l) ? 1.0f : 0.0f;
+                // The row clip (option h2_chord): a row of the square whose chord of the inscribed disc misses this strip's 64 W columns
+                // is taken for uncovered -- every pixel of it would receive weight x (0 top + 0 bot), an exact zero: the records here
+                // have finite weights (huge_nonfinite_kernel draws the others itself and negates their widths), so 0 x weight is 0 and
+                // no float32 strip sum changes by a bit.  Its factors go to (0, 0) like an uncovered row's (cv).  The rows a disc leaves
+                // to a column interval are ONE interval of rows (|d| below a bound), so the covered rows stay contiguous: what the
+                // masks below, `first`, r_off and both walks assume.  A NaN limit clears nothing (the comparison is false).
+                const bool covered_row = __builtin_fabsf(d) < half_l && !row_outside_chord(d, lim_l);
+                const float cv = covered_row ? 1.0f : 0.0f;
                 // the canonical float32 texel coordinate (tsp_math.h: the oracle forms it with the same operations -- a value next to
                 // a zero texel is proportional to its fraction, so even one ulp of difference here shows at 1e-5 relative)
                 const float v = (d + half_l) * invP_l;
@@ -328,7 +344,8 @@ __global__ __launch_bounds__(H2T, OCC) void splat_huge2_kernel(TileArgs a) {
                 asm volatile("" ::: "memory");
                 // the row masks straight from vector compares (as __ballot(bool expression) each costs a v_cndmask + v_cmp round trip)
                 constexpr unsigned long long ROW0S = (HR == 64) ? 1ull : ((HR == 32) ? 0x0000000100000001ull : 0x0001000100010001ull);
-                cov64 = __builtin_amdgcn_fcmpf(__builtin_fabsf(d), half_l, 4 /* FCMP_OLT */);
+                cov64 = __builtin_amdgcn_fcmpf(__builtin_fabsf(d), half_l, 4 /* FCMP_OLT */) &
+                        ~__builtin_amdgcn_fcmpf(d * d, lim_l, 3 /* FCMP_OGE */);      // (= the lanes of covered_row)
                 chg64 = __builtin_amdgcn_uicmp((unsigned)r, (unsigned)rprev, 33 /* ICMP_NE */) & cov64 & ~ROW0S;
                 // texel rows advance by at most one per pixel row when P >= 64; rounding at P ~ 64 may still skip one
                 jmp64 = __builtin_amdgcn_uicmp((unsigned)r, (unsigned)(rprev + 1), 33 /* ICMP_NE */) & chg64;

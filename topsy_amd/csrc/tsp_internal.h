@@ -164,6 +164,7 @@ struct tsp_context {
     int64_t huge_band_budget = 6ll << 30;   // bytes the band bins of the huge records may take (n_bands x n_huge records); above it kernel H2 scans one list
     int huge_variant = 1;             // kernel H2's strip shape / occupancy: 1 = auto (density: 64x32 strips at 8 waves/SIMD from 7e5 records, 64x16 below; two channels 64x16 at 7; rgb at 5), 2 / 4-7 = A/B builds
     int h2_walk = 1;                  // kernel H2's row walk in the single-channel 8-waves/SIMD builds: 1 = hand-allocated asm (tsp_huge.hip), 0 = the C++ walk (A/B and parity)
+    int h2_chord = 1;                 // kernel H2 walks a hit's pixel rows: 1 = those whose chord of the inscribed disc reaches the strip's columns (tsp_pipeline.h chord_limit), 0 = every row of the square (A/B and parity)
     int huge_split = 0;              // workgroups per image tile of kernel H2 (0 = auto)
     int reorder_interleave = 2;     // tsp_reorder_spatial's arrangement inside every 512-particle block: 0 Morton order, 1 transposed 64 x 8, 2 by descending smoothing length (tsp_data.hip)
     int stream_blocks_per_cu = 0;    // kernel S: persistent workgroups per CU (0 = what the occupancy query reports)

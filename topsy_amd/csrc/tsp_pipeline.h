@@ -74,11 +74,33 @@ __device__ __forceinline__ void fmac_plain(float &acc, float x, float y) {     /
 // The test of a (record, strip) pair: the footprint square of g = (pcx, pcy, P, .) and the disc inscribed in it (disc_k2 > 0) reach the
 // strip [sx0, sx1] x [sy0, sy1]; P <= 0 marks an empty slot.  Kernels G and H2 make it per pair, the strip bins of kernel N once per
 // copy (tsp_mid.hip strip_hit): kernel N draws every record of a bin unasked, so there is one copy of the test.
+// The disc test -- here and in kernel H2's row clip below, which is its second entry: the nearest point of the strip (of a pixel row's
+// part of it) lies at (sdx, sdy) from the centre, at or beyond the radius sqrt(disc_k2) P = 0.5235 P (TileArgs::disc_k2; 0: no test).
+// Why the one constant serves a strip rectangle and a pixel centre alike: the bilinear texels a pixel reads with a non-zero weight lie
+// within one texel pitch (P / 64) of it per axis, so a pixel at >= (0.5 + sqrt(2) / 64) P = 0.5221 P from the centre takes them from
+// >= 0.5 P = 2 h away, where they are exactly 0 when lut_zero_outside_disc holds.  (The clamp at the low edge reads texel 0 with weight 1
+// and texel 1, farther off, with weight exactly 0; at the high edge it repeats texel 63.  tests/test_h2_chord_cpu.py checks this
+// against the kernel image.)  Every pixel of a rectangle is at least as far as its nearest point.  0.5235 leaves 2.7e-3 of the radius
+// for the float32 rounding of sdx, sdy and the products (~1e-7 each).
 __device__ __forceinline__ bool reaches_strip(const float4 g, float sx0, float sx1, float sy0, float sy1, float disc_k2) {
     const float half = 0.5f * g.z;
     const float sdx = fmaxf(fmaxf(sx0 - g.x, g.x - sx1), 0.0f), sdy = fmaxf(fmaxf(sy0 - g.y, g.y - sy1), 0.0f);
     return g.z > 0.0f && sdx < half && sdy < half && !(disc_k2 > 0.0f && sdx * sdx + sdy * sdy >= disc_k2 * g.z * g.z);
 }
+// The second entry, kernel H2's row clip: the same comparison, sdx * sdx + d * d >= disc_k2 * P * P, for the pixel row whose centre is
+// d from the footprint's centre in y (sdy = |d|: the row's part of the strip is a segment) -- the row's chord of the disc misses the
+// strip's columns, all its pixels read zero texels.  The kernel makes the test for 64 rows at once, so the part that does not depend on
+// the row is formed once per record and strip,
+//     chord_limit = disc_k2 P P - sdx sdx,     row outside  <=>  d d >= chord_limit,
+// which is that comparison with sdx sdx moved across (one more rounding of ~1e-7 P P against the margin of 1.5e-3 P P above).  Without
+// a disc (disc_k2 = 0) the limit is +inf: no finite d is outside.  A NaN limit (inf - inf at widths beyond 1e19 px) clears nothing.
+// (reaches_strip keeps its own text of sdx and of the comparison: called through shared helpers it compiles to other machine code in
+// kernels N and G, which this clip does not concern.)
+__device__ __forceinline__ float chord_limit(float pcx, float P, float sx0, float sx1, float disc_k2) {
+    const float sdx = fmaxf(fmaxf(sx0 - pcx, pcx - sx1), 0.0f);
+    return disc_k2 > 0.0f ? disc_k2 * P * P - sdx * sdx : __builtin_inff();
+}
+__device__ __forceinline__ bool row_outside_chord(float d, float limit) { return d * d >= limit; }
 // Margin of the binning passes around a footprint's extent c -+ half: one pixel plus two ulps of the coordinate, so that it still
 // covers the rounding of c -+ half at any magnitude (float rounding can only add a bin, never drop one)
 __device__ __forceinline__ float bin_margin(float c, float half) { return 1.0f + 2.4e-7f * (__builtin_fabsf(c) + half); }
@@ -115,6 +137,9 @@ struct TileArgs {
     // kernels N and G: wave i draws work item i = item_records consecutive records of strip item_tile[i]'s bin (that strip's items start
     // at item_base[strip]; item_base[n_tiles] = their number)
     int n_tiles; const int *item_tile; const int *item_base; int item_records;      // item_records: records per work item (a power of two)
+    // kernel H2's row clip (chord_limit): disc_k2 with option h2_chord on, else 0 (every row of the square is walked).  Last, so that
+    // the kernels that do not read it find every other argument where it was
+    float chord_k2;
 };
 
 // A run-time flag / mode as a compile-time constant: f receives std::true_type or std::false_type (a std::integral_constant of

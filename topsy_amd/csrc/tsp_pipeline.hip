@@ -936,6 +936,10 @@ static int run_pipeline(tsp_context *ctx, const Camera &cam, const int64_t *h_st
     // corner culling is exact for the value channels; the rgb counter channel (which also counts zero-valued
     // fragments) is not touched by kernel H2 at all: add_rect_counts() sums the footprint rectangles instead
     ta.disc_k2 = (ctx->lut_zero_outside_disc && !ctx->count_fragments) ? 0.5235f * 0.5235f : 0.0f;
+#ifdef TSP_H2_DEBUG      // analysis build: kernel H2 counts the pairs and rows the product frame walks, so the disc stays on while it counts
+    if (ctx->lut_zero_outside_disc) ta.disc_k2 = 0.5235f * 0.5235f;
+#endif
+    ta.chord_k2 = ctx->h2_chord ? ta.disc_k2 : 0.0f;      // kernel H2's row clip (option h2_chord): the same disc, per pixel row
     // Kernels G and H2 only depend on kernel S and add into the float64 image with atomics: option overlap_mid_huge runs them on
     // two streams (no gain measured: both are bound by the vector units).
     hipStream_t st_mid = ctx->overlap_mid_huge ? ctx->stream2 : st;
