@@ -98,6 +98,141 @@ def test_model_prunes():
     assert per_target.max() < n / 4 and (got["pairs_direct"] + got["pairs_node"]) * (n / len(rows)) < n * n / 4
 
 
+# ---- the model with the kernel's group decisions and stored records ---------------------------------------------------------------------
+def _same_sums(got, want, ref):
+    assert np.array_equal(np.isnan(got["pot"]), np.isnan(want["pot"])) and np.array_equal(np.isnan(got["acc"]), np.isnan(want["acc"]))
+    ok = ~np.isnan(want["pot"])
+    assert (np.abs(got["pot"][ok] - want["pot"][ok]) <= 1e-12 * ref["pot_scale"][ok]).all()
+    assert (np.abs(got["acc"][ok] - want["acc"][ok]) <= 1e-12 * ref["acc_scale"][ok]).all()
+    assert (got["pairs_direct"], got["pairs_node"]) == (want["pairs_direct"], want["pairs_node"])
+    assert np.array_equal(got["per_target_pairs"], want["per_target_pairs"])
+
+
+@pytest.mark.parametrize("self_targets", [True, False])
+def test_group_model_reproduces_the_single_target_model(self_targets):
+    """theta = 0 (any groups, stored or not), and one target per group with the unrounded records: today's tree_sum"""
+    src, mass, eps, tgt = scenes.scene(32 * 64 + 7, 129)
+    src[5, 0], mass[40], eps[900] = np.nan, np.inf, np.nan
+    mass[[3, 77]] = 0.0
+    tgt[17, 2] = np.inf
+    targets = None if self_targets else tgt
+    ref = gravity_ref.direct_sum(src, mass, eps, targets)
+    k = len(src) if self_targets else len(tgt)
+    for stored in (False, True):
+        tree = tree_gravity_ref.build_tree(src, mass, eps, stored=stored)
+        groups = tree_gravity_ref.sorted_groups(tree) if self_targets else tree_gravity_ref.consecutive_groups(k)
+        want = tree_gravity_ref.tree_sum(src, mass, eps, targets, theta=0.0)
+        got = tree_gravity_ref.tree_sum(src, mass, eps, targets, theta=0.0, tree=tree, groups=groups)
+        _same_sums(got, want, ref)
+        assert got["pairs_node"] == 0
+        # the scales of the pair terms are the direct sum's
+        ok = ~np.isnan(ref["pot"])
+        assert got["pot_scale"][ok] == pytest.approx(ref["pot_scale"][ok], rel=1e-12)
+        assert got["acc_scale"][ok] == pytest.approx(ref["acc_scale"][ok], rel=1e-12)
+    finite = np.nonzero(np.isfinite(src if self_targets else tgt).all(axis=1))[0]
+    for theta in (0.5, 1.0):
+        want = tree_gravity_ref.tree_sum(src, mass, eps, targets, theta=theta)
+        got = tree_gravity_ref.tree_sum(src, mass, eps, targets, theta=theta, groups=[[i] for i in range(k)])
+        assert want["pairs_node"] > 0
+        _same_sums(got, want, ref)
+        assert [len(g["targets"]) for g in got["groups"]] == [int(i in finite) for i in range(k)]
+
+
+def test_stored_records_are_the_kernels_roundings():
+    src, mass, eps, _ = scenes.scene(32 * 8 * 3 + 11, 1, seed=2)
+    plain = tree_gravity_ref.build_tree(src, mass, eps)
+    tree = tree_gravity_ref.build_tree(src, mass, eps, stored=True)
+    up = np.float32(1.0) + np.float32(2.0 ** -20)
+    for level, plain_level, raw, rec in zip(tree["levels"], plain["levels"], plain["walk"], tree["walk"]):
+        for name in ("M", "c", "Q", "lo", "hi", "rule", "b"):
+            assert np.array_equal(level[name], plain_level[name])                                    # parents: from unrounded sums
+        for name in ("c", "M", "e2", "Q"):
+            assert np.array_equal(rec[name], raw[name].astype(f32).astype(np.float64))
+        far = np.maximum(rec["c"] - level["lo"], level["hi"] - rec["c"])
+        radius = np.sqrt((far * far).sum(axis=1))                                                    # from the float32 c
+        assert np.array_equal(rec["b"], (radius.astype(f32) * up).astype(np.float64))
+        assert (rec["b"] >= radius).all() and (rec["b"] <= radius * (1 + 2.0 ** -19)).all()           # never below it
+        positive = raw["rule"] > 0
+        assert positive.any() and np.array_equal(rec["rule"][positive], (raw["rule"][positive].astype(f32) * up).astype(np.float64))
+        assert (rec["rule"][~positive] == 0).all()
+
+
+@pytest.mark.parametrize("size", list(scenes.CELL_SIZES))
+def test_cell_scene_is_sorted_by_its_coarse_cells(size):
+    g, n = scenes.CELL_SIZES[size]
+    for eps_name in scenes.CELL_EPS:
+        src, mass, eps, cells = scenes.term_scene(size, eps_name)
+        tree = scenes.term_tree(size, eps_name)
+        assert len(tree["levels"]) == int(size[0]) and len(src) == n
+        keys = scenes.cell_keys(cells)
+        assert len(np.unique(keys)) == n, "two particles share a cell"
+        assert np.array_equal(tree["order"], np.argsort(keys, kind="stable"))
+        frac = src.astype(np.float64) * g - cells
+        inner = np.ones(n, dtype=bool)
+        inner[tree["order"][[0, -1]]] = False
+        assert (frac[inner] >= 0.25 - 1e-5).all() and (frac[inner] <= 0.75 + 1e-5).all()
+        assert (src[tree["order"][0]] == 0).all() and (src[tree["order"][-1]] == 1).all()
+        assert mass.max() / mass.min() > 50 and (np.ndim(eps) == 0 or eps.max() / eps.min() > 500)
+        Q = tree["levels"][-1]["Q"][0]
+        assert (np.abs(Q) > 1e-3 * Q[:3].max()).all() and np.abs(np.diff(np.sort(np.abs(Q)))).min() > 1e-3 * Q[:3].max()
+
+
+TERM_CASES = [(size, eps_name, theta, self_targets) for size in scenes.CELL_SIZES for eps_name in scenes.CELL_EPS
+              for self_targets, thetas in ((False, scenes.TERM_THETAS), (True, scenes.SELF_THETAS)) for theta in thetas]
+
+
+@pytest.mark.parametrize("size, eps_name, theta, self_targets", TERM_CASES)
+def test_term_cases_meet_their_conditions(size, eps_name, theta, self_targets):
+    """what the GPU test requires of every case before it compares: at most a tenth of the groups within 1e-4 of a threshold, nodes
+    accepted on three levels (two where the 4-level scene's geometry allows no more: tree_gravity_scenes.min_levels)"""
+    model = scenes.term_model(size, eps_name, theta, self_targets)
+    amb, levels = scenes.check_case_conditions(model, (size, eps_name, theta, self_targets), scenes.min_levels(size, theta, self_targets))
+    print(f"\n{size}, {eps_name}, theta = {theta}, self = {self_targets}: {int(amb.sum())} of {len(amb)} groups ambiguous, nodes "
+          f"accepted on levels {levels.tolist()}: {model['accepted_per_level'].tolist()}")
+    if np.ndim(scenes.term_scene(size, eps_name)[2]):      # eps varies: the second rule decides somewhere
+        tree = scenes.term_tree(size, eps_name)
+        assert any((rec["rule"] > 0).any() for rec in tree["walk"])
+
+
+def test_model_at_huge_softening_is_the_closed_form():
+    """eps = 1e5: every term is m / eps, so pot_i = -(M - m_i) / eps however the tree partitions the sources -- the model (theta =
+    1, the kernel's groups) meets that and the direct sum within 0.01 * 2^-24"""
+    g, n = scenes.CELL_SIZES["4 levels"]
+    src, mass, _, _ = scenes.cell_scene(g, n, 41, 0.01)
+    eps = scenes.PARTITION_EPS
+    tree = tree_gravity_ref.build_tree(src, mass, eps)
+    got = tree_gravity_ref.tree_sum(src, mass, eps, None, theta=1.0, tree=tree, groups=tree_gravity_ref.sorted_groups(tree))
+    assert got["pairs_node"] > 0 and got["pairs_direct"] + got["pairs_node"] < n * n / 2
+    m = mass.astype(np.float64)
+    tol = 0.01 * 2.0 ** -24
+    assert np.abs(got["pot"] * eps / -(m.sum() - m) - 1.0).max() <= tol
+    ref = gravity_ref.direct_sum(src, mass, eps)
+    assert (np.abs(got["pot"] - ref["pot"]) <= tol * ref["pot_scale"]).all()
+    assert (np.abs(got["acc"] - ref["acc"]) <= tol * ref["acc_scale"]).all()
+
+
+@pytest.mark.parametrize("size", list(scenes.CELL_SIZES))
+@pytest.mark.parametrize("mutation", ["Qxy and Qxz swapped", "no parallel-axis term"])
+def test_term_bound_notices_a_wrong_moment(size, mutation):
+    """a fault put into the MODEL's tree moves its sums by more than 100 times the bound the GPU test asserts, in a group that is
+    not ambiguous: the assertion of test_gpu_gravity_tree_terms.py has teeth"""
+    from topsy_amd import _native
+    eps_name, theta = "eps over three decades", 0.8
+    src, mass, eps, _ = scenes.term_scene(size, eps_name)
+    model = scenes.term_model(size, eps_name, theta, False)
+    tgt, groups = scenes.term_targets()
+    if mutation == "no parallel-axis term":
+        wrong = tree_gravity_ref.build_tree(src, mass, eps, stored=True, parallel_axis=False)
+    else:
+        wrong = dict(scenes.term_tree(size, eps_name))
+        wrong["walk"] = [dict(rec, Q=rec["Q"][:, [0, 1, 2, 4, 3, 5]]) for rec in wrong["walk"]]
+    got = tree_gravity_ref.tree_sum(src, mass, eps, tgt, theta=theta, tree=wrong, groups=groups)
+    assert (got["pairs_direct"], got["pairs_node"]) == (model["pairs_direct"], model["pairs_node"])      # the same decisions
+    ratios = scenes.group_ratios(got["pot"], got["acc"], model)[~scenes.ambiguous(model)]
+    print(f"\n{size}, {mutation}: the model moves by up to {ratios.max():.0f} x 2^-24 scale (bound {_native.GRAVITY_TREE_ERROR_K})")
+    assert ratios.max() > 100 * _native.GRAVITY_TREE_ERROR_K
+
+
 # ---- the host layer -------------------------------------------------------------------------------------------------------------------
 def test_argument_checks():
     import topsy_amd
