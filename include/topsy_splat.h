@@ -114,7 +114,9 @@ const char *tsp_last_error(void);
  * 123: new entry point tsp_gravity_direct and the struct tsp_gravity_info (softened direct-sum gravity: the potential and the
  * accelerations at targets, for 'phi' and a disc's rotation curve); nothing else changed.
  * 124: new entry point tsp_gravity_tree and the struct tsp_gravity_tree_info (the same sums by a Barnes-Hut tree over the
- * Morton order, O(n log n)); nothing else changed. */
+ * Morton order, O(n log n)); nothing else changed.
+ * 125: new entry points tsp_group_potential and tsp_halo_properties and the structs tsp_group_potential_info / tsp_halo_info (the
+ * haloes of a catalogue in one call: self-potential, masses, centres, radii, spin, bound mass); nothing else changed. */
 int tsp_version(void);
 int tsp_stats_size(void);
 
@@ -670,6 +672,93 @@ int tsp_gravity_tree(tsp_context *ctx,
         int64_t n_tgt, const float *tx, const float *ty, const float *tz /* all three NULL: the targets are the sources */,
         float theta, double *pot_out /* n_tgt, or NULL */, double *acc_out /* n_tgt * 3, or NULL */,
         tsp_gravity_tree_info *info_out /* optional */);
+
+/* The haloes of a catalogue in one call: the self-potential of every halo (tsp_group_potential) and per-halo reductions
+ * (tsp_halo_properties).  Host arrays in, caller's order; both use ctx's device and stream only, in every context state: resident
+ * particles, image, accumulator and tsp_stats unchanged.  G = 1.  Shared by both:
+ *   - Labels.  group[i] in 1 .. n_groups: particle i is a member of that halo; group[i] <= 0: of none (what tsp_fof_groups writes).
+ *     A label above n_groups returns TSP_EINVAL.  A member is valid iff the fields named below are finite; an invalid member
+ *     takes no part in its halo.
+ *   - Order.  (label, index) pairs are sorted by label with a stable radix sort, everything that is no valid member under the
+ *     key ~0: a halo's members are then contiguous and in the caller's index order.
+ *   - Anchor and offsets.  The anchor a of a halo is the position of its valid member with the smallest index.  Per axis a member
+ *     has the offset d = (double)x - (double)a and, with period > 0, d -= period * rint(d / period): float64, nothing fused, so
+ *     that a numpy model forms the same bits.  That is the nearest image as long as every member lies within period / 2 of the
+ *     anchor per axis, which is not checked: max_extent of the info struct is the largest |d| on any axis of any halo.
+ *   - Determinism.  No floating-point atomics; the results are a function of the inputs alone (not of the device's CU count,
+ *     not of timing): the same call returns the same bits.
+ * 1 <= n < 2^31, 1 <= n_groups < 2^31; period 0 (open) or finite and > 0; no NULL among the required arrays; anything else
+ * returns TSP_EINVAL and writes nothing.  Device memory is allocated for the call only, through the two allocation sites of the
+ * gather sums (the radix sort's temporary storage included); a failed allocation returns TSP_ENOMEM and writes nothing.
+ *
+ * tsp_group_potential: phi_out[i] = - sum over the valid members j != i of i's halo of m_j / sqrt(|e_i - e_j|^2 + eps_j^2).
+ *   - e = (float)d: the anchor-relative offset rounded once to float32, so that a halo far from the origin, or one that straddles
+ *     a face of a periodic box, keeps its digits.
+ *   - A valid member has finite x, y, z, mass and softening length (eps[i], or eps_all for every particle when eps is NULL).
+ *     Non-members and invalid members get NaN.
+ *   - Pair arithmetic, pairs that count (the own pair and r2 < 2^-126 contribute nothing) and the error bound are those of
+ *     tsp_gravity_direct: |got - want| <= TSP_GRAVITY_ERROR_K * 2^-24 * sum |term| against the float64 evaluation on the float32
+ *     e, m, eps.  The float32 runs of 16 are runs of 16 consecutive positions of the sorted order, aligned to that order (not to
+ *     the halo's first member); a workgroup owns TSP_HALO_TARGET_BLOCK consecutive sorted targets and sums tiles of
+ *     TSP_HALO_SOURCE_TILE sorted sources; a source range of more than 2 tiles is cut into up to 16 parts of at least 2 tiles, added in order.
+ *   - max_members > 0: a halo with more valid members is skipped -- its members get NaN -- and counted in n_skipped_groups /
+ *     n_skipped_members (the caller sends it to tsp_gravity_tree).  0: no limit.  Negative: TSP_EINVAL.
+ *   - info_out (optional): n_members (valid members, those of skipped haloes included), n_groups_nonempty, pairs (ordered pairs
+ *     i != j that count, skipped haloes left out), pair_slots (pairs the kernel evaluated, masked ones included), the two skip
+ *     counts, max_extent.
+ *
+ * tsp_halo_properties: everything in float64.  A valid member has finite x, y, z, a finite mass > 0 and, when velocities are
+ * given (all three or none), finite velocities.  Per halo, with M = sum m:
+ *   - pass 1: count; M; com_off = sum m d / M; com = a + com_off, wrapped into [0, period) when periodic; v_com = sum m v / M.
+ *   - pass 2, with e = d - com_off and w = v - v_com (w = 0 without velocities): S = sum m e_a e_b (xx, xy, xz, yy, yz, zz);
+ *     L = sum m e x w; e_kin = 0.5 sum m |w|^2; sigma2 = 2 e_kin / (3 M); r_max = max |e|.  With phi (n float64, the caller's
+ *     potential, G included): e_pot = 0.5 sum m phi; i_pot the member with the smallest phi (ties: the smaller index), pot_pos its
+ *     position; n_bound, m_bound over the members with 0.5 |w|^2 + phi < 0.  A valid member with a non-finite phi gives its halo
+ *     e_pot = NaN, i_pot = -1, n_bound = -1, m_bound = NaN, pot_pos = NaN.
+ *   - pass 3: the members ordered by the key (float)|e|, ties by index; cum_k the running sum of m in that order; r_half = |e| of
+ *     the first member with cum_k >= M / 2 (i_half its index); v2_max = the largest cum_k / |e_k| over the ranks k >= 10 (1-based)
+ *     with |e_k| > 0, r_vmax that member's |e| (i_vmax its index; ties: the smaller rank).  Fewer than 10 members: v2_max, r_vmax
+ *     and i_vmax are NaN.
+ *   - A label without valid members: count = 0, mass = 0, every other column NaN, n_bound = -1, i_pot = -1.  Without velocities
+ *     v_com, L, e_kin, sigma2 are NaN; without phi e_pot, m_bound, pot_pos are NaN, n_bound = -1 and i_pot = -1.
+ *   - Sums.  Each sum is formed over slices of 256 consecutive sorted members (one partial per halo and slice, added in order),
+ *     and a halo's partials are added in order in 64 chunks of consecutive partials, then the chunks in order: the association is
+ *     a function of where the halo lies in the sorted order.  Against the exact sum each is within (n_h + 16) * 2^-53 * sum |term|.
+ * Outputs: count_out, n_bound_out, i_pot_out int64[n_groups]; props_out[n_groups * TSP_HALO_NPROPS], row g = label g + 1, columns
+ * TSP_HALO_*; info_out (optional): n_members, max_extent. */
+#define TSP_HALO_SOURCE_TILE 512                    /* sorted sources per tile of the halo pair kernel */
+#define TSP_HALO_TARGET_BLOCK 1024                  /* sorted targets of a workgroup */
+#define TSP_HALO_MASS 0
+#define TSP_HALO_COM 1                              /* 3 columns */
+#define TSP_HALO_VCOM 4                             /* 3 */
+#define TSP_HALO_S 7                                /* 6: xx, xy, xz, yy, yz, zz */
+#define TSP_HALO_L 13                               /* 3 */
+#define TSP_HALO_EKIN 16
+#define TSP_HALO_SIGMA2 17
+#define TSP_HALO_RMAX 18
+#define TSP_HALO_RHALF 19
+#define TSP_HALO_V2MAX 20
+#define TSP_HALO_RVMAX 21
+#define TSP_HALO_EPOT 22
+#define TSP_HALO_MBOUND 23
+#define TSP_HALO_POTPOS 24                          /* 3 */
+#define TSP_HALO_IHALF 27                           /* the caller's index of the r_half member, as a double */
+#define TSP_HALO_IVMAX 28                           /* ... of the r_vmax member */
+#define TSP_HALO_NPROPS 29
+typedef struct { int64_t n_members, n_groups_nonempty, pairs, pair_slots, n_skipped_groups, n_skipped_members; double max_extent; }
+        tsp_group_potential_info;
+typedef struct { int64_t n_members; double max_extent; } tsp_halo_info;
+int tsp_group_potential(tsp_context *ctx,
+        int64_t n, const float *x, const float *y, const float *z, const float *mass,
+        const float *eps /* n softening lengths, or NULL: eps_all for every particle */, float eps_all,
+        const int32_t *group, int64_t n_groups, double period, int64_t max_members /* 0: no limit */,
+        double *phi_out /* n */, tsp_group_potential_info *info_out /* optional */);
+int tsp_halo_properties(tsp_context *ctx,
+        int64_t n, const float *x, const float *y, const float *z, const float *mass,
+        const float *vx, const float *vy, const float *vz /* all three or none (NULL) */, const double *phi /* n, or NULL */,
+        const int32_t *group, int64_t n_groups, double period,
+        int64_t *count_out, int64_t *n_bound_out, int64_t *i_pot_out /* n_groups each */,
+        double *props_out /* n_groups * TSP_HALO_NPROPS */, tsp_halo_info *info_out /* optional */);
 
 /* Kinematic maps: the mass-weighted mean line-of-sight velocity and its dispersion per pixel, from resident velocities (what
  * pynbody's image(qty="vz", av_z=True) draws after analysis.angmom.sideon; the reference has no such mode).  The rgb kernels

@@ -49,6 +49,9 @@ def from_arrays(pos, smooth, mass, quantities=None, rgb=None, with_cells=False, 
     periodicity_scale if one is given), a dict of its keywords (linking_length, b, min_members), or your own integer (n,) labels
     (halo N is label N; <= 0: no halo).  With it center="halo-N" opens the view on halo N (1 = the largest) and
     vis.centre_on_halo(N) jumps there; vis.data_loader.get_halos() returns the catalogue, set_halos() restores it.
+    vis.halo_properties() is the HaloProperties of the catalogue (halo_properties, with this call's vel, eps and
+    periodicity_scale; computed on the GPU on first use and cached), and vis.centre_on_halo(N, at="com" | "pot") centres on a
+    halo's centre of mass or potential minimum instead of its shrinking-sphere centre.
 
     vel, orient: the angle the view opens at -- orient="faceon" or "sideon" turns the view (no particle moves) so that the disc
     inside the sphere of radius orient_radius (required: a length in the units of pos) around the initial centre, whatever center=
@@ -429,6 +432,51 @@ def friends_of_friends(pos, linking_length=None, b=0.2, min_members=20, periodic
         ctx.close()
 
 
+def group_potential(pos, mass, eps, group, periodicity_scale=None, G=1.0, tree_above=None, theta=0.5, device_id=0):
+    """The self-potential of every halo of a catalogue on GPU `device_id`, in one call (C: tsp_group_potential): for particle i
+    of halo N, -G sum over the other members j of N of mass_j / sqrt(|r_i - r_j|^2 + eps_j^2).  group: a FofCatalogue
+    (friends_of_friends) or an integer (n,) label array, N >= 1 = halo N, 0 or less = no halo.  The sums are formed on float32
+    offsets from each halo's first member (nearest image in a periodic box of side periodicity_scale), with the pair arithmetic
+    and the error bound of gravity_direct.  A halo with more than tree_above members (None: config.HALO_TREE_MEMBERS) is summed
+    by gravity_tree with the opening angle theta instead.  Returns float64 (n,): NaN for a particle in no halo and for one with
+    a non-finite coordinate, mass or eps."""
+    from . import _native, gravity, halos
+    pos = halos.check_positions(pos)
+    mass, eps = halos.check_mass(mass, len(pos)), gravity.check_eps(eps, len(pos))
+    labels, n_groups = halos.check_group(group, len(pos))
+    period, G, theta = halos.check_period(periodicity_scale), gravity.check_G(G), gravity.check_theta(theta)
+    tree_above = halos.check_tree_above(tree_above)
+    ctx = _native.Context(1, 2, device_id)
+    try:
+        return G * halos.compute_group_potential(ctx, pos, mass, eps, labels, n_groups, period, tree_above, theta)[0]
+    finally:
+        ctx.close()
+
+
+def halo_properties(pos, mass, group, vel=None, eps=None, phi=None, periodicity_scale=None, G=1.0, tree_above=None, theta=0.5,
+                    device_id=0):
+    """The properties of every halo of a catalogue on GPU `device_id`, in one call (C: tsp_halo_properties): member count, mass,
+    centre of mass, and about it the second moments, r_max, the half-mass radius and v_max = max sqrt(G M(<r) / r) (from the 10th
+    member outward); with vel (n, 3) the mean velocity, dispersion, angular momentum and kinetic energy; with a potential the
+    potential energy, the position of the potential minimum and the bound members and mass (0.5 |v - v_com|^2 + phi < 0).  The
+    potential is phi (n,), taken as already containing G, or, with eps, group_potential(pos, mass, eps, group, ...).  group: a
+    FofCatalogue or integer labels.  Everything is summed in float64 on offsets from each halo's first member (nearest image in
+    a periodic box of side periodicity_scale).  Returns a HaloProperties (topsy_amd/halos.py)."""
+    from . import _native, gravity, halos
+    pos = halos.check_positions(pos)
+    n = len(pos)
+    mass, vel, phi = halos.check_mass(mass, n), halos.check_vel(vel, n), halos.check_phi(phi, n)
+    eps = None if eps is None else gravity.check_eps(eps, n)
+    labels, n_groups = halos.check_group(group, n)
+    period, G, theta = halos.check_period(periodicity_scale), gravity.check_G(G), gravity.check_theta(theta)
+    tree_above = halos.check_tree_above(tree_above)
+    ctx = _native.Context(1, 2, device_id)
+    try:
+        return halos.compute_halo_properties(ctx, pos, mass, labels, n_groups, vel, eps, phi, period, G, tree_above, theta)
+    finally:
+        ctx.close()
+
+
 def SurfaceView(visualizer, **colormap_params):
     """Surface rendering of `visualizer`'s scene (the reference's render_mode "surface"): the front-most sphere of every
     particle above a density cut, smoothed and lit.  render(), get_sph_image() ((R, R, 2) filtered (q, depth)),
@@ -469,6 +517,9 @@ def __getattr__(name):
     if name == "FofCatalogue":
         from .loader import FofCatalogue
         return FofCatalogue
+    if name == "HaloProperties":
+        from .halos import HaloProperties
+        return HaloProperties
     if name == "Profile":
         from .loader import Profile
         return Profile

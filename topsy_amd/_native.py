@@ -20,7 +20,8 @@ ABI_VERSION = 112            # the oldest tsp_version() whose structs this bindi
                              # (113: tsp_shrink_sphere_center, 114: tsp_fof_groups, 115: tsp_sphere_moments,
                              # 116: tsp_radial_profile, 117: the kinematic maps, 119: tsp_moment_sort,
                              # 120: tsp_sph_velocity_gradient, 122: tsp_sph_sample_lattice, 123: tsp_gravity_direct,
-                             # 124: tsp_gravity_tree) are required by name in load_library()
+                             # 124: tsp_gravity_tree, 125: tsp_group_potential, tsp_halo_properties) are required by
+                             # name in load_library()
 PRESENT_SCALAR, PRESENT_BIVARIATE, PRESENT_RGB, PRESENT_RGB_HDR, PRESENT_MOMENT_MEAN, PRESENT_MOMENT_SIGMA = 0, 1, 2, 3, 4, 5
 LAYER_QUAD, LAYER_LINES = 0, 1
 
@@ -119,6 +120,26 @@ class GravityTreeInfo(ctypes.Structure):
 GRAVITY_TREE_LEAF = 32
 GRAVITY_TREE_FANOUT = 8
 GRAVITY_TREE_ERROR_K = 64
+
+
+class GroupPotentialInfo(ctypes.Structure):
+    """struct tsp_group_potential_info."""
+    _fields_ = [(name, ctypes.c_int64) for name in ("n_members", "n_groups_nonempty", "pairs", "pair_slots", "n_skipped_groups",
+                                                    "n_skipped_members")] + [("max_extent", ctypes.c_double)]
+
+
+class HaloInfo(ctypes.Structure):
+    """struct tsp_halo_info."""
+    _fields_ = [("n_members", ctypes.c_int64), ("max_extent", ctypes.c_double)]
+
+
+# tsp_group_potential / tsp_halo_properties (the header's TSP_HALO_* constants): the pair kernel's tile and target block, and the
+# first column of every property in a row of props_out
+HALO_SOURCE_TILE = 512
+HALO_TARGET_BLOCK = 1024
+HALO_COLUMNS = {"mass": 0, "com": 1, "v_com": 4, "S": 7, "L": 13, "e_kin": 16, "sigma2": 17, "r_max": 18, "r_half": 19, "v2_max": 20,
+                "r_vmax": 21, "e_pot": 22, "m_bound": 23, "pot_pos": 24, "i_half": 27, "i_vmax": 28}
+HALO_NPROPS = 29
 LATTICE_MAX_FIELDS = 4       # fields per tsp_sph_sample_lattice call
 PROFILE_SUMS = 11            # doubles per bin of tsp_radial_profile's sums_out: mass, ms, mc (3), mc2 (3), mj (3)
 
@@ -211,6 +232,12 @@ SIGNATURES = {
     "tsp_gravity_tree": (ctypes.c_int, [_ctx, ctypes.c_int64, _fp, _fp, _fp, _fp, _fp, ctypes.c_float, ctypes.c_int64, _fp, _fp, _fp,
                                         ctypes.c_float, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double),
                                         ctypes.POINTER(GravityTreeInfo)]),
+    "tsp_group_potential": (ctypes.c_int, [_ctx, ctypes.c_int64, _fp, _fp, _fp, _fp, _fp, ctypes.c_float, ctypes.POINTER(ctypes.c_int32),
+                                           ctypes.c_int64, ctypes.c_double, ctypes.c_int64, ctypes.POINTER(ctypes.c_double),
+                                           ctypes.POINTER(GroupPotentialInfo)]),
+    "tsp_halo_properties": (ctypes.c_int, [_ctx, ctypes.c_int64, _fp, _fp, _fp, _fp, _fp, _fp, _fp, ctypes.POINTER(ctypes.c_double),
+                                           ctypes.POINTER(ctypes.c_int32), ctypes.c_int64, ctypes.c_double, _i64p, _i64p, _i64p,
+                                           ctypes.POINTER(ctypes.c_double), ctypes.POINTER(HaloInfo)]),
     "tsp_set_sphere_mips": (ctypes.c_int, [_ctx, _fp, ctypes.c_int, ctypes.c_int]),
     "tsp_density_order_stats": (ctypes.c_int, [_ctx, _i64p, ctypes.c_int, _fp]),
     "tsp_render_surface": (ctypes.c_int, [_ctx, _fp, ctypes.c_float, ctypes.c_float, _i64p, _i64p, ctypes.c_int, ctypes.c_int,
@@ -720,6 +747,59 @@ class Context:
         else:
             _check(self._lib.tsp_gravity_direct(*sources, *outputs))
         return pot, acc, {name: int(getattr(info, name)) for name, _ in info._fields_}
+
+    def group_potential(self, x, y, z, mass, eps, group, n_groups, period=0.0, max_members=0):
+        """The self-potential of every halo (tsp_group_potential, G = 1): for particle i with the label group[i] in 1..n_groups,
+        the softened sum over the other valid members of its halo, on anchor-relative float32 offsets (nearest image in a box
+        of side `period`; None or 0: open).  eps: one softening length or an array.  max_members > 0: haloes with more valid
+        members are skipped.  Returns (float64 (n,), NaN for non-members, invalid members and skipped haloes; dict of
+        struct tsp_group_potential_info).  Uses this context's device only; what is resident stays."""
+        n = len(x)
+        x, y, z, mass = _f32(x, n, "x"), _f32(y, n, "y"), _f32(z, n, "z"), _f32(mass, n, "mass")
+        if np.ndim(eps) == 0:
+            eps_array, eps_all = None, float(np.float32(eps))
+        else:
+            eps_array, eps_all = _f32(eps, n, "eps"), 0.0
+        group = np.ascontiguousarray(group, dtype=np.int32)
+        if group.size != n:
+            raise ValueError(f"group has {group.size} elements, expected {n}")
+        phi = np.empty(n, dtype=np.float64)
+        info = GroupPotentialInfo()
+        _check(self._lib.tsp_group_potential(self._h, n, _ptr(x), _ptr(y), _ptr(z), _ptr(mass), _ptr(eps_array), eps_all,
+                                             group.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), int(n_groups), float(period or 0.0),
+                                             int(max_members), phi.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), ctypes.byref(info)))
+        return phi, {name: (float if kind is ctypes.c_double else int)(getattr(info, name)) for name, kind in info._fields_}
+
+    def halo_properties(self, x, y, z, mass, group, n_groups, vel=None, phi=None, period=0.0):
+        """The per-halo reductions of tsp_halo_properties over the labels group[i] in 1..n_groups; vel = (vx, vy, vz) or None,
+        phi = float64 (n,) potential or None.  Returns a dict: count, n_bound, i_pot int64 (n_groups,), props float64 (n_groups,
+        HALO_NPROPS) (columns: HALO_COLUMNS), n_members, max_extent.  Uses this context's device only; what is resident stays."""
+        n = len(x)
+        x, y, z, mass = _f32(x, n, "x"), _f32(y, n, "y"), _f32(z, n, "z"), _f32(mass, n, "mass")
+        if vel is not None:
+            if len(vel) != 3:
+                raise ValueError("vel must be the three arrays (vx, vy, vz)")
+            vel = [_f32(v, n, name) for v, name in zip(vel, ("vx", "vy", "vz"))]
+        vx, vy, vz = vel if vel is not None else (None, None, None)
+        if phi is not None:
+            phi = np.ascontiguousarray(phi, dtype=np.float64)
+            if phi.size != n:
+                raise ValueError(f"phi has {phi.size} elements, expected {n}")
+        group = np.ascontiguousarray(group, dtype=np.int32)
+        if group.size != n:
+            raise ValueError(f"group has {group.size} elements, expected {n}")
+        n_groups = int(n_groups)
+        count, n_bound, i_pot = (np.empty(max(n_groups, 0), dtype=np.int64) for _ in range(3))
+        props = np.empty((max(n_groups, 0), HALO_NPROPS), dtype=np.float64)
+        info = HaloInfo()
+        dp = ctypes.POINTER(ctypes.c_double)
+        _check(self._lib.tsp_halo_properties(self._h, n, _ptr(x), _ptr(y), _ptr(z), _ptr(mass), _ptr(vx), _ptr(vy), _ptr(vz),
+                                             None if phi is None else phi.ctypes.data_as(dp),
+                                             group.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), n_groups, float(period or 0.0),
+                                             count.ctypes.data_as(_i64p), n_bound.ctypes.data_as(_i64p), i_pot.ctypes.data_as(_i64p),
+                                             props.ctypes.data_as(dp), ctypes.byref(info)))
+        return {"count": count, "n_bound": n_bound, "i_pot": i_pot, "props": props, "n_members": int(info.n_members),
+                "max_extent": float(info.max_extent)}
 
     # ---- surface (include/topsy_splat.h "Surface rendering") ---------------------------------
     def set_sphere_mips(self, mips, n0=64, n_levels=4):

@@ -47,3 +47,6 @@ MULTI_GPU_SHARD_ASSIGNMENT = "auto"
 # the potential-only sum on one MI355X, 3.96e12 pairs a second: n = 1.5e7 particles.
 GRAVITY_DIRECT_MAX_PAIRS = 2.4e14
 MULTI_GPU_INTERLEAVE_BLOCK = 4096
+# A halo with more valid members than this gets its self-potential (group_potential, halo_properties(eps=...)) from the tree
+# instead of the direct sum confined to the halo.  DESIGN.md section 4 "Halo properties" has the measured crossover.
+HALO_TREE_MEMBERS = 2 ** 17

@@ -234,7 +234,7 @@ using namespace tsp;
 extern "C" {
 
 const char *tsp_last_error(void) { return g_err; }
-int tsp_version(void) { return 124; }     // 124: tsp_gravity_tree and the struct tsp_gravity_tree_info (Barnes-Hut tree gravity over the Morton order); 123: tsp_gravity_direct and the struct tsp_gravity_info (softened direct-sum gravity: potential, accelerations); 122: tsp_sph_sample_lattice and the struct tsp_lattice (SPH sums at the points of a lattice); 121: a failed upload is atomic (attributes: nothing changed; particles / synthetic: no particles left; groups: every member emptied); 120: tsp_sph_velocity_gradient; 119: tsp_moment_sort, TSP_PRESENT_MOMENT_MEAN / _SIGMA (the kinematic maps as the base of tsp_present / tsp_present_yuv420); 118: tsp_render_undo, tsp_group_render all-or-nothing across the members; 117: kinematic maps (tsp_upload_velocities, tsp_set_line_of_sight, TSP_MODE_KINEMATIC, tsp_velocity_moments, tsp_colormap_moment); 116: tsp_radial_profile; 115: tsp_sphere_moments; 114: tsp_fof_groups; 113: tsp_shrink_sphere_center; 112: tsp_present_surface, tsp_present_surface_yuv420; 111: tsp_content_neg_inf; 110: tsp_sph_sum; 109: tsp_present_yuv420; 108: tsp_present; 107: surface rendering; 106: tsp_smoothing_lengths; 101: tsp_stats gained ms_mega, n_mega (16 bytes); 102: the per-kernel fragment counts (32 bytes); 103: n_chunk_culled (8 bytes); 104: matrix-core / kernel-I options removed; 105: kernel M's options removed (kernel G draws the mid footprints)
+int tsp_version(void) { return 125; }     // 124: tsp_gravity_tree and the struct tsp_gravity_tree_info (Barnes-Hut tree gravity over the Morton order); 123: tsp_gravity_direct and the struct tsp_gravity_info (softened direct-sum gravity: potential, accelerations); 122: tsp_sph_sample_lattice and the struct tsp_lattice (SPH sums at the points of a lattice); 121: a failed upload is atomic (attributes: nothing changed; particles / synthetic: no particles left; groups: every member emptied); 120: tsp_sph_velocity_gradient; 119: tsp_moment_sort, TSP_PRESENT_MOMENT_MEAN / _SIGMA (the kinematic maps as the base of tsp_present / tsp_present_yuv420); 118: tsp_render_undo, tsp_group_render all-or-nothing across the members; 117: kinematic maps (tsp_upload_velocities, tsp_set_line_of_sight, TSP_MODE_KINEMATIC, tsp_velocity_moments, tsp_colormap_moment); 116: tsp_radial_profile; 115: tsp_sphere_moments; 114: tsp_fof_groups; 113: tsp_shrink_sphere_center; 112: tsp_present_surface, tsp_present_surface_yuv420; 111: tsp_content_neg_inf; 110: tsp_sph_sum; 109: tsp_present_yuv420; 108: tsp_present; 107: surface rendering; 106: tsp_smoothing_lengths; 101: tsp_stats gained ms_mega, n_mega (16 bytes); 102: the per-kernel fragment counts (32 bytes); 103: n_chunk_culled (8 bytes); 104: matrix-core / kernel-I options removed; 105: kernel M's options removed (kernel G draws the mid footprints)
 int tsp_stats_size(void) { return (int)sizeof(tsp_stats); }
 
 int tsp_device_count(void) {
@@ -1142,6 +1142,42 @@ int tsp_gravity_tree(tsp_context *ctx, int64_t n_src, const float *sx, const flo
                     (double)mass[j]);
     TSP_HIP(hipSetDevice(ctx->device));
     return gravity_tree(ctx, n_src, sx, sy, sz, mass, eps, eps_all, n_tgt, tx, ty, tz, theta, pot_out, acc_out, info_out);
+}
+
+int tsp_group_potential(tsp_context *ctx, int64_t n, const float *x, const float *y, const float *z, const float *mass,
+                        const float *eps, float eps_all, const int32_t *group, int64_t n_groups, double period, int64_t max_members,
+                        double *phi_out, tsp_group_potential_info *info_out) {
+    TSP_REQUIRE(ctx && x && y && z && mass && group && phi_out, TSP_EINVAL, "NULL argument");
+    TSP_REQUIRE(n >= 1 && n < (1ll << 31), TSP_EINVAL, "n = %lld outside [1, 2^31)", (long long)n);
+    TSP_REQUIRE(n_groups >= 1 && n_groups < (1ll << 31), TSP_EINVAL, "n_groups = %lld outside [1, 2^31)", (long long)n_groups);
+    if (!eps) TSP_REQUIRE(std::isfinite(eps_all) && eps_all >= 0.0f, TSP_EINVAL, "eps_all must be finite and >= 0, not %g", (double)eps_all);
+    TSP_REQUIRE(period == 0.0 || (std::isfinite(period) && period > 0.0), TSP_EINVAL,
+                "period must be 0 (open box) or finite and > 0, not %g", period);
+    TSP_REQUIRE(max_members >= 0, TSP_EINVAL, "max_members = %lld is negative (0: no limit)", (long long)max_members);
+    for (int64_t i = 0; i < n; ++i)
+        TSP_REQUIRE(group[i] <= n_groups, TSP_EINVAL, "group[%lld] = %d above n_groups = %lld", (long long)i, (int)group[i],
+                    (long long)n_groups);
+    TSP_HIP(hipSetDevice(ctx->device));
+    return group_potential(ctx, n, x, y, z, mass, eps, eps_all, group, n_groups, period == 0.0 ? 0.0 : period, max_members, phi_out,
+                           info_out);
+}
+
+int tsp_halo_properties(tsp_context *ctx, int64_t n, const float *x, const float *y, const float *z, const float *mass,
+                        const float *vx, const float *vy, const float *vz, const double *phi, const int32_t *group, int64_t n_groups,
+                        double period, int64_t *count_out, int64_t *n_bound_out, int64_t *i_pot_out, double *props_out,
+                        tsp_halo_info *info_out) {
+    TSP_REQUIRE(ctx && x && y && z && mass && group && count_out && n_bound_out && i_pot_out && props_out, TSP_EINVAL, "NULL argument");
+    TSP_REQUIRE((vx && vy && vz) || (!vx && !vy && !vz), TSP_EINVAL, "vx, vy and vz must be given together or not at all");
+    TSP_REQUIRE(n >= 1 && n < (1ll << 31), TSP_EINVAL, "n = %lld outside [1, 2^31)", (long long)n);
+    TSP_REQUIRE(n_groups >= 1 && n_groups < (1ll << 31), TSP_EINVAL, "n_groups = %lld outside [1, 2^31)", (long long)n_groups);
+    TSP_REQUIRE(period == 0.0 || (std::isfinite(period) && period > 0.0), TSP_EINVAL,
+                "period must be 0 (open box) or finite and > 0, not %g", period);
+    for (int64_t i = 0; i < n; ++i)
+        TSP_REQUIRE(group[i] <= n_groups, TSP_EINVAL, "group[%lld] = %d above n_groups = %lld", (long long)i, (int)group[i],
+                    (long long)n_groups);
+    TSP_HIP(hipSetDevice(ctx->device));
+    return halo_properties(ctx, n, x, y, z, mass, vx, vy, vz, phi, group, n_groups, period == 0.0 ? 0.0 : period, count_out, n_bound_out,
+                           i_pot_out, props_out, info_out);
 }
 
 int tsp_present(tsp_context *ctx, int width, int height, const tsp_present_base *base, const tsp_present_layer *layers,

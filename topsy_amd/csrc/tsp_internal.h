@@ -232,7 +232,7 @@ int scratch_alloc(tsp_context *ctx, const char *site, DeviceScratch &buf, size_t
         if (rc_ != TSP_OK) return rc_;                                               \
     } while (0)
 
-// The two scratch buffers that every gather call (tsp_smooth.hip) and the direct gravity sum (tsp_gravity.hip) take, in this
+// The two scratch buffers that every gather call (tsp_smooth.hip), the gravity sums and the halo calls (tsp_halo.hip) take, in this
 // order: the one place that owns their sites (tsp_api.hip).  Each caller partitions them by offsets of its own.
 int gather_scratch(tsp_context *ctx, DeviceScratch &dh, size_t h_bytes, DeviceScratch &da, size_t a_bytes);
 
@@ -333,6 +333,15 @@ int gravity_direct(tsp_context *ctx, int64_t n_src, const float *sx, const float
 int gravity_tree(tsp_context *ctx, int64_t n_src, const float *sx, const float *sy, const float *sz, const float *mass,
                  const float *eps, float eps_all, int64_t n_tgt, const float *tx, const float *ty, const float *tz, float theta,
                  double *pot_out, double *acc_out, tsp_gravity_tree_info *info_out);
+// tsp_halo.hip: the self-potential of every halo of a catalogue by a direct sum confined to the halo (tsp_group_potential) and
+// the per-halo reductions (tsp_halo_properties) over the members sorted by label; per-call DeviceScratch only, through the sites
+// of gather_scratch(); no context state
+int group_potential(tsp_context *ctx, int64_t n, const float *x, const float *y, const float *z, const float *mass, const float *eps,
+                    float eps_all, const int32_t *group, int64_t n_groups, double period, int64_t max_members, double *phi_out,
+                    tsp_group_potential_info *info_out);
+int halo_properties(tsp_context *ctx, int64_t n, const float *x, const float *y, const float *z, const float *mass, const float *vx,
+                    const float *vy, const float *vz, const double *phi, const int32_t *group, int64_t n_groups, double period,
+                    int64_t *count_out, int64_t *n_bound_out, int64_t *i_pot_out, double *props_out, tsp_halo_info *info_out);
 // tsp_surface.hip: the occlusion pass + resolve (keys in image64, (q, depth) in image), the rho order statistics and the
 // filter + shading; per-call memory is DeviceScratch
 int render_surface(tsp_context *ctx, const Camera &cam, float cut, const int64_t *h_starts, const int64_t *h_lens,

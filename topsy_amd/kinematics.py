@@ -386,9 +386,9 @@ class VelocityFrames(FrameInterface):
         """The visualizer's orient: the camera is the visualizer's."""
         return self._vis.orient(orient, radius, center=center, method=method)
 
-    def centre_on_halo(self, n):
-        """The visualizer's centre_on_halo: the camera is the visualizer's."""
-        return self._vis.centre_on_halo(n)
+    def centre_on_halo(self, n, at="shrink"):
+        """The visualizer's centre_on_halo: the camera is the visualizer's.  (The default goes through the call as it was.)"""
+        return self._vis.centre_on_halo(n) if at == "shrink" else self._vis.centre_on_halo(n, at=at)
 
     def profile(self, r_max=None, **kwargs):
         """The visualizer's profile: the camera is the visualizer's."""

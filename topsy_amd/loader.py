@@ -778,6 +778,7 @@ class ArrayDataLoader(AbstractDataLoader):
         self._halos_option = check_halos_option(halos, len(self._pos), periodicity_scale)
         self._halos = None               # the catalogue once known
         self._halo_centers = {}          # N -> centre of halo N (float64 (3,))
+        self._halo_properties = None     # the HaloProperties of the catalogue once computed
         self._center_option = check_center_option(center, self._halos_option)
         self._center = None              # the initial centre once known (float64 (3,))
         self.needs_smoothing = smooth is None
@@ -1025,6 +1026,23 @@ class ArrayDataLoader(AbstractDataLoader):
             self._halos_option = labels
         self._halos = FofCatalogue(labels)
         self._halo_centers = {}
+        self._halo_properties = None
+
+    def get_halo_properties(self):
+        """The HaloProperties (topsy_amd.halo_properties) of the catalogue of halos=, with this loader's vel, eps and
+        periodicity_scale: computed on the GPU on first use, on the same context as 'rho', and cached; set_halos drops them."""
+        if getattr(self, "_halo_properties", None) is None:
+            from . import halos
+            catalogue = self.get_halos()
+            pos = halos.check_positions(self._pos)
+            mass = halos.check_mass(self._mass, len(pos))
+            labels, n_groups = halos.check_group(catalogue, len(pos))
+            vel = halos.check_vel(self._vel, len(pos))
+            period = halos.check_period(self._period or None)
+            tree_above = halos.check_tree_above(None)
+            self._halo_properties = self._with_context(lambda ctx: halos.compute_halo_properties(
+                ctx, pos, mass, labels, n_groups, vel, self._eps, None, period, 1.0, tree_above, self._gravity_theta))
+        return self._halo_properties
 
     def get_halo_center(self, n):
         """The shrinking-sphere centre (float64 (3,)) of the members of halo n, found on the GPU and cached."""

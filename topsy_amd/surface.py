@@ -139,9 +139,9 @@ class SurfaceView(FrameInterface):
         """The visualizer's scale_to_virial: the camera is the visualizer's."""
         return self._vis.scale_to_virial(rho_threshold, r_max, factor)
 
-    def centre_on_halo(self, n):
-        """The visualizer's centre_on_halo: the camera is the visualizer's."""
-        return self._vis.centre_on_halo(n)
+    def centre_on_halo(self, n, at="shrink"):
+        """The visualizer's centre_on_halo: the camera is the visualizer's.  (The default goes through the call as it was.)"""
+        return self._vis.centre_on_halo(n) if at == "shrink" else self._vis.centre_on_halo(n, at=at)
 
     @property
     def quantity_name(self):

@@ -303,14 +303,37 @@ class VisualizerBase(FrameInterface):
         self.position_offset = np.asarray(self.position_offset, dtype=np.float64) - np.asarray(self.rotation_matrix).T @ view
         return self.position_offset
 
-    def centre_on_halo(self, n):
+    def halo_properties(self):
+        """The HaloProperties of the data loader's halo catalogue (get_halo_properties: every halo's mass, centres, radii, spin
+        and, with eps=, energies and bound mass, found on the GPU in one call and cached)."""
+        if not hasattr(self.data_loader, "get_halo_properties"):
+            raise ValueError(f"{type(self.data_loader).__name__} has no halo catalogue")
+        return self.data_loader.get_halo_properties()
+
+    def centre_on_halo(self, n, at="shrink"):
         """Move position_offset to minus the centre of halo n (1 = the largest) of the data loader's halo catalogue
         (halos= of from_arrays / ArrayDataLoader: friends-of-friends groups found on the GPU, or the caller's labels): the
-        shrinking-sphere centre of the halo's members.  The array-snapshot counterpart of centre_on_pixel.  Returns the new
-        offset."""
+        shrinking-sphere centre of the halo's members (at="shrink"), or, from halo_properties(), its centre of mass (at="com")
+        or the position of its potential minimum (at="pot": needs eps=).  The array-snapshot counterpart of centre_on_pixel.
+        Returns the new offset."""
+        if at not in ("shrink", "com", "pot"):
+            raise ValueError(f"at must be 'shrink', 'com' or 'pot', not {at!r}")
         if not hasattr(self.data_loader, "get_halo_center"):
             raise ValueError(f"{type(self.data_loader).__name__} has no halo catalogue")
-        self.position_offset = -np.asarray(self.data_loader.get_halo_center(n), dtype=np.float64)
+        if at == "shrink":
+            centre = self.data_loader.get_halo_center(n)
+        else:
+            if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or n < 1:
+                raise ValueError(f"halo numbers are integers >= 1, not {n!r}")
+            props = self.halo_properties()
+            if n > len(props):
+                raise ValueError(f"halo {n} does not exist: the catalogue has {len(props)} halo(es)")
+            if at == "pot" and props.pot_pos is None:
+                raise ValueError("at='pot' needs a potential: pass eps= to from_arrays / ArrayDataLoader")
+            centre = (props.com if at == "com" else props.pot_pos)[n - 1]
+            if not np.isfinite(centre).all():
+                raise ValueError(f"halo {n} has no {'centre of mass' if at == 'com' else 'potential minimum'} (no valid member)")
+        self.position_offset = -np.asarray(centre, dtype=np.float64)
         return self.position_offset
 
     def orient(self, orient, radius, center=None, method=None):
