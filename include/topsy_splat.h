@@ -116,7 +116,9 @@ const char *tsp_last_error(void);
  * 124: new entry point tsp_gravity_tree and the struct tsp_gravity_tree_info (the same sums by a Barnes-Hut tree over the
  * Morton order, O(n log n)); nothing else changed.
  * 125: new entry points tsp_group_potential and tsp_halo_properties and the structs tsp_group_potential_info / tsp_halo_info (the
- * haloes of a catalogue in one call: self-potential, masses, centres, radii, spin, bound mass); nothing else changed. */
+ * haloes of a catalogue in one call: self-potential, masses, centres, radii, spin, bound mass); nothing else changed.
+ * 126: new entry points tsp_spectral_cube and tsp_spectral_cube_layout (position-position-velocity cubes of the resident
+ * particles, "Spectral cubes" below) and the option "cube_slice_particles"; no struct changed, nothing else changed. */
 int tsp_version(void);
 int tsp_stats_size(void);
 
@@ -815,6 +817,56 @@ int tsp_velocity_moments(tsp_context *ctx, float *maps_out /* R * R * 4 */);
 int tsp_colormap_moment(tsp_context *ctx, int which /* 1 mean, 2 sigma */, const float *lut_rgba, int n_lut, float vmin, float vmax,
                         int log_scale, uint8_t *out_rgba8);
 int tsp_moment_sort(tsp_context *ctx, int which /* 1 mean, 2 sigma */, int absolute, int64_t *n_finite);
+
+/* Spectral cubes: the whole line-of-sight velocity distribution per pixel, a position-position-velocity cube (channel maps, the
+ * integrated line profile, position-velocity diagrams), where the kinematic maps above keep two numbers of it.  One call draws
+ * every resident particle (no index ranges) at the camera M, scale_factor of tsp_render:
+ *     cube_out[c][j][i] = sum over particles of (double)k * (double)w0 * g_c          float32 [n_channels][R][R], host
+ *   - Geometry: the canonical rule of tsp_render -- projection, the draw test (0 <= cz <= 1; P, pcx, pcy finite; P > 0), coverage,
+ *     mip level, nearest or bilinear sampling -- gives the float32 kernel value k of every covered pixel; w0 = m / (h * h) in float32.
+ *   - Velocity: u, the float32 u of the kinematic weights above (same operations, same order, none fused), along the axis and about
+ *     the v_ref of tsp_set_line_of_sight.
+ *   - Channels: n_channels of them, with the edges e_k = v_min + k * dv formed in float64 for k = 0 .. n_channels (dv > 0).
+ *   - Line width, per particle, in float64: s = sqrt(sigma_v^2 + sigma_p^2).  sigma_v >= 0 is the call's scalar (an instrumental or
+ *     turbulent floor); sigma_p comes from `sigma`, n float32 in the caller's order (permuted by the library after
+ *     tsp_reorder_spatial, as tsp_upload_quantity's array), or is 0 for every particle when sigma is NULL.
+ *   - Channel response g_c: the Gaussian of width s about u INTEGRATED over the channel (not sampled at its centre: mass is
+ *     conserved), in float64 without cancellation in the tails.  With a = (e_c - u) / s and b = (e_{c+1} - u) / s:
+ *         a >= 0:     g_c = (erfc(a / sqrt 2) - erfc(b / sqrt 2)) / 2
+ *         b <= 0:     g_c = (erfc(-b / sqrt 2) - erfc(-a / sqrt 2)) / 2
+ *         otherwise:  g_c = (erf(b / sqrt 2) - erf(a / sqrt 2)) / 2
+ *     s == 0: g_c = 1 for the one channel with e_c <= u < e_{c+1} (a u on an edge falls in the upper channel), 0 elsewhere; a u
+ *     outside the band contributes nothing.  Channels that lie wholly more than 5 s from u are skipped: at most erfc(5 / sqrt 2) =
+ *     5.8e-7 of a particle's mass.
+ *   - Dead particles: m, u or sigma_p not finite, or sigma_p < 0: the particle contributes nothing.
+ *   - Order: every cell is summed in float64 in ascending resident particle index, and rounded to float32 once per slice of
+ *     particles (the float32 cube takes the slices' sums one after the other).  No floating-point atomics: two calls with the same
+ *     arguments on the same context give the same bits.
+ *   - Slices: the particles go through in slices of consecutive resident indices.  A slice holds
+ *     min(2^27 / n_bins, 2^22, n) particles, n_bins = ceil(R / 16)^2 * ceil(n_channels / 32) -- a function of (n, R, n_channels)
+ *     alone -- so that its (image tile, channel block) lists never exceed 2^27 entries whatever the data: 2 GiB of lists and
+ *     192 MiB of records at most, next to the device copy of the cube.  Option "cube_slice_particles" > 0 lowers the slice further
+ *     (a test aid: the many-slice path at small n); 0 restores the default.
+ *   - The call is a read-only per-call entry point like the gather analyses: the image, the accumulator, tsp_stats and the
+ *     context's state are untouched.  It is allowed wherever tsp_velocity_moments' inputs exist: particles with mass, velocities, a
+ *     line of sight and the kernel mips (TSP_ESTATE otherwise).  Device memory is per call, through the two allocations of
+ *     tsp_sph_sum (TSP_ENOMEM: nothing written).
+ *   - TSP_EINVAL: M or cube_out NULL; v_min, dv or sigma_v not finite; dv <= 0; sigma_v < 0; n_channels outside [1, 4096];
+ *     n_channels * R * R > 2^31.  A refused call leaves cube_out as it was.
+ * tsp_spectral_cube_layout: the host arithmetic of the call without a device or a context -- for n particles, a resolution, a channel
+ * count, the option's value (0: default) and has_sigma, out[TSP_CUBE_LAYOUT_VALUES] receives: tiles per image side, channel
+ * blocks, bins, the bits of a bin index, particles per slice, slices, list entries per slice; then the byte offsets inside the
+ * first allocation of sigma, the geometry records, the line records and its size; then inside the second of the cube, the pair
+ * counts, the pair offsets, the keys, the sorted keys, the indices, the sorted indices, the bins' first entries, the bins' end
+ * entries, the temporary storage of the scan and the sort (counted as 0 bytes here) and its size.  TSP_EINVAL as above, and for n
+ * outside [0, 2^31) or a negative option. */
+#define TSP_CUBE_TILE 16                            /* pixels per side of an image tile */
+#define TSP_CUBE_CHANNEL_BLOCK 32                   /* channels per block */
+#define TSP_CUBE_LAYOUT_VALUES 22
+int tsp_spectral_cube(tsp_context *ctx, const float *M, float scale_factor, double v_min, double dv, int n_channels,
+                      float sigma_v, const float *sigma /* n, caller's order, or NULL */, float *cube_out /* n_channels * R * R */);
+int tsp_spectral_cube_layout(int64_t n, int resolution, int n_channels, int64_t slice_option, int has_sigma,
+                             int64_t *out /* TSP_CUBE_LAYOUT_VALUES */);
 
 /* Surface rendering: DepthSPHWithOcclusion + ColorAsSurfaceMap (reference src/topsy/sph.py:448-656, shaders/sph.wgsl:94-122,
  * 149-158, shaders/smooth.wgsl, shaders/surface.wgsl, colormap/surface.py).  Float32 throughout, operations in the order written.

@@ -508,9 +508,25 @@ def velocity_maps(pos, smooth, mass, vel, rotation=None, center=(0, 0, 0), scale
                                     v_ref=v_ref, device_id=device_id)
 
 
+def spectral_cube(pos, smooth, mass, vel, v_range=None, n_channels=64, sigma_v=0.0, sigma=None, rotation=None, center=(0, 0, 0),
+                  scale=config.DEFAULT_SCALE, resolution=config.DEFAULT_RESOLUTION, v_ref=None, device_id=0):
+    """The position-position-velocity cube of arrays, without a visualizer, on GPU `device_id` (C: tsp_spectral_cube): a
+    topsy_amd.SpectralCube, data (n_channels, R, R) float32 over n_channels equal velocity channels of v_range (None: wide enough
+    for every particle) at velocity_maps' camera, with moment(), spectrum() and pv().  A particle's line is a Gaussian of width
+    sqrt(sigma_v^2 + sigma[i]^2) integrated over each channel.  VelocityView.get_cube() is the same at a visualizer's camera."""
+    from . import spectral
+    return spectral.spectral_cube(pos, smooth, mass, vel, v_range=v_range, n_channels=n_channels, sigma_v=sigma_v, sigma=sigma,
+                                  rotation=rotation, center=center, scale=scale, resolution=resolution, v_ref=v_ref,
+                                  device_id=device_id)
+
+
 def __getattr__(name):
     """topsy_amd.VisualizationRecorder (movie recording and export, topsy_amd/recorder), topsy_amd.FofCatalogue and
-    topsy_amd.Profile (topsy_amd/loader.py), topsy_amd.RotationCurve (topsy_amd/gravity.py), imported on first use."""
+    topsy_amd.Profile (topsy_amd/loader.py), topsy_amd.RotationCurve (topsy_amd/gravity.py), topsy_amd.SpectralCube
+    (topsy_amd/spectral.py), imported on first use."""
+    if name == "SpectralCube":
+        from .spectral import SpectralCube
+        return SpectralCube
     if name == "RotationCurve":
         from .gravity import RotationCurve
         return RotationCurve

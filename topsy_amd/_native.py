@@ -141,7 +141,12 @@ HALO_COLUMNS = {"mass": 0, "com": 1, "v_com": 4, "S": 7, "L": 13, "e_kin": 16, "
                 "r_vmax": 21, "e_pot": 22, "m_bound": 23, "pot_pos": 24, "i_half": 27, "i_vmax": 28}
 HALO_NPROPS = 29
 LATTICE_MAX_FIELDS = 4       # fields per tsp_sph_sample_lattice call
-PROFILE_SUMS = 11            # doubles per bin of tsp_radial_profile's sums_out: mass, ms, mc (3), mc2 (3), mj (3)
+CUBE_MAX_CHANNELS = 4096     # tsp_spectral_cube: n_channels at most
+CUBE_MAX_CELLS = 1 << 31     # ... and n_channels * R * R
+CUBE_LAYOUT_NAMES = ("tiles", "blocks", "bins", "key_bits", "slice_particles", "slices", "list_capacity",
+                     "h_sigma", "h_geom", "h_line", "h_bytes", "a_cube", "a_count", "a_offset", "a_keys", "a_keys_sorted", "a_index",
+                     "a_index_sorted", "a_bin_first", "a_bin_end", "a_tmp", "a_bytes")      # tsp_spectral_cube_layout's values
+PROFILE_SUMS = 11           # doubles per bin of tsp_radial_profile's sums_out: mass, ms, mc (3), mc2 (3), mj (3)
 
 
 class BackendUnavailable(RuntimeError):
@@ -184,6 +189,9 @@ SIGNATURES = {
     "tsp_upload_velocities": (ctypes.c_int, [_ctx, _fp, _fp, _fp]),
     "tsp_set_line_of_sight": (ctypes.c_int, [_ctx, _fp, _fp]),
     "tsp_velocity_moments": (ctypes.c_int, [_ctx, _fp]),
+    "tsp_spectral_cube": (ctypes.c_int, [_ctx, _fp, ctypes.c_float, ctypes.c_double, ctypes.c_double, ctypes.c_int, ctypes.c_float,
+                                         _fp, _fp]),
+    "tsp_spectral_cube_layout": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int64, ctypes.c_int, _i64p]),
     "tsp_colormap_moment": (ctypes.c_int, [_ctx, ctypes.c_int, _fp, ctypes.c_int, ctypes.c_float, ctypes.c_float, ctypes.c_int, _u8p]),
     "tsp_upload_band_magnitudes": (ctypes.c_int, [_ctx, ctypes.c_int, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]),
     "tsp_generate_synthetic": (ctypes.c_int, [_ctx, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_uint64,
@@ -360,6 +368,15 @@ def device_count():
     return load_library().tsp_device_count()
 
 
+def spectral_cube_layout(n, resolution, n_channels, slice_option=0, has_sigma=False):
+    """The host arithmetic of tsp_spectral_cube as a dict (CUBE_LAYOUT_NAMES): tiles, channel blocks, bins, particles per slice,
+    slices, list capacity and the byte offsets of its two device buffers (tsp_spectral_cube_layout; needs no GPU)."""
+    out = np.zeros(len(CUBE_LAYOUT_NAMES), dtype=np.int64)
+    _check(load_library().tsp_spectral_cube_layout(int(n), int(resolution), int(n_channels), int(slice_option), int(bool(has_sigma)),
+                                                   out.ctypes.data_as(_i64p)))
+    return dict(zip(CUBE_LAYOUT_NAMES, out.tolist()))
+
+
 def _ranges(starts, lens):
     """(starts pointer, lens pointer, count, the arrays the pointers lend from) of a render call's ranges; None = no ranges."""
     if starts is None:
@@ -446,6 +463,20 @@ class Context:
         mass-weighted mean line-of-sight velocity, its dispersion (NaN where S is not > 0) and the fragment count."""
         out = np.empty((self.resolution, self.resolution, 4), dtype=np.float32)
         _check(self._lib.tsp_velocity_moments(self._h, _ptr(out)))
+        return out
+
+    def spectral_cube(self, matrix, scale_factor, v_min, dv, n_channels, sigma_v=0.0, sigma=None):
+        """(n_channels, R, R) float32: the position-position-velocity cube of every resident particle at the camera (matrix,
+        scale_factor) along the line of sight set last (tsp_spectral_cube): channel c spans v_min + c * dv .. v_min + (c + 1) * dv;
+        a particle's line is a Gaussian of width sqrt(sigma_v^2 + sigma[i]^2) integrated over each channel (sigma: per particle,
+        the caller's order, or None)."""
+        M = _f32(np.asarray(matrix, dtype=np.float32).reshape(16), 16, "matrix")
+        s = None if sigma is None else _f32(sigma, self.num_particles, "sigma")
+        shape = (int(n_channels), self.resolution, self.resolution)
+        allowed = 0 < shape[0] <= CUBE_MAX_CHANNELS and shape[0] * shape[1] * shape[2] <= CUBE_MAX_CELLS
+        out = np.empty(shape if allowed else (1,), dtype=np.float32)       # (the library refuses the others: TSP_EINVAL)
+        _check(self._lib.tsp_spectral_cube(self._h, _ptr(M), float(scale_factor), float(v_min), float(dv), int(n_channels),
+                                           float(np.float32(sigma_v)), _ptr(s), _ptr(out)))
         return out
 
     def colormap_moment(self, which, lut_rgba, vmin, vmax, log=False):

@@ -10,6 +10,7 @@
 #include <cmath>
 #include <vector>
 
+#include "tsp_cube_layout.h"
 #include "tsp_internal.h"
 #include "tsp_morton.h"
 
@@ -234,7 +235,7 @@ using namespace tsp;
 extern "C" {
 
 const char *tsp_last_error(void) { return g_err; }
-int tsp_version(void) { return 125; }     // 124: tsp_gravity_tree and the struct tsp_gravity_tree_info (Barnes-Hut tree gravity over the Morton order); 123: tsp_gravity_direct and the struct tsp_gravity_info (softened direct-sum gravity: potential, accelerations); 122: tsp_sph_sample_lattice and the struct tsp_lattice (SPH sums at the points of a lattice); 121: a failed upload is atomic (attributes: nothing changed; particles / synthetic: no particles left; groups: every member emptied); 120: tsp_sph_velocity_gradient; 119: tsp_moment_sort, TSP_PRESENT_MOMENT_MEAN / _SIGMA (the kinematic maps as the base of tsp_present / tsp_present_yuv420); 118: tsp_render_undo, tsp_group_render all-or-nothing across the members; 117: kinematic maps (tsp_upload_velocities, tsp_set_line_of_sight, TSP_MODE_KINEMATIC, tsp_velocity_moments, tsp_colormap_moment); 116: tsp_radial_profile; 115: tsp_sphere_moments; 114: tsp_fof_groups; 113: tsp_shrink_sphere_center; 112: tsp_present_surface, tsp_present_surface_yuv420; 111: tsp_content_neg_inf; 110: tsp_sph_sum; 109: tsp_present_yuv420; 108: tsp_present; 107: surface rendering; 106: tsp_smoothing_lengths; 101: tsp_stats gained ms_mega, n_mega (16 bytes); 102: the per-kernel fragment counts (32 bytes); 103: n_chunk_culled (8 bytes); 104: matrix-core / kernel-I options removed; 105: kernel M's options removed (kernel G draws the mid footprints)
+int tsp_version(void) { return 126; }     // 126: tsp_spectral_cube and tsp_spectral_cube_layout (position-position-velocity cubes of the resident particles), option "cube_slice_particles"; 125: tsp_group_potential and tsp_halo_properties (halo properties); 124: tsp_gravity_tree and the struct tsp_gravity_tree_info (Barnes-Hut tree gravity over the Morton order); 123: tsp_gravity_direct and the struct tsp_gravity_info (softened direct-sum gravity: potential, accelerations); 122: tsp_sph_sample_lattice and the struct tsp_lattice (SPH sums at the points of a lattice); 121: a failed upload is atomic (attributes: nothing changed; particles / synthetic: no particles left; groups: every member emptied); 120: tsp_sph_velocity_gradient; 119: tsp_moment_sort, TSP_PRESENT_MOMENT_MEAN / _SIGMA (the kinematic maps as the base of tsp_present / tsp_present_yuv420); 118: tsp_render_undo, tsp_group_render all-or-nothing across the members; 117: kinematic maps (tsp_upload_velocities, tsp_set_line_of_sight, TSP_MODE_KINEMATIC, tsp_velocity_moments, tsp_colormap_moment); 116: tsp_radial_profile; 115: tsp_sphere_moments; 114: tsp_fof_groups; 113: tsp_shrink_sphere_center; 112: tsp_present_surface, tsp_present_surface_yuv420; 111: tsp_content_neg_inf; 110: tsp_sph_sum; 109: tsp_present_yuv420; 108: tsp_present; 107: surface rendering; 106: tsp_smoothing_lengths; 101: tsp_stats gained ms_mega, n_mega (16 bytes); 102: the per-kernel fragment counts (32 bytes); 103: n_chunk_culled (8 bytes); 104: matrix-core / kernel-I options removed; 105: kernel M's options removed (kernel G draws the mid footprints)
 int tsp_stats_size(void) { return (int)sizeof(tsp_stats); }
 
 int tsp_device_count(void) {
@@ -1180,6 +1181,49 @@ int tsp_halo_properties(tsp_context *ctx, int64_t n, const float *x, const float
                            i_pot_out, props_out, info_out);
 }
 
+static int check_cube_shape(int resolution, int n_channels) {
+    TSP_REQUIRE(resolution >= 1, TSP_EINVAL, "resolution = %d must be at least 1", resolution);
+    TSP_REQUIRE(n_channels >= 1 && n_channels <= cube::MAX_CHANNELS, TSP_EINVAL, "n_channels = %d outside [1, %d]", n_channels,
+                cube::MAX_CHANNELS);
+    TSP_REQUIRE((int64_t)n_channels * resolution * resolution <= cube::MAX_CELLS, TSP_EINVAL,
+                "n_channels * R * R = %lld above 2^31", (long long)n_channels * resolution * resolution);
+    return TSP_OK;
+}
+
+int tsp_spectral_cube(tsp_context *ctx, const float *M, float scale_factor, double v_min, double dv, int n_channels, float sigma_v,
+                      const float *sigma, float *cube_out) {
+    TSP_REQUIRE(ctx && M && cube_out, TSP_EINVAL, "NULL argument");
+    TSP_REQUIRE(std::isfinite(v_min) && std::isfinite(dv) && std::isfinite(sigma_v), TSP_EINVAL, "v_min, dv and sigma_v must be finite");
+    TSP_REQUIRE(dv > 0.0, TSP_EINVAL, "dv = %g must be > 0", dv);
+    TSP_REQUIRE(sigma_v >= 0.0f, TSP_EINVAL, "sigma_v = %g must be >= 0", (double)sigma_v);
+    if (int rc = check_cube_shape(ctx->R, n_channels)) return rc;
+    const Particles &p = ctx->p;
+    TSP_REQUIRE(ctx->have_mips, TSP_ESTATE, "tsp_set_kernel_mips must be called before tsp_spectral_cube");
+    TSP_REQUIRE(p.n > 0 && p.x && p.y && p.z && p.h && p.m, TSP_ESTATE, "no particles with mass are resident");
+    TSP_REQUIRE(p.vx && p.vy && p.vz, TSP_ESTATE, "velocities not uploaded (tsp_upload_velocities)");
+    TSP_REQUIRE(ctx->have_los, TSP_ESTATE, "no line of sight set (tsp_set_line_of_sight)");
+    TSP_REQUIRE(p.n < (1ll << 31), TSP_EINVAL, "n = %lld outside [1, 2^31)", (long long)p.n);
+    TSP_HIP(hipSetDevice(ctx->device));
+    return spectral_cube(ctx, make_camera(ctx, M, scale_factor), v_min, dv, n_channels, (double)sigma_v, sigma, cube_out);
+}
+
+int tsp_spectral_cube_layout(int64_t n, int resolution, int n_channels, int64_t slice_option, int has_sigma, int64_t *out) {
+    TSP_REQUIRE(out, TSP_EINVAL, "NULL argument");
+    TSP_REQUIRE(n >= 0 && n < (1ll << 31), TSP_EINVAL, "n = %lld outside [0, 2^31)", (long long)n);
+    TSP_REQUIRE(slice_option >= 0, TSP_EINVAL, "slice_option = %lld must be >= 0", (long long)slice_option);
+    if (int rc = check_cube_shape(resolution, n_channels)) return rc;
+    const cube::Grid g = cube::grid_of(resolution, n_channels);
+    const int64_t per_slice = cube::slice_particles(n, resolution, n_channels, slice_option);
+    const cube::Carve c = cube::carve(n, per_slice, resolution, n_channels, has_sigma != 0, 0);
+    const int64_t v[TSP_CUBE_LAYOUT_VALUES] = {
+        g.tiles, g.blocks, g.bins, g.key_bits, per_slice, cube::slice_count(n, per_slice), c.capacity,
+        (int64_t)c.h_sigma, (int64_t)c.h_geom, (int64_t)c.h_line, (int64_t)c.h_bytes,
+        (int64_t)c.a_cube, (int64_t)c.a_count, (int64_t)c.a_offset, (int64_t)c.a_keys, (int64_t)c.a_keys_sorted, (int64_t)c.a_index,
+        (int64_t)c.a_index_sorted, (int64_t)c.a_bin_first, (int64_t)c.a_bin_end, (int64_t)c.a_tmp, (int64_t)c.a_bytes};
+    for (int k = 0; k < TSP_CUBE_LAYOUT_VALUES; ++k) out[k] = v[k];
+    return TSP_OK;
+}
+
 int tsp_present(tsp_context *ctx, int width, int height, const tsp_present_base *base, const tsp_present_layer *layers,
                 int n_layers, void *out, double *gpu_ms_out) {
     TSP_REQUIRE(ctx && base && out, TSP_EINVAL, "NULL argument");
@@ -1361,6 +1405,11 @@ int tsp_set_option(tsp_context *ctx, const char *name, int64_t value) {
     if (!strcmp(name, "slice_records")) {     // deferred footprints per launch of kernels G / H2 (0 = default: 2^27 mid, 2^30 huge)
         TSP_REQUIRE(value == 0 || (value >= 64 && value <= (1ll << 27)), TSP_EINVAL, "%s: 0 or 64 .. 2^27", name);
         ctx->slice_records = value;
+        return TSP_OK;
+    }
+    if (!strcmp(name, "cube_slice_particles")) {     // particles per slice of tsp_spectral_cube (0 = default: what the list bound allows); only lowers it
+        TSP_REQUIRE(value >= 0 && value < (1ll << 31), TSP_EINVAL, "%s: 0 .. 2^31 - 1", name);
+        ctx->cube_slice_particles = value;
         return TSP_OK;
     }
     if (!strcmp(name, "debug_fail_stage")) {   // test aid: the next tsp_render fails after kernel S (1) or after kernel G (2)

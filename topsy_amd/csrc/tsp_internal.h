@@ -178,7 +178,8 @@ struct tsp_context {
     int64_t chunk_culled_particles = 0;   // of the last render call
     bool overlap_mid_huge = false;    // option: kernels G and H2 on two streams (measured: no gain at 1.25e8, +6 % at 1e7)
     int64_t slice_records = 0;        // option: deferred records kernels G / H2 take per launch (0 = 2^27 mid / 2^30 huge); a block of any size draws in slices
-    int debug_fail_stage = 0;         // test aid: the next render fails with TSP_ENOMEM after kernel S (1) / after kernel G (2); cleared by the failure
+    int64_t cube_slice_particles = 0; // option: particles per slice of tsp_spectral_cube (0 = what the list bound allows, tsp_cube_layout.h); only lowers it
+    int debug_fail_stage = 0;        // test aid: the next render fails with TSP_ENOMEM after kernel S (1) / after kernel G (2); cleared by the failure
     int64_t debug_fail_alloc = 0;     // test aid: the k-th allocation of alloc_group() or scratch_alloc() from now on fails once, as hipMalloc would (0 = off)
     int stream_occ[3][2] = {};        // kernel S: workgroups resident per CU by [mode][one-channel window | all channels] (occupancy query, once per context)
     bool debug_no_raster = false;    // measurement aid: kernel S classifies and emits records but rasterises nothing (the image is then incomplete)
@@ -288,6 +289,10 @@ int ensure_weights(tsp_context *ctx, bool rgb);
 // tsp_kinematics.hip: the kinematic weights into p.wr / wg / wb (on ctx->stream) and the per-pixel moment maps of a kinematic image
 int launch_kinematic_weights(tsp_context *ctx);
 int launch_velocity_moments(tsp_context *ctx, const float *d_img, int64_t npix, float *d_maps);
+// tsp_cube.hip: the position-position-velocity cube of every resident particle (tsp_spectral_cube); per-call DeviceScratch only,
+// through the sites of gather_scratch(); no context state
+int spectral_cube(tsp_context *ctx, const Camera &cam, double v_min, double dv, int n_channels, double sigma_v, const float *sigma,
+                  float *cube_out);
 int ensure_block_bounds(tsp_context *ctx);     // (re)computes ws.block_bounds on ctx->stream when the particles changed
 int measure_read_bandwidth(tsp_context *ctx, int64_t bytes, int iters, double *gbps_out);
 int launch_image_convert(tsp_context *ctx, bool to_float);

@@ -214,6 +214,16 @@ class VelocityView:
         self._ensure_rendered()
         return maps_dict(self._sph._context.velocity_moments(), self._sph.last_render_mass_scale)
 
+    def get_cube(self, v_range=None, n_channels=64, sigma_v=0.0, sigma=None):
+        """The spectral cube of the scene at the visualizer's camera and this view's v_ref (topsy_amd.SpectralCube: data
+        (n_channels, R, R), v_edges, moment(), spectrum(), pv()): per pixel the whole distribution of the line-of-sight velocity
+        that v_los and sigma_los summarise, every particle drawn once in one pass (tsp_spectral_cube).  v_range: (v_min, v_max), or
+        None for (-V, V) with V = max |u| over the loader's finite velocities plus 5 times the largest line width.  A particle's
+        line is a Gaussian of width sqrt(sigma_v^2 + sigma[i]^2) integrated over each channel; sigma: per particle, in the
+        loader's order, or None.  The view's own frame stays as it is."""
+        from . import spectral
+        return spectral.view_cube(self, v_range=v_range, n_channels=n_channels, sigma_v=sigma_v, sigma=sigma)
+
     def _lut(self, name):
         if name not in self._luts:
             from .colormap.implementation import _lut_from_matplotlib
