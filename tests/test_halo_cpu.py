@@ -89,7 +89,7 @@ def test_a_clump_and_its_image_across_a_face():
 
 def test_ordered_sums_are_sums():
     rs = np.random.RandomState(1)
-    for k, start in ((1, 0), (255, 1), (256, 0), (257, 255), (20000, 77)):
+    for k, start in ((1, 0), (255, 1), (256, 0), (257, 255), (20000, 77), (32769, 0)):
         t = rs.normal(size=(k, 2))
         assert np.allclose(ref.ordered_sum(t, start), t.sum(axis=0), rtol=0, atol=1e-12 * np.abs(t).sum())
         m = rs.uniform(0.5, 1.5, k)
@@ -123,6 +123,152 @@ def test_crumbs_and_nonfinite_conditions():
     assert props["n_members"] == clean["n_members"] - 7 and pot["info"]["n_members"] == clean["n_members"] - 5
     assert props["n_key_ambiguous"] == 0
     assert (props["n_bound"] == -1).sum() == 1 and np.isnan(props["e_pot"]).sum() == 1      # the halo whose member has no eps: NaN phi
+
+
+@pytest.mark.parametrize("name", ["clumps", "periodic"])
+def test_sampled_potential_model_gives_the_full_models_bits(name):
+    scene, full, _ = ref.reference(name)
+    targets = ref.target_sample(scene, 4, seed=1)
+    part = ref.potential_model(scene, targets=targets)
+    assert len(targets) >= 4 * 17 and np.array_equal(part["targets"], targets)
+    for k in ("phi", "scale"):
+        assert np.array_equal(part[k][targets].view(np.uint64), full[k][targets].view(np.uint64)), k
+    rest = np.setdiff1d(np.arange(len(scene["pos"])), targets)
+    assert np.isnan(part["phi"][rest]).all() and (part["scale"][rest] == 0).all()
+    assert part["info"] == full["info"] and np.array_equal(part["counts"], full["counts"])
+    assert np.array_equal(part["member_has_value"], full["member_has_value"])
+    assert np.array_equal(full["member_has_value"], ~np.isnan(full["phi"])), "the NaN pattern of the whole array"
+    skip = ref.potential_model(scene, max_members=1000, targets=targets)
+    assert np.array_equal(skip["member_has_value"], ~np.isnan(ref.potential_model(scene, max_members=1000)["phi"]))
+
+
+def layout(scene):
+    """(sorted position of every particle or -1, starts, counts) of the potential's members"""
+    index, starts, counts = ref.sorted_positions(scene)
+    where = np.full(len(scene["pos"]), -1, dtype=np.int64)
+    where[index] = np.arange(len(index))
+    return where, starts, counts
+
+
+@pytest.mark.parametrize("name", ["edges", "edges+1", "giants", "legion"])
+def test_target_sample_holds_every_edge_class(name):
+    scene = ref.reference(name)[0]
+    targets = ref.reference(name)[1]["targets"] if name in ref.SAMPLED else ref.target_sample(scene, 4, seed=1)
+    where, starts, counts = layout(scene)
+    p = where[targets]
+    assert (p >= 0).all() and len(np.unique(targets)) == len(targets)
+    assert np.isin(starts, p).all() and np.isin(starts + counts - 1, p).all(), "every halo's first and last sorted member"
+    for modulus, residues in ((1024, (0, 255, 256, 1023)), (512, (0, 511))):
+        for r in residues:
+            assert (p % modulus == r).sum() >= 3, f"sorted positions = {r} mod {modulus}"
+    per_halo = np.bincount(scene["labels"][targets], minlength=scene["n_groups"] + 1)[1:]
+    assert (per_halo >= np.minimum(counts, ref.SAMPLED.get(name, 4))).all()
+    if name in ref.SAMPLED:
+        assert 500 <= len(targets) <= ref.MAX_TARGETS
+    if name == "legion":       # the blocks of the second launch have targets of every class of lane plane and tile edge
+        block0 = ref.work_items(counts)["launches"][1][0]
+        late = p[p >= block0 * 1024]
+        assert len(late) >= 50 and {0, 255, 256, 1023} <= set(late % 1024) and {0, 511} <= set(late % 512)
+
+
+@pytest.mark.parametrize("name", ["edges", "edges+1"])
+def test_edges_layout(name):
+    scene, pot, props = ref.reference(name)
+    extra = int(name == "edges+1")
+    counts = props["count"]
+    assert list(counts) == list(ref.EDGE_SIZES[:-1]) + [ref.EDGE_SIZES[-1] + extra] and np.array_equal(pot["counts"], counts)
+    ends = np.cumsum(counts)
+    starts = ends - counts
+    lay = [ref.piece_layout(int(s), int(c)) for s, c in zip(starts, counts)]
+    H = len(counts)
+    assert any(g > 0 and starts[g] % 256 == 0 and lay[g][0] == 0 for g in range(H)), "a later halo that starts a slice"
+    assert any(ends[g] % 256 == 0 for g in range(H - 1)), "a halo that ends a slice"
+    assert any(g > 0 and counts[g] == 256 and starts[g] % 256 == 0 and lay[g] == (0, 1, 1, 1) for g in range(H)), "one aligned slice"
+    one_b = [g for g in range(H) if counts[g] == 256 and starts[g] % 256 == 255]
+    assert one_b and lay[one_b[0]] == (1, 2, 1, 2) and ref._pieces(256, int(starts[one_b[0]]))[0] == (0, 1), "a B piece of one member"
+    singles = [g for g in range(H - 2) if (counts[g:g + 3] == 1).all() and starts[g + 1] % 256 in (0, 255)]
+    assert singles, "three one-member haloes across a slice boundary"
+    assert 10 in counts and 9 in counts
+    ten, nine = list(counts).index(10), list(counts).index(9)
+    assert props["v2_max"][ten] > 0 and props["i_vmax"][ten] >= 0 and np.isnan(props["v2_max"][nine]) and props["i_vmax"][nine] == -1
+    assert any(ends[g] % 1024 == 0 and starts[g + 1] == ends[g] for g in range(H - 1)), "a halo that ends a block"
+    assert any(counts[g] == 1024 and starts[g] % 1024 == 0 for g in range(H)), "a halo that is exactly one block"
+    assert props["n_members"] == pot["info"]["n_members"] == ends[-1] and ends[-1] % 512 == extra
+    assert len(scene["pos"]) == ends[-1] + ref.N_BACKGROUND_BIG and set(scene["labels"][scene["labels"] < 1]) == {0, -1, -7}
+    assert props["n_key_ambiguous"] == 0, "members whose radial key could round either way"
+
+
+def test_giants_conditions():
+    scene, pot, props = ref.reference("giants")
+    counts = props["count"]
+    assert list(counts) == list(ref.GIANT_SIZES) and np.array_equal(pot["counts"], counts)
+    starts = np.cumsum(counts) - counts
+    lay = {name: ref.piece_layout(int(starts[g - 1]), int(counts[g - 1])) for name, g in ref.GIANT_LABELS.items()}
+    assert lay == dict(aligned_16384=(0, 64, 1, 64), misaligned_16384=(1, 65, 2, 33), aligned_32768=(0, 128, 2, 64),
+                       aligned_32769=(0, 129, 3, 43))
+    assert props["n_key_ambiguous"] == 0, "members whose radial key could round either way"
+    # the bound fraction, at the sampled members (the potential of every member of a giant is out of the model's reach)
+    t = pot["targets"]
+    g = scene["labels"][t] - 1
+    w = scene["vel"][t].astype(np.float64) - props["v_com"][g]
+    bound = 0.5 * (w * w).sum(axis=1) + pot["phi"][t] < 0.0
+    frac = np.array([bound[g == k - 1].mean() for k in ref.GIANT_LABELS.values()])
+    print(f"\ngiants: bound fractions of the sampled members {frac}")
+    assert (frac > 0.5).all() and (frac < 1.0).any(), "n_bound would test nothing"
+    assert pot["info"]["max_extent"] == props["max_extent"] and pot["info"]["n_members"] == sum(ref.GIANT_SIZES) == 98561
+    # every block of a giant has the 16 work items of the cap, in one launch
+    w = ref.work_items(counts)
+    assert len(w["launches"]) == 1 and (w["splits_per_block"] == 16).all()
+
+
+def test_legion_conditions():
+    scene, pot, _ = ref.reference("legion")
+    counts = pot["counts"]
+    assert list(counts) == list(ref.LEGION_SIZES) and (counts[len(ref.GIANT_SIZES):] >= 15872).all()
+    assert (counts[len(ref.GIANT_SIZES):] % 256 != 0).all() and len(set(counts)) == len(counts) - 1       # (16384 twice)
+    w = ref.work_items(counts)
+    items = np.array(w["items"])
+    print(f"\nlegion: {pot['info']['n_members']} members, {len(items)} work items, launches {w['launches']}")
+    assert len(items) > 4096 and len(w["launches"]) >= 2 and sum(l[2] for l in w["launches"]) == len(items)
+    assert all(l[2] <= 4096 for l in w["launches"]) and w["launches"][0][1] == w["launches"][1][0]
+    index, starts, _ = ref.sorted_positions(scene)
+    p = w["launches"][1][0] * 1024
+    lab = scene["labels"][index]                                                # the labels by sorted position
+    assert 0 < p < len(lab) and lab[p - 1] == lab[p] and p not in starts, "the launch break falls between two haloes"
+    # the slots restart in every launch, and a block's items are consecutive slots
+    for b0, b1, n_items in w["launches"]:
+        sel = (items[:, 0] >= b0) & (items[:, 0] < b1)
+        assert np.array_equal(items[sel, 3], np.arange(n_items))
+    tiles = np.array([items[items[:, 0] == b, 2].max() - items[items[:, 0] == b, 1].min() for b in range(len(w["splits_per_block"]))])
+    assert ((w["splits_per_block"] == 16) & (tiles % 16 != 0)).any(), "no block at the cap has items of unequal length"
+    assert (tiles >= 31).all() and len(set(items[:, 2] - items[:, 1])) >= 3
+    assert np.array_equal(np.bincount(items[:, 0]), w["splits_per_block"]) and (items[:, 2] > items[:, 1]).all()
+    assert w["pair_slots"] == (items[:, 2] - items[:, 1]).sum() * 512 * 1024
+    skip = ref.work_items(counts, ref.LEGION_MAX_MEMBERS)
+    none = np.flatnonzero(skip["splits_per_block"] == 0)
+    assert len(none) and (skip["splits_per_block"][:none[0]] > 0).any() and (skip["splits_per_block"][none[-1] + 1:] > 0).any()
+    model = ref.potential_model(scene, ref.LEGION_MAX_MEMBERS, targets=pot["targets"][:1])
+    assert model["info"]["n_skipped_groups"] == 2 and model["info"]["n_skipped_members"] == 32768 + 32769
+
+
+def test_work_items_of_single_haloes():
+    """the pair slots that the contract states outright: blocks x tiles of the block's range x 512 x 1024"""
+    w = ref.work_items([2048])
+    assert w["pair_slots"] == 2 * 4 * 512 * 1024 and w["launches"] == [(0, 2, 4)] and list(w["splits_per_block"]) == [2, 2]
+    assert w["items"] == [(0, 0, 2, 0), (0, 2, 4, 1), (1, 0, 2, 2), (1, 2, 4, 3)]
+    assert ref.work_items([1])["pair_slots"] == 512 * 1024 and ref.work_items([1])["items"] == [(0, 0, 1, 0)]
+    assert ref.work_items([513])["items"] == [(0, 0, 2, 0)] and ref.work_items([1025])["pair_slots"] == 2 * 3 * 512 * 1024
+    assert ref.work_items([0, 0, 0])["items"] == [] and ref.work_items([0])["launches"] == []
+    # one halo of 16384: 16 blocks of 32 tiles, 16 items of 2 tiles each; of 16385: 17 blocks of 33 tiles, items of 2 and 3 tiles
+    w = ref.work_items([16384])
+    assert w["pair_slots"] == 16 * 32 * 512 * 1024 and len(w["items"]) == 256 and {b - a for _, a, b, _ in w["items"]} == {2}
+    w = ref.work_items([16385])
+    assert len(w["items"]) == 17 * 16 and {b - a for _, a, b, _ in w["items"]} == {2, 3}
+    assert [a for blk, a, _, _ in w["items"] if blk == 0] == [33 * s // 16 for s in range(16)]
+    # a skipped halo has no items and is left out of its neighbours' ranges
+    w = ref.work_items([100, 5000, 100], max_members=1000)
+    assert list(w["splits_per_block"]) == [1, 0, 0, 0, 1, 1] and w["items"] == [(0, 0, 1, 0), (4, 9, 11, 1), (5, 9, 11, 2)]
+    assert ref.piece_layout(0, 0) == (0, 0, 0, 0) and ref.piece_layout(5, 1) == (1, 1, 1, 1) and ref.piece_layout(255, 2) == (1, 2, 1, 2)
 
 
 # ---- the argument checks ----------------------------------------------------------------------------------------------------------
