@@ -118,7 +118,9 @@ const char *tsp_last_error(void);
  * 125: new entry points tsp_group_potential and tsp_halo_properties and the structs tsp_group_potential_info / tsp_halo_info (the
  * haloes of a catalogue in one call: self-potential, masses, centres, radii, spin, bound mass); nothing else changed.
  * 126: new entry points tsp_spectral_cube and tsp_spectral_cube_layout (position-position-velocity cubes of the resident
- * particles, "Spectral cubes" below) and the option "cube_slice_particles"; no struct changed, nothing else changed. */
+ * particles, "Spectral cubes" below) and the option "cube_slice_particles"; no struct changed, nothing else changed.
+ * 127: new entry points tsp_histogram_2d and tsp_histogram_2d_layout and the structs tsp_hist2d_spec / tsp_hist2d_info (weighted 2-D
+ * histograms of per-particle quantities: phase diagrams, "Weighted 2-D histograms" below); nothing else changed. */
 int tsp_version(void);
 int tsp_stats_size(void);
 
@@ -574,6 +576,64 @@ int tsp_radial_profile(tsp_context *ctx, int64_t n, const float *x, const float 
                        const float *vx, const float *vy, const float *vz,      /* all three or none (NULL) */
                        const tsp_profile_spec *spec, int64_t *count_out /* n_bins */, double *sums_out /* n_bins * 11 */,
                        tsp_profile_info *info_out);
+
+/* Weighted 2-D histograms: the phase diagram -- the mass in each cell of a (rho, T) plane, or any quantity against any other weighted
+ * by a third (pynbody's plot.rho_T / plot.generic.hist2d).  Host arrays in, in the caller's order, as the other per-call analyses;
+ * the call uses the context's device and stream only, is allowed in every state of the context, and leaves the resident particles,
+ * the image, the accumulator and tsp_stats as they are.
+ *
+ * tsp_histogram_2d: n particles with the float32 coordinates x, y, the float32 weights w (NULL: every weight 1) and the float32
+ * values v (NULL: no value), binned into nx columns and ny rows.
+ *   - Valid.  A particle is valid iff x[i], y[i], w[i] (when given) and v[i] (when given) are all finite.  Any finite weight is
+ *     allowed, negative and zero included.  n_valid = the number of valid particles.
+ *   - Bin.  The float32 coordinate is widened to float64 (exact) and compared with the edges as passed: column i holds
+ *     edges_x[i] <= x < edges_x[i + 1], row j holds edges_y[j] <= y < edges_y[j + 1].  A valid particle with both in range is a
+ *     member of cell c = j * nx + i.  A value equal to an inner edge goes to the upper cell; a value equal to the LAST edge is
+ *     outside -- the rule of tsp_radial_profile, not the closed last bin of numpy.histogram2d (move the last edge up by one ulp to
+ *     bin a maximum).  The device evaluates no logarithm: logarithmic bins are logarithmic edges built by the caller, and the
+ *     binning is exact against a float64 model.  n_binned = the number of members of all cells.
+ *   - Outputs.  With S = nx * ny: count_out[c] = the members of cell c; sums_out[0 * S + c] = sum w; with v,
+ *     sums_out[1 * S + c] = sum w * v and sums_out[2 * S + c] = sum (w * v) * v.  The terms are formed in float64 from the widened
+ *     float32s; every sum starts at +0.0; a cell without members is count 0 and +0.0 whatever an earlier call left on the device.
+ *     bin_out (n int32, or NULL): bin_out[p] = the cell of particle p, or -1 if it is invalid or outside.  info_out is optional.
+ *     A histogram without members is zeros, not an error.
+ *   - Determinism.  No floating-point atomics.  The particles are sorted by cell (a stable radix sort over the
+ *     ceil(log2(S + 1)) bits of a cell index; particles in no cell sort last) and every cell's terms are added by a tree whose shape
+ *     depends on n alone: a segmented scan over each wave's 64 sorted entries, then over the two boundary runs of each of a
+ *     workgroup's four waves in wave order, then the same over the two boundary records of every block of TSP_HIST2D_BLOCK entries,
+ *     level by level.  The order of a sum is therefore fixed but depends on where the cell's run lies in the sorted list: the same
+ *     call on the same input and device returns the same bits; a permuted input may differ in the last bits of a sum.  Counts are
+ *     integers.  For a cell of m members each sum lies within m * 2^-52 * sum |term| of the exact sum.
+ *   - Cost.  A cell that holds a third of the particles is reduced by n / 3 / TSP_HIST2D_BLOCK workgroups in parallel: no
+ *     workgroup walks a cell's members.
+ *   - TSP_EINVAL: n < 1 or n >= 2^31; NULL among x, y, spec, spec->edges_x, spec->edges_y, count_out, sums_out; nx or ny outside
+ *     [1, 1024]; an edge that is not finite, or edges that are not strictly ascending.  A refused call writes nothing.
+ *   - Device memory is per call, through the two allocations of tsp_sph_sum (first the caller's arrays, 8 to 16 bytes per particle;
+ *     then the table, the keys and indices in and out of the sort, 16 bytes per particle, the records of the reduction, about 0.25
+ *     byte per particle, and the sort's temporary storage); a failed allocation returns TSP_ENOMEM and writes nothing.
+ * tsp_histogram_2d_layout: the host arithmetic of the call without a device or a context -- for (n, nx, ny, has_w, has_v,
+ * want_bins), out[TSP_HIST2D_LAYOUT_VALUES] receives: the bits of a key, TSP_HIST2D_BLOCK, the levels of the reduction, the
+ * blocks of level 0, the records of the two record buffers; then (byte offset, bytes used) of x, y, w, v inside the first
+ * allocation and its size; then (byte offset, bytes used) inside the second of the counts, the sums, the edges, the two counters,
+ * the keys, the sorted keys, the indices, the sorted indices, the record buffers A and B, the sort's temporary storage (counted as
+ * 0 bytes here) and its size; last the bytes copied into bin_out (the key array itself: all ones is -1; 0 without want_bins).
+ * Every offset is a multiple of 256.  TSP_EINVAL for n outside [1, 2^31), nx or ny outside [1, 1024] or a NULL out. */
+#define TSP_HIST2D_MAX_BINS 1024                    /* per axis */
+#define TSP_HIST2D_BLOCK 256                        /* sorted entries per workgroup of the reduction */
+#define TSP_HIST2D_LAYOUT_VALUES 39
+typedef struct {
+    int32_t nx, ny;            /* 1 .. 1024 each */
+    const double *edges_x;     /* nx + 1, finite, strictly ascending */
+    const double *edges_y;     /* ny + 1, finite, strictly ascending */
+} tsp_hist2d_spec;
+typedef struct { int64_t n_valid, n_binned; } tsp_hist2d_info;
+int tsp_histogram_2d(tsp_context *ctx, int64_t n, const float *x, const float *y,
+                     const float *w /* NULL: every weight 1 */, const float *v /* NULL: no value */,
+                     const tsp_hist2d_spec *spec,
+                     int64_t *count_out /* ny * nx */, double *sums_out /* (v ? 3 : 1) * ny * nx */,
+                     int32_t *bin_out /* n, or NULL */, tsp_hist2d_info *info_out /* optional */);
+int tsp_histogram_2d_layout(int64_t n, int nx, int ny, int has_w, int has_v, int want_bins,
+                            int64_t *out /* TSP_HIST2D_LAYOUT_VALUES */);
 
 /* Softened direct-sum gravity: the potential and the acceleration at every target from every source -- pynbody's gravity.calc
  * direct sum, from which a snapshot's 'phi' and a disc profile's midplane rotation curve and potential are taken.  Host arrays in,

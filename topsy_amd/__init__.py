@@ -520,10 +520,34 @@ def spectral_cube(pos, smooth, mass, vel, v_range=None, n_channels=64, sigma_v=0
                                   device_id=device_id)
 
 
+def phase_diagram(x, y, weights=None, values=None, x_range=None, y_range=None, bins=(256, 256), x_log=False, y_log=False, edges=None,
+                  return_index=False, device=None):
+    """The phase diagram of arrays on GPU `device` (None: 0; C: tsp_histogram_2d): a topsy_amd.PhaseDiagram (topsy_amd/phase.py) --
+    per cell of a 2-D table over (x, y) the particle count, the sum of `weights` (None: the count) and, with `values`, their
+    weighted mean and dispersion: pynbody's plot.rho_T / plot.generic.hist2d for arrays, e.g. phase_diagram(rho, temp, mass,
+    x_log=True, y_log=True).  bins: an int or (nx, ny), 1 to 1024 each, between x_range / y_range (None: the minimum and the
+    maximum of the axis' finite values -- for a logarithmic axis of its finite positive ones -- the upper end moved up by one
+    float64 ulp so that the maximum is binned); x_log / y_log make the bins logarithmic; edges = (edges_x, edges_y) takes the
+    caller's own ascending edges instead.  Bins are half-open, the last edge is outside.  Arrays are any float dtype, converted to
+    float32; a particle with a non-finite x, y, weight or value takes no part; any finite weight is allowed.  The sums are
+    float64 in a fixed order: the same call returns the same bits.  return_index keeps every particle's cell
+    (PhaseDiagram.bin_index, PhaseDiagram.select).  Raises ValueError for mismatched lengths and bad arguments."""
+    from . import _native, phase
+    x, y, w, v, edges_x, edges_y = phase.check_phase_arguments(x, y, weights, values, x_range, y_range, bins, x_log, y_log, edges)
+    ctx = _native.Context(1, 2, 0 if device is None else device)
+    try:
+        return phase.compute_phase_diagram(ctx, x, y, w, v, edges_x, edges_y, x_log, y_log, return_index)
+    finally:
+        ctx.close()
+
+
 def __getattr__(name):
     """topsy_amd.VisualizationRecorder (movie recording and export, topsy_amd/recorder), topsy_amd.FofCatalogue and
     topsy_amd.Profile (topsy_amd/loader.py), topsy_amd.RotationCurve (topsy_amd/gravity.py), topsy_amd.SpectralCube
-    (topsy_amd/spectral.py), imported on first use."""
+    (topsy_amd/spectral.py), topsy_amd.PhaseDiagram (topsy_amd/phase.py), imported on first use."""
+    if name == "PhaseDiagram":
+        from .phase import PhaseDiagram
+        return PhaseDiagram
     if name == "SpectralCube":
         from .spectral import SpectralCube
         return SpectralCube

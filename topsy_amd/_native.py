@@ -20,7 +20,8 @@ ABI_VERSION = 112            # the oldest tsp_version() whose structs this bindi
                              # (113: tsp_shrink_sphere_center, 114: tsp_fof_groups, 115: tsp_sphere_moments,
                              # 116: tsp_radial_profile, 117: the kinematic maps, 119: tsp_moment_sort,
                              # 120: tsp_sph_velocity_gradient, 122: tsp_sph_sample_lattice, 123: tsp_gravity_direct,
-                             # 124: tsp_gravity_tree, 125: tsp_group_potential, tsp_halo_properties) are required by
+                             # 124: tsp_gravity_tree, 125: tsp_group_potential, tsp_halo_properties, 126: tsp_spectral_cube,
+                             # 127: tsp_histogram_2d) are required by
                              # name in load_library()
 PRESENT_SCALAR, PRESENT_BIVARIATE, PRESENT_RGB, PRESENT_RGB_HDR, PRESENT_MOMENT_MEAN, PRESENT_MOMENT_SIGMA = 0, 1, 2, 3, 4, 5
 LAYER_QUAD, LAYER_LINES = 0, 1
@@ -91,6 +92,17 @@ class ProfileInfo(ctypes.Structure):
                 ("mass_inner", ctypes.c_double)]
 
 
+class Hist2dSpec(ctypes.Structure):
+    """struct tsp_hist2d_spec."""
+    _fields_ = [("nx", ctypes.c_int32), ("ny", ctypes.c_int32), ("edges_x", ctypes.POINTER(ctypes.c_double)),
+                ("edges_y", ctypes.POINTER(ctypes.c_double))]
+
+
+class Hist2dInfo(ctypes.Structure):
+    """struct tsp_hist2d_info."""
+    _fields_ = [("n_valid", ctypes.c_int64), ("n_binned", ctypes.c_int64)]
+
+
 class Lattice(ctypes.Structure):
     """struct tsp_lattice: point (i, j, k) is origin + i du + j dv + k dw."""
     _fields_ = [("origin", ctypes.c_double * 3), ("du", ctypes.c_double * 3), ("dv", ctypes.c_double * 3),
@@ -146,6 +158,15 @@ CUBE_MAX_CELLS = 1 << 31     # ... and n_channels * R * R
 CUBE_LAYOUT_NAMES = ("tiles", "blocks", "bins", "key_bits", "slice_particles", "slices", "list_capacity",
                      "h_sigma", "h_geom", "h_line", "h_bytes", "a_cube", "a_count", "a_offset", "a_keys", "a_keys_sorted", "a_index",
                      "a_index_sorted", "a_bin_first", "a_bin_end", "a_tmp", "a_bytes")      # tsp_spectral_cube_layout's values
+HIST2D_MAX_BINS = 1024      # tsp_histogram_2d: bins per axis at most
+HIST2D_BLOCK = 256          # ... and the sorted entries a workgroup of its reduction takes (the header's TSP_HIST2D_BLOCK)
+_HIST2D_REGIONS_H = ("h_x", "h_y", "h_w", "h_v")
+_HIST2D_REGIONS_A = ("a_count", "a_sums", "a_edges", "a_counters", "a_keys", "a_keys_sorted", "a_index", "a_index_sorted",
+                     "a_records_a", "a_records_b", "a_tmp")
+HIST2D_LAYOUT_NAMES = (("key_bits", "block", "levels", "blocks", "records_a", "records_b")
+                       + tuple(f"{r}{suffix}" for r in _HIST2D_REGIONS_H for suffix in ("", "_size")) + ("h_bytes",)
+                       + tuple(f"{r}{suffix}" for r in _HIST2D_REGIONS_A for suffix in ("", "_size")) + ("a_bytes", "bins_bytes"))
+                                                                                        # tsp_histogram_2d_layout's values
 PROFILE_SUMS = 11           # doubles per bin of tsp_radial_profile's sums_out: mass, ms, mc (3), mc2 (3), mj (3)
 
 
@@ -234,6 +255,9 @@ SIGNATURES = {
                                           ctypes.c_double, ctypes.c_double, ctypes.POINTER(Moments)]),
     "tsp_radial_profile": (ctypes.c_int, [_ctx, ctypes.c_int64, _fp, _fp, _fp, _fp, _fp, _fp, _fp, ctypes.POINTER(ProfileSpec), _i64p,
                                           ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ProfileInfo)]),
+    "tsp_histogram_2d": (ctypes.c_int, [_ctx, ctypes.c_int64, _fp, _fp, _fp, _fp, ctypes.POINTER(Hist2dSpec), _i64p,
+                                        ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(Hist2dInfo)]),
+    "tsp_histogram_2d_layout": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _i64p]),
     "tsp_gravity_direct": (ctypes.c_int, [_ctx, ctypes.c_int64, _fp, _fp, _fp, _fp, _fp, ctypes.c_float, ctypes.c_int64, _fp, _fp, _fp,
                                           ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double),
                                           ctypes.POINTER(GravityInfo)]),
@@ -377,6 +401,16 @@ def spectral_cube_layout(n, resolution, n_channels, slice_option=0, has_sigma=Fa
     return dict(zip(CUBE_LAYOUT_NAMES, out.tolist()))
 
 
+def histogram_2d_layout(n, nx, ny, has_w=False, has_v=False, want_bins=False):
+    """The host arithmetic of tsp_histogram_2d as a dict (HIST2D_LAYOUT_NAMES): the bits of a key, the block of the reduction, its
+    levels and blocks, the records of its two record buffers, and per region of the two device buffers the byte offset (`name`) and
+    the bytes used (`name_size`) (tsp_histogram_2d_layout; needs no GPU)."""
+    out = np.zeros(len(HIST2D_LAYOUT_NAMES), dtype=np.int64)
+    _check(load_library().tsp_histogram_2d_layout(int(n), int(nx), int(ny), int(bool(has_w)), int(bool(has_v)), int(bool(want_bins)),
+                                                  out.ctypes.data_as(_i64p)))
+    return dict(zip(HIST2D_LAYOUT_NAMES, out.tolist()))
+
+
 def _ranges(starts, lens):
     """(starts pointer, lens pointer, count, the arrays the pointers lend from) of a render call's ranges; None = no ranges."""
     if starts is None:
@@ -477,6 +511,34 @@ class Context:
         out = np.empty(shape if allowed else (1,), dtype=np.float32)       # (the library refuses the others: TSP_EINVAL)
         _check(self._lib.tsp_spectral_cube(self._h, _ptr(M), float(scale_factor), float(v_min), float(dv), int(n_channels),
                                            float(np.float32(sigma_v)), _ptr(s), _ptr(out)))
+        return out
+
+    def histogram_2d(self, x, y, w=None, v=None, edges_x=(0.0, 1.0), edges_y=(0.0, 1.0), want_bins=False):
+        """The weighted 2-D histogram of the caller-ordered float32 arrays (tsp_histogram_2d): column i holds
+        edges_x[i] <= x < edges_x[i + 1], row j likewise from edges_y (the last edge is outside).  Returns a dict: "count"
+        (ny, nx) int64, "sums" (1 or, with v, 3 planes of (ny, nx)) float64 -- sum w, sum w v, sum (w v) v; w None: weights of 1 --,
+        "n_valid", "n_binned" and, with want_bins, "bin_index" (n int32: the cell j * nx + i of every particle, or -1)."""
+        n = len(x)
+        x, y = _f32(x, n, "x"), _f32(y, n, "y")
+        w = None if w is None else _f32(w, n, "w")
+        v = None if v is None else _f32(v, n, "v")
+        ex, ey = (np.ascontiguousarray(e, dtype=np.float64).ravel() for e in (edges_x, edges_y))
+        nx, ny = len(ex) - 1, len(ey) - 1
+        allowed = 1 <= nx <= HIST2D_MAX_BINS and 1 <= ny <= HIST2D_MAX_BINS
+        shape = (ny, nx) if allowed else (1, 1)                 # (the library refuses the others: TSP_EINVAL)
+        dp = ctypes.POINTER(ctypes.c_double)
+        spec = Hist2dSpec(nx, ny, ex.ctypes.data_as(dp), ey.ctypes.data_as(dp))
+        count = np.empty(shape, dtype=np.int64)
+        sums = np.empty((1 if v is None else 3,) + shape, dtype=np.float64)
+        bins = np.empty(n, dtype=np.int32) if want_bins else None
+        info = Hist2dInfo()
+        _check(self._lib.tsp_histogram_2d(self._h, n, _ptr(x), _ptr(y), _ptr(w), _ptr(v), ctypes.byref(spec),
+                                          count.ctypes.data_as(_i64p), sums.ctypes.data_as(dp),
+                                          None if bins is None else bins.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
+                                          ctypes.byref(info)))
+        out = {"count": count, "sums": sums, "n_valid": int(info.n_valid), "n_binned": int(info.n_binned)}
+        if want_bins:
+            out["bin_index"] = bins
         return out
 
     def colormap_moment(self, which, lut_rgba, vmin, vmax, log=False):

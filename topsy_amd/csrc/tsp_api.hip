@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "tsp_cube_layout.h"
+#include "tsp_hist2d_layout.h"
 #include "tsp_internal.h"
 #include "tsp_morton.h"
 
@@ -235,7 +236,7 @@ using namespace tsp;
 extern "C" {
 
 const char *tsp_last_error(void) { return g_err; }
-int tsp_version(void) { return 126; }     // 126: tsp_spectral_cube and tsp_spectral_cube_layout (position-position-velocity cubes of the resident particles), option "cube_slice_particles"; 125: tsp_group_potential and tsp_halo_properties (halo properties); 124: tsp_gravity_tree and the struct tsp_gravity_tree_info (Barnes-Hut tree gravity over the Morton order); 123: tsp_gravity_direct and the struct tsp_gravity_info (softened direct-sum gravity: potential, accelerations); 122: tsp_sph_sample_lattice and the struct tsp_lattice (SPH sums at the points of a lattice); 121: a failed upload is atomic (attributes: nothing changed; particles / synthetic: no particles left; groups: every member emptied); 120: tsp_sph_velocity_gradient; 119: tsp_moment_sort, TSP_PRESENT_MOMENT_MEAN / _SIGMA (the kinematic maps as the base of tsp_present / tsp_present_yuv420); 118: tsp_render_undo, tsp_group_render all-or-nothing across the members; 117: kinematic maps (tsp_upload_velocities, tsp_set_line_of_sight, TSP_MODE_KINEMATIC, tsp_velocity_moments, tsp_colormap_moment); 116: tsp_radial_profile; 115: tsp_sphere_moments; 114: tsp_fof_groups; 113: tsp_shrink_sphere_center; 112: tsp_present_surface, tsp_present_surface_yuv420; 111: tsp_content_neg_inf; 110: tsp_sph_sum; 109: tsp_present_yuv420; 108: tsp_present; 107: surface rendering; 106: tsp_smoothing_lengths; 101: tsp_stats gained ms_mega, n_mega (16 bytes); 102: the per-kernel fragment counts (32 bytes); 103: n_chunk_culled (8 bytes); 104: matrix-core / kernel-I options removed; 105: kernel M's options removed (kernel G draws the mid footprints)
+int tsp_version(void) { return 127; }     // 127: tsp_histogram_2d and tsp_histogram_2d_layout and the structs tsp_hist2d_spec / tsp_hist2d_info (weighted 2-D histograms: phase diagrams); 126: tsp_spectral_cube and tsp_spectral_cube_layout (position-position-velocity cubes of the resident particles), option "cube_slice_particles"; 125: tsp_group_potential and tsp_halo_properties (halo properties); 124: tsp_gravity_tree and the struct tsp_gravity_tree_info (Barnes-Hut tree gravity over the Morton order); 123: tsp_gravity_direct and the struct tsp_gravity_info (softened direct-sum gravity: potential, accelerations); 122: tsp_sph_sample_lattice and the struct tsp_lattice (SPH sums at the points of a lattice); 121: a failed upload is atomic (attributes: nothing changed; particles / synthetic: no particles left; groups: every member emptied); 120: tsp_sph_velocity_gradient; 119: tsp_moment_sort, TSP_PRESENT_MOMENT_MEAN / _SIGMA (the kinematic maps as the base of tsp_present / tsp_present_yuv420); 118: tsp_render_undo, tsp_group_render all-or-nothing across the members; 117: kinematic maps (tsp_upload_velocities, tsp_set_line_of_sight, TSP_MODE_KINEMATIC, tsp_velocity_moments, tsp_colormap_moment); 116: tsp_radial_profile; 115: tsp_sphere_moments; 114: tsp_fof_groups; 113: tsp_shrink_sphere_center; 112: tsp_present_surface, tsp_present_surface_yuv420; 111: tsp_content_neg_inf; 110: tsp_sph_sum; 109: tsp_present_yuv420; 108: tsp_present; 107: surface rendering; 106: tsp_smoothing_lengths; 101: tsp_stats gained ms_mega, n_mega (16 bytes); 102: the per-kernel fragment counts (32 bytes); 103: n_chunk_culled (8 bytes); 104: matrix-core / kernel-I options removed; 105: kernel M's options removed (kernel G draws the mid footprints)
 int tsp_stats_size(void) { return (int)sizeof(tsp_stats); }
 
 int tsp_device_count(void) {
@@ -1221,6 +1222,50 @@ int tsp_spectral_cube_layout(int64_t n, int resolution, int n_channels, int64_t 
         (int64_t)c.a_cube, (int64_t)c.a_count, (int64_t)c.a_offset, (int64_t)c.a_keys, (int64_t)c.a_keys_sorted, (int64_t)c.a_index,
         (int64_t)c.a_index_sorted, (int64_t)c.a_bin_first, (int64_t)c.a_bin_end, (int64_t)c.a_tmp, (int64_t)c.a_bytes};
     for (int k = 0; k < TSP_CUBE_LAYOUT_VALUES; ++k) out[k] = v[k];
+    return TSP_OK;
+}
+
+static int check_hist2d_shape(int64_t n, int nx, int ny) {
+    TSP_REQUIRE(n >= 1 && n < (1ll << 31), TSP_EINVAL, "n = %lld outside [1, 2^31)", (long long)n);
+    TSP_REQUIRE(nx >= 1 && nx <= hist2d::MAX_BINS && ny >= 1 && ny <= hist2d::MAX_BINS, TSP_EINVAL, "nx = %d or ny = %d outside [1, %d]",
+                nx, ny, hist2d::MAX_BINS);
+    return TSP_OK;
+}
+
+int tsp_histogram_2d(tsp_context *ctx, int64_t n, const float *x, const float *y, const float *w, const float *v,
+                     const tsp_hist2d_spec *spec, int64_t *count_out, double *sums_out, int32_t *bin_out, tsp_hist2d_info *info_out) {
+    TSP_REQUIRE(ctx && x && y && spec && count_out && sums_out, TSP_EINVAL, "NULL argument");
+    TSP_REQUIRE(spec->edges_x && spec->edges_y, TSP_EINVAL, "NULL edges");
+    if (int rc = check_hist2d_shape(n, spec->nx, spec->ny)) return rc;
+    const double *axis[2] = {spec->edges_x, spec->edges_y};
+    const int bins[2] = {spec->nx, spec->ny};
+    for (int a = 0; a < 2; ++a) {
+        TSP_REQUIRE(std::isfinite(axis[a][0]), TSP_EINVAL, "edges_%c[0] = %g is not finite", "xy"[a], axis[a][0]);
+        for (int k = 1; k <= bins[a]; ++k)
+            TSP_REQUIRE(std::isfinite(axis[a][k]) && axis[a][k] > axis[a][k - 1], TSP_EINVAL,
+                        "edges must be finite and strictly ascending: edges_%c[%d] = %g after %g", "xy"[a], k, axis[a][k], axis[a][k - 1]);
+    }
+    TSP_HIP(hipSetDevice(ctx->device));
+    return histogram_2d(ctx, n, x, y, w, v, spec, count_out, sums_out, bin_out, info_out);
+}
+
+int tsp_histogram_2d_layout(int64_t n, int nx, int ny, int has_w, int has_v, int want_bins, int64_t *out) {
+    TSP_REQUIRE(out, TSP_EINVAL, "NULL argument");
+    if (int rc = check_hist2d_shape(n, nx, ny)) return rc;
+    const hist2d::Levels lv = hist2d::levels_of(n);
+    const hist2d::Carve c = hist2d::carve(n, nx, ny, has_w != 0, has_v != 0, want_bins != 0, 0);
+    const hist2d::Region h[4] = {c.h_x, c.h_y, c.h_w, c.h_v};
+    const hist2d::Region a[11] = {c.a_count, c.a_sums, c.a_edges, c.a_counters, c.a_keys, c.a_keys_sorted, c.a_index, c.a_index_sorted,
+                                  c.a_records_a, c.a_records_b, c.a_tmp};
+    int k = 0;
+    out[k++] = hist2d::key_bits((int64_t)nx * ny), out[k++] = hist2d::BLOCK, out[k++] = lv.count, out[k++] = lv.blocks[0];
+    out[k++] = c.records_a, out[k++] = c.records_b;
+    for (const hist2d::Region &r : h) out[k++] = (int64_t)r.offset, out[k++] = (int64_t)r.bytes;
+    out[k++] = (int64_t)c.h_bytes;
+    for (const hist2d::Region &r : a) out[k++] = (int64_t)r.offset, out[k++] = (int64_t)r.bytes;
+    out[k++] = (int64_t)c.a_bytes;
+    out[k++] = (int64_t)c.bins_bytes;
+    static_assert(6 + 2 * 4 + 1 + 2 * 11 + 1 + 1 == TSP_HIST2D_LAYOUT_VALUES, "the header's count of layout values");
     return TSP_OK;
 }
 

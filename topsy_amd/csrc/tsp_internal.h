@@ -289,6 +289,10 @@ int ensure_weights(tsp_context *ctx, bool rgb);
 // tsp_kinematics.hip: the kinematic weights into p.wr / wg / wb (on ctx->stream) and the per-pixel moment maps of a kinematic image
 int launch_kinematic_weights(tsp_context *ctx);
 int launch_velocity_moments(tsp_context *ctx, const float *d_img, int64_t npix, float *d_maps);
+// tsp_hist2d.hip: weighted 2-D histograms of caller-ordered host arrays (tsp_histogram_2d); per-call DeviceScratch only, through the
+// sites of gather_scratch(); no context state
+int histogram_2d(tsp_context *ctx, int64_t n, const float *x, const float *y, const float *w, const float *v,
+                 const tsp_hist2d_spec *spec, int64_t *count_out, double *sums_out, int32_t *bin_out, tsp_hist2d_info *info_out);
 // tsp_cube.hip: the position-position-velocity cube of every resident particle (tsp_spectral_cube); per-call DeviceScratch only,
 // through the sites of gather_scratch(); no context state
 int spectral_cube(tsp_context *ctx, const Camera &cam, double v_min, double dv, int n_channels, double sigma_v, const float *sigma,

@@ -214,6 +214,10 @@ class VelocityView:
         self._ensure_rendered()
         return maps_dict(self._sph._context.velocity_moments(), self._sph.last_render_mass_scale)
 
+    def phase_diagram(self, x, y, weight="mass", value=None, **kwargs):
+        """The visualizer's phase_diagram: the particles are the visualizer's."""
+        return self._vis.phase_diagram(x, y, weight=weight, value=value, **kwargs)
+
     def get_cube(self, v_range=None, n_channels=64, sigma_v=0.0, sigma=None):
         """The spectral cube of the scene at the visualizer's camera and this view's v_ref (topsy_amd.SpectralCube: data
         (n_channels, R, R), v_edges, moment(), spectrum(), pv()): per pixel the whole distribution of the line-of-sight velocity
@@ -403,6 +407,10 @@ class VelocityFrames(FrameInterface):
     def profile(self, r_max=None, **kwargs):
         """The visualizer's profile: the camera is the visualizer's."""
         return self._vis.profile(r_max, **kwargs)
+
+    def phase_diagram(self, x, y, weight="mass", value=None, **kwargs):
+        """The visualizer's phase_diagram: the particles are the visualizer's."""
+        return self._vis.phase_diagram(x, y, weight=weight, value=value, **kwargs)
 
     def scale_to_virial(self, rho_threshold, r_max, factor=1.0):
         """The visualizer's scale_to_virial: the camera is the visualizer's."""

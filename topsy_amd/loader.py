@@ -1118,6 +1118,32 @@ class ArrayDataLoader(AbstractDataLoader):
         pos, mass, vel = check_moments_arrays(self._pos, self._mass, self._vel)
         return self._with_context(lambda ctx: compute_profile(ctx, pos, mass, vel, kwargs, G))
 
+    def _phase_array(self, role, name):
+        """The per-particle array a phase diagram names: a loader quantity (derived ones are computed on first use), "mass" or
+        "smooth".  ValueError for any other name."""
+        if name == "mass":
+            return self._mass
+        if name == "smooth":
+            return self.get_smooth()
+        if not isinstance(name, str) or name not in self.get_quantity_names():
+            raise ValueError(f"{role} = {name!r} names no per-particle array: the loader has {self.get_quantity_names()}, "
+                             f"'mass' and 'smooth'")
+        return self.get_named_quantity(name)
+
+    def phase_diagram(self, x, y, weight="mass", value=None, x_range=None, y_range=None, bins=(256, 256), x_log=True, y_log=True,
+                      edges=None, return_index=False):
+        """The PhaseDiagram (topsy_amd.phase_diagram) of two named per-particle arrays -- e.g. phase_diagram("rho", "temp"): the
+        mass in each cell of the (rho, T) plane -- found on the GPU (tsp_histogram_2d) from the host arrays.  x, y, weight and value
+        name a loader quantity ('rho', 'v_div', 'vorticity' and 'phi' are computed on first use as get_named_quantity does), "mass"
+        or "smooth"; weight=None counts particles, value=None leaves the mean and the dispersion out.  Both axes are logarithmic
+        unless told otherwise; the other keywords are topsy_amd.phase_diagram's."""
+        from . import phase
+        columns = [self._phase_array(role, name) for role, name in (("x", x), ("y", y))]
+        columns += [None if name is None else self._phase_array(role, name) for role, name in (("weight", weight), ("value", value))]
+        xa, ya, w, v, edges_x, edges_y = phase.check_phase_arguments(*columns, x_range, y_range, bins, x_log, y_log, edges)
+        return self._with_context(lambda ctx: phase.compute_phase_diagram(ctx, xa, ya, w, v, edges_x, edges_y, x_log, y_log,
+                                                                          return_index))
+
     def sample_lattice(self, lattice_spec, quantity=None):
         """{"rho", "smooth"[, "mean"]} of topsy_amd.lattice.sample on the lattice `lattice_spec` (dict: origin, du, dv, dw, shape),
         found on the GPU (tsp_sph_sample_lattice) from the host arrays in the loader's periodic box; quantity: the name of the

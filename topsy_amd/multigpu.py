@@ -256,6 +256,10 @@ class MultiGpuContext:
         """The binned shell / annulus sums of the whole (caller-ordered) snapshot, on the first context like smoothing_lengths."""
         return self.contexts[0].radial_profile(x, y, z, mass, **kwargs)
 
+    def histogram_2d(self, x, y, w=None, v=None, **kwargs):
+        """The weighted 2-D histogram of the whole (caller-ordered) arrays, on the first context like smoothing_lengths."""
+        return self.contexts[0].histogram_2d(x, y, w, v, **kwargs)
+
     def generate_synthetic(self, n_total, first=0, count=None, seed=1337, h_cap=0.0, with_quantity=False, with_rgb=False):
         count = n_total - first if count is None else count
         # the generator's index bijection makes every index range a uniform sample: contiguous shards are balanced

@@ -135,6 +135,10 @@ class SurfaceView(FrameInterface):
         """The visualizer's profile: the camera is the visualizer's."""
         return self._vis.profile(r_max, **kwargs)
 
+    def phase_diagram(self, x, y, weight="mass", value=None, **kwargs):
+        """The visualizer's phase_diagram: the particles are the visualizer's."""
+        return self._vis.phase_diagram(x, y, weight=weight, value=value, **kwargs)
+
     def scale_to_virial(self, rho_threshold, r_max, factor=1.0):
         """The visualizer's scale_to_virial: the camera is the visualizer's."""
         return self._vis.scale_to_virial(rho_threshold, r_max, factor)

@@ -370,6 +370,13 @@ class VisualizerBase(FrameInterface):
             frame = np.asarray(self.rotation_matrix, dtype=np.float64)
         return ld.profile(r_max, center=center, frame=frame, **kwargs)
 
+    def phase_diagram(self, x, y, weight="mass", value=None, **kwargs):
+        """The PhaseDiagram (topsy_amd.phase_diagram) of two of the loader's named per-particle arrays, e.g.
+        phase_diagram("rho", "temp"): ArrayDataLoader.phase_diagram's arguments (names of quantities, "mass" or "smooth"; both
+        axes logarithmic unless told otherwise).  The sums are found on the GPU from the loader's host arrays -- with several GPUs
+        on the first: there is nothing to shard."""
+        return self._array_loader("a phase diagram").phase_diagram(x, y, weight=weight, value=value, **kwargs)
+
     def rotation_curve(self, radii, eps=None, G=1.0, method="direct", theta=0.5):
         """The RotationCurve (topsy_amd.rotation_curve: v_circ and the midplane potential from direct sums of the softened forces
         at four probes per radius) of what the view shows: about -position_offset, what the view is centred on, in the frame of
