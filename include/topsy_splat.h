@@ -928,6 +928,46 @@ int tsp_spectral_cube(tsp_context *ctx, const float *M, float scale_factor, doub
 int tsp_spectral_cube_layout(int64_t n, int resolution, int n_channels, int64_t slice_option, int has_sigma,
                              int64_t *out /* TSP_CUBE_LAYOUT_VALUES */);
 
+/* Perspective view.  Every render call is orthographic.  To first order across each footprint, a perspective view of SPH particles
+ * is the orthographic view of a transformed snapshot: a particle at distance d along the optical axis is seen as if it lay on the
+ * reference plane at distance D -- position scaled by s = D / d, smoothing length h s, mass m s^2, so that the vertex weight
+ * m' / h'^2 and with it the column density along the ray through the particle's centre are unchanged.  The small-angle statement:
+ * a footprint is drawn as a disc, not as the conic the sphere projects to.  A pixel's ray that meets the particle's plane z = zv
+ * at the distance b' from its centre has the kernel sampled at b' / h; the ray's true impact parameter is
+ * b = b' sqrt(1 - sin^2(theta) cos^2(phi)) >= b' cos(theta), theta the ray's angle to the optical axis.  The sample is exact on the
+ * ray through the centre and off by at most max|g'| (2 / cos(theta)) (1 - cos(theta)) elsewhere (g the projected kernel): small
+ * while the footprint's rays stay near the axis (angular radius 2 h / d << 1 for a particle near it), second order in theta.
+ *
+ * tsp_project_perspective writes that snapshot of src's particles into dst, which the caller then renders with rotation =
+ * identity, offset = 0 and any scale: tsp_render, tsp_render_surface and everything downstream are unchanged.
+ *   Preconditions, checked before anything changes (a refused call leaves dst as it found it): src != dst, on one device
+ *   (TSP_EINVAL); both hold n > 0 particles with x, y, z, h -- the caller uploaded the same snapshot into dst once, with the same
+ *   tsp_reorder_spatial arguments where src was reordered, so that the resident orders agree index for index (TSP_ESTATE for a
+ *   missing array, TSP_EINVAL for unequal n); dst holds mass iff src does and r, g, b iff src does (TSP_ESTATE); distance finite
+ *   and > 0, near finite with 0 < near < distance, rot and offset finite (TSP_EINVAL).
+ *   Per particle i in resident order, float32, in this order of operations:
+ *     tx = x + offset[0]   ty = y + offset[1]   tz = z + offset[2]
+ *     xv = (rot[0]*tx + rot[1]*ty) + rot[2]*tz     (yv with rot[3..5], zv with rot[6..8])
+ *     d  = distance - zv          (the viewer sits at zv = +distance and looks down -z: greater z is nearer, as in the surface pass)
+ *     visible = d >= near         (false for NaN)
+ *     s  = distance / d           (IEEE division)
+ *     x' = xv*s   y' = yv*s   z' = zv   h' = h*s   m' = m*(s*s)   r' = r*(s*s)   g' = g*(s*s)   b' = b*(s*s)
+ *     not visible:  x' = y' = z' = NaN,  h' = 0,  m' = r' = g' = b' = 0     (a particle with NaN coordinates draws nothing)
+ *   dst's q is not touched (it does not depend on the camera); src is only read.
+ *   The same pass writes dst's vertex weights m' / (h' * h') and the bounds of every 512 transformed particles (chunk culling),
+ *   so the next render forms neither.  Afterwards in dst: the rgb weights are re-formed by the next rgb block, the cell grid of
+ *   tsp_get_cell_layout is gone (it described world coordinates: TSP_ESTATE), tsp_get_strata_offsets is unchanged, and
+ *   tsp_render_undo has nothing to undo.  dst stays an ordinary context: any upload into it works as before.
+ *   It allocates only what dst lacks of the weights and the bounds (once; TSP_ENOMEM leaves dst as it was) and runs on dst's
+ *   stream after what src's stream holds; it returns when the pass has finished. */
+typedef struct tsp_perspective {
+    float rot[9];      /* row-major rotation, world -> view */
+    float offset[3];   /* added to the position first */
+    float distance;    /* D: from the viewer to the reference plane zv = 0 */
+    float near;        /* particles with d < near are not drawn */
+} tsp_perspective;
+int tsp_project_perspective(tsp_context *src, tsp_context *dst, const tsp_perspective *cam);
+
 /* Surface rendering: DepthSPHWithOcclusion + ColorAsSurfaceMap (reference src/topsy/sph.py:448-656, shaders/sph.wgsl:94-122,
  * 149-158, shaders/smooth.wgsl, shaders/surface.wgsl, colormap/surface.py).  Float32 throughout, operations in the order written.
  *

@@ -485,6 +485,19 @@ def SurfaceView(visualizer, **colormap_params):
     return surface.SurfaceView(visualizer, **colormap_params)
 
 
+def PerspectiveView(visualizer, fov=60.0, near=None):
+    """`visualizer`'s scene seen by a perspective camera, for fly-throughs: a view with a visualizer's whole interface (camera,
+    quantity_name, render_mode, get_sph_image, get_sph_presentation_image, get_depth_image -- the distance from the viewer --,
+    get_presentation_image((W, H)) and its 4:2:0 form) and a camera of its own that starts at the visualizer's, plus fov (degrees,
+    inside (0, 180)), distance = scale / tan(fov / 2), near, far and dolly(delta).  The plane through the view centre fills the
+    frame as in the orthographic view; fov -> 0 tends to it.  The GPU writes a perspective-transformed copy of the snapshot into a
+    second context whenever the camera changes (tsp_project_perspective) and the unchanged pipeline draws it: a footprint is a
+    disc, exact on the ray through its centre and good while its rays make a small angle with the optical axis.  A target of
+    VisualizationRecorder, which records fov as well.  One GPU, no periodic tiling; no kinematic, cube or surface views in perspective; a second resident snapshot."""
+    from . import perspective
+    return perspective.PerspectiveView(visualizer, fov=fov, near=near)
+
+
 def VelocityView(visualizer, v_ref="center", **parameters):
     """The kinematic maps of `visualizer`'s scene (needs from_arrays(..., vel=vel)): per pixel the mass-weighted mean
     line-of-sight velocity and its dispersion along the view axis, drawn on the GPU from resident velocities.  v_ref, subtracted

@@ -21,7 +21,7 @@ ABI_VERSION = 112            # the oldest tsp_version() whose structs this bindi
                              # 116: tsp_radial_profile, 117: the kinematic maps, 119: tsp_moment_sort,
                              # 120: tsp_sph_velocity_gradient, 122: tsp_sph_sample_lattice, 123: tsp_gravity_direct,
                              # 124: tsp_gravity_tree, 125: tsp_group_potential, tsp_halo_properties, 126: tsp_spectral_cube,
-                             # 127: tsp_histogram_2d) are required by
+                             # 127: tsp_histogram_2d, 128: tsp_project_perspective) are required by
                              # name in load_library()
 PRESENT_SCALAR, PRESENT_BIVARIATE, PRESENT_RGB, PRESENT_RGB_HDR, PRESENT_MOMENT_MEAN, PRESENT_MOMENT_SIGMA = 0, 1, 2, 3, 4, 5
 LAYER_QUAD, LAYER_LINES = 0, 1
@@ -101,6 +101,11 @@ class Hist2dSpec(ctypes.Structure):
 class Hist2dInfo(ctypes.Structure):
     """struct tsp_hist2d_info."""
     _fields_ = [("n_valid", ctypes.c_int64), ("n_binned", ctypes.c_int64)]
+
+
+class Perspective(ctypes.Structure):
+    """struct tsp_perspective: view = rot @ (position + offset); the viewer sits at view z = +distance and looks down -z."""
+    _fields_ = [("rot", ctypes.c_float * 9), ("offset", ctypes.c_float * 3), ("distance", ctypes.c_float), ("near", ctypes.c_float)]
 
 
 class Lattice(ctypes.Structure):
@@ -222,6 +227,7 @@ SIGNATURES = {
     "tsp_get_cell_layout": (ctypes.c_int, [_ctx, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), _fp, _fp]),
     "tsp_get_cell_offsets": (ctypes.c_int64, [_ctx, _i64p, ctypes.c_int64]),
     "tsp_download_particles": (ctypes.c_int, [_ctx] + [_fp] * 9),
+    "tsp_project_perspective": (ctypes.c_int, [_ctx, _ctx, ctypes.POINTER(Perspective)]),
     "tsp_num_particles": (ctypes.c_int64, [_ctx]),
     "tsp_render": (ctypes.c_int, [_ctx, _fp, ctypes.c_float, _i64p, _i64p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                   ctypes.c_int, ctypes.POINTER(ctypes.c_double)]),
@@ -369,6 +375,31 @@ def lattice_struct(origin, du, dv, dw, shape):
         getattr(lat, name)[:] = a.tolist()
     lat.nu, lat.nv, lat.nw = dims
     return lat
+
+
+def perspective_struct(rot, offset, distance, near):
+    """The tsp_perspective of a (3, 3) rotation, a (3,) offset, the distance to the reference plane and the near distance, each
+    rounded to float32.  Raises ValueError for a wrong shape, a value that is not finite, distance <= 0 or near outside
+    (0, distance) -- what the library would refuse with TSP_EINVAL."""
+    cam = Perspective()
+    for name, v, shape in (("rot", rot, (3, 3)), ("offset", offset, (3,))):
+        try:
+            a = np.asarray(v, dtype=np.float32)
+        except (TypeError, ValueError):
+            raise ValueError(f"{name} must be {shape} finite numbers, not {v!r}") from None
+        if a.shape != shape or not np.isfinite(a).all():
+            raise ValueError(f"{name} must be {shape} finite numbers, not {v!r}")
+        getattr(cam, name)[:] = a.ravel().tolist()
+    try:
+        d, nr = float(np.float32(distance)), float(np.float32(near))
+    except (TypeError, ValueError):
+        raise ValueError(f"distance and near must be numbers, not {distance!r} and {near!r}") from None
+    if not (np.isfinite(d) and d > 0):
+        raise ValueError(f"distance must be finite and > 0, not {distance!r}")
+    if not (np.isfinite(nr) and 0 < nr < d):
+        raise ValueError(f"near must be finite, > 0 and < distance, not {near!r}")
+    cam.distance, cam.near = d, nr
+    return cam
 
 
 def _check(rc):
@@ -603,6 +634,17 @@ class Context:
         out = {k: np.empty(n, dtype=np.float32) for k in names}
         _check(self._lib.tsp_download_particles(self._h, *[_ptr(out.get(k)) for k in order]))
         return out
+
+    def project_perspective(self, dst, rot, offset, distance, near):
+        """Write the perspective-transformed snapshot of this context's particles into the Context `dst`, which holds the same
+        snapshot in the same resident order (tsp_project_perspective): view = rot @ (position + offset), a particle at
+        d = distance - view z is scaled by s = distance / d about the optical axis (h by s, mass and rgb by s^2) and dropped (NaN
+        position) when d < near; dst's vertex weights and chunk bounds are written by the same pass.  dst then renders with the
+        identity rotation and no offset.  rot (3, 3), offset (3,), distance and near are rounded to float32 here."""
+        if not isinstance(dst, Context):
+            raise ValueError(f"dst must be a Context, not {type(dst).__name__}")
+        cam = perspective_struct(rot, offset, distance, near)
+        _check(self._lib.tsp_project_perspective(self._h, dst._h, ctypes.byref(cam)))
 
     @property
     def num_particles(self):

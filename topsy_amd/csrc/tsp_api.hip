@@ -236,7 +236,7 @@ using namespace tsp;
 extern "C" {
 
 const char *tsp_last_error(void) { return g_err; }
-int tsp_version(void) { return 127; }     // 127: tsp_histogram_2d and tsp_histogram_2d_layout and the structs tsp_hist2d_spec / tsp_hist2d_info (weighted 2-D histograms: phase diagrams); 126: tsp_spectral_cube and tsp_spectral_cube_layout (position-position-velocity cubes of the resident particles), option "cube_slice_particles"; 125: tsp_group_potential and tsp_halo_properties (halo properties); 124: tsp_gravity_tree and the struct tsp_gravity_tree_info (Barnes-Hut tree gravity over the Morton order); 123: tsp_gravity_direct and the struct tsp_gravity_info (softened direct-sum gravity: potential, accelerations); 122: tsp_sph_sample_lattice and the struct tsp_lattice (SPH sums at the points of a lattice); 121: a failed upload is atomic (attributes: nothing changed; particles / synthetic: no particles left; groups: every member emptied); 120: tsp_sph_velocity_gradient; 119: tsp_moment_sort, TSP_PRESENT_MOMENT_MEAN / _SIGMA (the kinematic maps as the base of tsp_present / tsp_present_yuv420); 118: tsp_render_undo, tsp_group_render all-or-nothing across the members; 117: kinematic maps (tsp_upload_velocities, tsp_set_line_of_sight, TSP_MODE_KINEMATIC, tsp_velocity_moments, tsp_colormap_moment); 116: tsp_radial_profile; 115: tsp_sphere_moments; 114: tsp_fof_groups; 113: tsp_shrink_sphere_center; 112: tsp_present_surface, tsp_present_surface_yuv420; 111: tsp_content_neg_inf; 110: tsp_sph_sum; 109: tsp_present_yuv420; 108: tsp_present; 107: surface rendering; 106: tsp_smoothing_lengths; 101: tsp_stats gained ms_mega, n_mega (16 bytes); 102: the per-kernel fragment counts (32 bytes); 103: n_chunk_culled (8 bytes); 104: matrix-core / kernel-I options removed; 105: kernel M's options removed (kernel G draws the mid footprints)
+int tsp_version(void) { return 128; }     // 128: tsp_project_perspective and the struct tsp_perspective (perspective camera: the transformed snapshot into a second context); 127: tsp_histogram_2d and tsp_histogram_2d_layout and the structs tsp_hist2d_spec / tsp_hist2d_info (weighted 2-D histograms: phase diagrams); 126: tsp_spectral_cube and tsp_spectral_cube_layout (position-position-velocity cubes of the resident particles), option "cube_slice_particles"; 125: tsp_group_potential and tsp_halo_properties (halo properties); 124: tsp_gravity_tree and the struct tsp_gravity_tree_info (Barnes-Hut tree gravity over the Morton order); 123: tsp_gravity_direct and the struct tsp_gravity_info (softened direct-sum gravity: potential, accelerations); 122: tsp_sph_sample_lattice and the struct tsp_lattice (SPH sums at the points of a lattice); 121: a failed upload is atomic (attributes: nothing changed; particles / synthetic: no particles left; groups: every member emptied); 120: tsp_sph_velocity_gradient; 119: tsp_moment_sort, TSP_PRESENT_MOMENT_MEAN / _SIGMA (the kinematic maps as the base of tsp_present / tsp_present_yuv420); 118: tsp_render_undo, tsp_group_render all-or-nothing across the members; 117: kinematic maps (tsp_upload_velocities, tsp_set_line_of_sight, TSP_MODE_KINEMATIC, tsp_velocity_moments, tsp_colormap_moment); 116: tsp_radial_profile; 115: tsp_sphere_moments; 114: tsp_fof_groups; 113: tsp_shrink_sphere_center; 112: tsp_present_surface, tsp_present_surface_yuv420; 111: tsp_content_neg_inf; 110: tsp_sph_sum; 109: tsp_present_yuv420; 108: tsp_present; 107: surface rendering; 106: tsp_smoothing_lengths; 101: tsp_stats gained ms_mega, n_mega (16 bytes); 102: the per-kernel fragment counts (32 bytes); 103: n_chunk_culled (8 bytes); 104: matrix-core / kernel-I options removed; 105: kernel M's options removed (kernel G draws the mid footprints)
 int tsp_stats_size(void) { return (int)sizeof(tsp_stats); }
 
 int tsp_device_count(void) {

@@ -96,6 +96,12 @@ class VisualizationRecorder:
         self._replaying = False
         self._recording_ends_at = None
         self._t0 = None
+        if hasattr(vis, "fov"):
+            # a perspective target (topsy_amd.PerspectiveView): its field of view is part of the camera path; a visualizer's
+            # timestream keeps the desktop recorder's layout
+            self._record_properties = self._record_properties + ["fov"]
+            self._record_interpolation_class_smoothed = self._record_interpolation_class_smoothed + [SmoothedLinearInterpolator]
+            self._record_interpolation_class_unsmoothed = self._record_interpolation_class_unsmoothed + [LinearInterpolator]
         self._reset_timestream()
         vis.add_frame_listener(self._on_frame)
 
@@ -183,7 +189,9 @@ class VisualizationRecorder:
         if not set_quantity:
             exclude.add("quantity_name")
         classes = self._record_interpolation_class_smoothed if smooth else self._record_interpolation_class_unsmoothed
-        interpolators = {p: c(self._timestream[p]) for c, p in zip(classes, self._record_properties) if p not in exclude}
+        # (a timestream recorded without fov -- on a visualizer, or before the perspective view existed -- leaves it alone)
+        interpolators = {p: c(self._timestream[p]) for c, p in zip(classes, self._record_properties)
+                         if p not in exclude and p in self._timestream}
         layers_before = (vis.show_colorbar, vis.show_scalebar)
         self._replaying = True
         try:

@@ -106,7 +106,7 @@ class SPH:
             return False
         rp = self._render_progression
         if draw_reason != DrawReason.REFINE:
-            rp.select_sphere(-np.asarray(self.position_offset), self.scale * 1.2)
+            self._begin_view(rp)
             self._transform = self._get_transform_params()
         self._prepare_buffers()
         M, sf = self._transform
@@ -133,6 +133,10 @@ class SPH:
         self.last_render_blocks = n_blocks        # tsp_render calls of this frame (EXPORT: one on this backend)
         self._visualizer.particle_buffers.last_renderer = self
         return True
+
+    def _begin_view(self, rp):
+        """What a frame at a new camera does before its first block: pick the cells near the view."""
+        rp.select_sphere(-np.asarray(self.position_offset), self.scale * 1.2)
 
     def needs_refine(self):
         return self._render_progression.needs_refine()
